@@ -179,6 +179,29 @@ def other_region(args, config):
     return (args.other_steps if args.other_steps >= 0 else k), (args.other_preroll if args.other_preroll >= 0 else p)
 
 
+DUMP_BYTES = 60 << 20   # --dump-outputs: the arrays in all, with room for the .npy headers under 64 MB
+
+
+def dump_outputs(env, ids, out_dir, rank, world):
+    """--dump-outputs: what a caller of the timed path holds after its last control step -- vec_env.VecEnv.step's observations, reward, done and
+    info (success, terminal_obs) -- as out_dir/<name>.npy in float32, one row per env, and env_ids.npy (float64) naming the global env of each row.
+    Above DUMP_BYTES in all, every array keeps the same seeded sample of envs.  Every rank takes part; rank 0 writes."""
+    out = {"env_ids": np.asarray(ids, dtype=np.float64)} | {k: env.batch.get(k).astype(np.float32) for k in ("obs", "reward", "done", "success", "terminal_obs")}
+    if world > 1:
+        parts = [None] * world
+        torch.distributed.all_gather_object(parts, out)
+        out = {k: np.concatenate([p[k] for p in parts]) for k in out}
+    if rank:
+        return
+    n, row = len(out["env_ids"]), sum(a[:1].nbytes for a in out.values())
+    if n * row > DUMP_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(n, DUMP_BYTES // row, replace=False))
+        out = {k: a[keep] for k, a in out.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def step_stats(ms):
     """Distribution of the per-step durations of a timed region (HIP events around every control step on the stream it runs on): a slow window explains itself."""
     a = np.asarray(ms, dtype=np.float64)
@@ -304,6 +327,7 @@ def main():
     ap.add_argument("--other-preroll", type=int, default=-1, help="untimed launches before each secondary region (episode steps staggered as in the headline region; default: OTHER_REGION, 300 / 50)")
     ap.add_argument("--strict-collective", action="store_true", help="N > 1: exit with code 4 if the C-ABI RCCL communicator cannot be formed (default: reduce the rollout statistics through torch.distributed and say so at top level, \"collective\": \"fallback: ...\", and on stderr)")
     ap.add_argument("--secondary-only", choices=sorted(CONFIGS), default=None, help="internal: run one secondary region and print its record (the default run starts one child per configuration)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last step of the headline region returned as DIR/<name>.npy (dump_outputs)")
     args = ap.parse_args()
 
     if args.secondary_only:
@@ -384,6 +408,8 @@ def main():
     kern_ms = float(np.mean(evms))   # one control step of all B envs: dispatch order + k_step + reset passes
     ring1 = env.bank_stats()
     tier1 = env.batch.tier_stats()
+    if args.dump_outputs:
+        dump_outputs(env, ids, args.dump_outputs, rank, world)
     if os.environ.get("RSIM_BENCH_TRACE"):
         print("per-step ms:", " ".join(f"{r[0]:.2f}" for r in evms), file=sys.stderr)
     # ---- secondary regions: BASELINE configs[2..4] at their stated batch sizes, a short lockstep region each, so that the clock of whoever runs the

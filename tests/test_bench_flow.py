@@ -62,6 +62,11 @@ class _Batch:
             return torch.ones(self.n * 2, dtype=torch.int32)
         return torch.zeros(self.n, dtype=torch.int32)
 
+    def get(self, name):
+        self.log.append(("get", name))
+        rows = np.arange(self.n, dtype=np.int32 if name in ("done", "success") else np.float32)   # row i holds env i
+        return np.repeat(rows[:, None], 60, axis=1) if name in ("obs", "terminal_obs") else rows
+
 
 class _Env:
     def __init__(self, n, log):
@@ -165,6 +170,33 @@ def test_other_config_line_and_a_failing_child(monkeypatch, capsys):
     d, log = _run_main(monkeypatch, capsys, ["--steps", "2", "--warmup", "1", "--preroll", "0", "--envs-per-gpu", "4", "--no-open-loop", "--no-cpu-baseline"], child=dying)
     oc = d["config"]["other_configs"]
     assert set(oc) == {"stack", "peg", "pickplace"} and all("Memory access fault" in v["error"] for v in oc.values()) and d["value"] > 0
+
+
+def test_dump_outputs_holds_the_last_timed_step(monkeypatch, capsys, tmp_path):
+    """--dump-outputs DIR: what a caller of the timed path receives after its last step, read directly behind the headline region (before the
+    open-loop region steps the envs on), one float32 / float64 .npy per array; above the byte cap every run keeps the same seeded sample of envs."""
+    import bench
+
+    names = ("env_ids", "obs", "reward", "done", "success", "terminal_obs")
+    argv = ["--steps", "3", "--warmup", "1", "--preroll", "0", "--envs-per-gpu", "8", "--groups", "2", "--no-other-configs", "--no-cpu-baseline", "--dump-outputs"]
+    d, log = _run_main(monkeypatch, capsys, argv + [str(tmp_path / "all")])
+    first_get = log.index(("get", "obs"))
+    assert [e for e in log[:first_get] if e[0] == "step"] == [("step", 8)] * (1 + 3) and first_get < log.index(("groups", 2))
+    out = {k: np.load(tmp_path / "all" / f"{k}.npy") for k in names}
+    assert sorted(os.listdir(tmp_path / "all")) == sorted(f"{k}.npy" for k in names)
+    assert out["env_ids"].dtype == np.float64 and all(out[k].dtype == np.float32 for k in names[1:])
+    assert out["obs"].shape == out["terminal_obs"].shape == (8, 60) and out["reward"].shape == out["done"].shape == (8,)
+    assert np.array_equal(out["env_ids"], np.arange(8)) and np.array_equal(out["obs"][:, 0], out["env_ids"])
+
+    row = sum(a[:1].nbytes for a in out.values())
+    monkeypatch.setattr(bench, "DUMP_BYTES", 3 * row)
+    samples = []
+    for run in ("s1", "s2"):
+        _run_main(monkeypatch, capsys, argv + [str(tmp_path / run)])
+        samples.append({k: np.load(tmp_path / run / f"{k}.npy") for k in names})
+    ids = samples[0]["env_ids"]
+    assert len(ids) == 3 and np.all(np.diff(ids) > 0) and np.array_equal(samples[0]["obs"][:, 0], ids) and np.array_equal(samples[0]["done"], ids)
+    assert all(np.array_equal(samples[0][k], samples[1][k]) for k in names)
 
 
 def test_reference_baseline_harness_is_blocked_loudly_without_mujoco_and_runs_on_the_shim():

@@ -72,7 +72,6 @@ def test_make_extracts_pickplace_single_with_the_set_order_of_this_process():
     assert all(np.array_equal(np.ravel(flat.arrays[k]), np.ravel(gflat.arrays[k])) for k in gflat.arrays if k not in ("body_pos", "body_quat", "site_rgba"))   # visual twins (and their markers) follow the draw
 
 
-@pytest.mark.skipif(not HAVE_REF, reason="reference checkout not present (GPU box)")
 def test_kinematics_backend_serves_constructors_but_does_not_step():
     flat, _ = factory.load_shipped("lift_panda")
     kb = factory.KinematicsBackend(flat)
