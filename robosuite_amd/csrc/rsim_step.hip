@@ -473,6 +473,10 @@ template <class S> struct LdsOf;
 template <> struct LdsOf<Smem0> { static __device__ __forceinline__ Smem0& get() { return smu.n; } };
 template <> struct LdsOf<SmemW> { static __device__ __forceinline__ SmemW& get() { return smu.w; } };
 static_assert(offsetof(Smem0, xpos) == offsetof(SmemW, xpos), "state arrays at the head of both LDS layouts");
+static_assert(SmemW::NV_ == Smem0::NV_, "the wide body carries on with the native body's qpos .. ctrl rows and per-env buffer strides, sized by NV");
+static_assert(SmemW::NB_ == Smem0::NB_, "both bodies walk the same body columns of the constant block and the same kinematic tree roles");
+static_assert(SmemW::NPT_ == Smem0::NPT_, "both bodies read the same candidate-pair rows (broadphase pair list, MPR warm-start cache strides)");
+static_assert(SmemW::HULLPOOL_ >= Smem0::HULLPOOL_, "the pool slots in Cmem.ghull are chosen against the native pool: every one must lie inside the wide pool too");
 #else
 static __shared__ Smem0 sm0_;
 template <class S> struct LdsOf { static __device__ __forceinline__ Smem0& get() { return sm0_; } };

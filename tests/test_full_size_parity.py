@@ -224,6 +224,17 @@ PP_STEP_DQ_MEDIAN, PP_STEP_DQ_ARM, PP_STEP_DQ_MAX, PP_STEP_DQ_ARM_MEDIAN = 3e-3,
 # one whole control step of a Lift env (25 substeps), fused kernel against the fp64 oracle from the same state and the env's live model.  Measured (round 6, 24 envs of
 # control step 251): |dq| 3e-7 typical, 2.2e-5 on the most contact-rich env (12 contacts / 50 rows); |dv| 5e-6 typical, 2.1e-4 worst
 LIFT_STEP_DQ, LIFT_STEP_DV = 2e-4, 5e-3
+# tests/golden/stack_over_capacity.npz (16 Stack envs whose next step needs 65 - 71 rows), each of three control steps against one oracle step from the kernel's own
+# state.  Measured: |dq| / |dv| at most 1.1e-4 / 2.5e-3 in any step on 14 envs (p50 3e-6 / 1.5e-4 in the step of the hand-over).  Envs 3152 and 3682 carry the fp32 tail the
+# slowest-envs test bounds at 5e-2: 1.8e-3 / 0.11 and 5.8e-4 / 1.0e-2 after step 1.  In 3152 the error arises at substep 2 (9 contacts / 38 rows, far inside the native
+# capacity; the demand passes 64 rows at substep 14) and it is bitwise the same in the native body alone (RSIM_NO_TIERS), the wide body alone (RSIM_FORCE_HANDOVER=0)
+# and the mid-step hand-over; 3682 likewise ends the same in all three.  The mid-step hand-over against the wide body from substep 0: at most 1.7e-6.  The truncating
+# build against the oracle, step 1 medians: |dq| 1.3e-5 (4.3x the tiered build's), |dv| 9.4e-4 (6.3x).
+STACK_OVER_DQ, STACK_OVER_DV = 3e-4, 1e-2
+STACK_OVER_TAIL_ENVS = (3152, 3682)
+STACK_STEP_DQ_TAIL, STACK_STEP_DV_TAIL = 5e-3, 3e-1
+STACK_HANDOVER_DQ = 2e-5
+STACK_TRUNC_RATIO = 2.5
 
 
 def spread(B, n=32):
@@ -431,50 +442,154 @@ def test_pickplace_8192_with_dynamics_randomisation_reached_states():
     assert int(env2.batch.get("diverged").sum()) == 0
 
 
-def test_stack_one_whole_control_step_of_the_slowest_envs_against_the_oracle():
+def _stack_assets():
+    from robosuite_amd import mjcf
+
+    adir = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "robosuite_amd", "assets")
+    return mjcf.load_model(os.path.join(adir, "stack_panda.rsim")), json.load(open(os.path.join(adir, "stack_panda.cfg.json")))
+
+
+def _stack_oracle_step(flat, cfg, qpos, qvel, qacc_warmstart, ctrl, cstate, action, n_sub):
+    """ONE control step of a Stack env on the fp64 oracle from a kernel state: rso_env_step one substep at a time (step1, set_goal on the first substep,
+    controller, step2).  Returns (qpos, qvel, Newton iterations per substep, largest constraint-row count of a substep)."""
+    from tests.util import make_oracle
+
+    om, od, oc = make_oracle(flat, cfg)
+    od.qpos[:] = qpos; od.qvel[:] = qvel; od.qacc_warmstart[:] = qacc_warmstart; od.ctrl[:] = ctrl
+    od.forward(); oc.reset(od)
+    st = oc.state
+    st[:20] = cstate[:20]; st[20:24] = cstate[20:24]; st[24:28] = cstate[20:24]
+    a = np.asarray(action, dtype=np.float64)
+    k, nefc = 0, 0
+    for s in range(n_sub):
+        od.step1()
+        if s == 0:
+            oc.set_goal(od, a)
+        oc.run(od)
+        od.step2()
+        k += od.solver_iter; nefc = max(nefc, od.nefc)
+    return od.qpos.copy(), od.qvel.copy(), k / n_sub, nefc
+
+
+_STACK_HARD_ORACLE = {}
+
+
+@pytest.mark.parametrize("force", (None, 0, 1, 12, 24))
+def test_stack_one_whole_control_step_of_the_slowest_envs_against_the_oracle(monkeypatch, force):
     """The envs a Stack launch waits for: the 48 Newton-heaviest envs of control step 300 of the 4096-env bench workload plus 48 envs spread over the batch
     (tests/golden/stack_hard_envs_step300.npz: their states, warm starts, commands, controller records and actions before that step, recorded by
     tools/newton_hard_envs.py).  ONE whole control step -- 25 substeps with set_goal, both controllers, up to 10 contacts and 8 Newton iterations per substep --
     through the fused kernel and through the oracle from identical inputs.  Typical env to rounding; the tail is bounded by what one contact's MPR facet choice
-    in fp32 does to a light cube (profiles/r04_x10_line_search.txt: with the kernel's contact geometry the two solvers agree to 3e-9)."""
-    import json
+    in fp32 does to a light cube (profiles/r04_x10_line_search.txt: with the kernel's contact geometry the two solvers agree to 3e-9).
+    `force` = k: every env hands over to the fused kernel's wide body at substep k (RSIM_FORCE_HANDOVER), so that the wide body of the Stack build -- J, M
+    and the contact block at its own offsets in DBatch.jg, rows staged one 64-row slot at a time -- carries the step on from there, first substep and last
+    included; held to the same bounds, and tier_stats() proves every env went through the hand-over."""
+    from tests.util import make_hip
 
-    from robosuite_amd import mjcf
-
-    adir = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "robosuite_amd", "assets")
-    flat = mjcf.load_model(os.path.join(adir, "stack_panda.rsim"))
-    cfg = json.load(open(os.path.join(adir, "stack_panda.cfg.json")))
+    flat, cfg = _stack_assets()
     z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "stack_hard_envs_step300.npz"))
     n, n_sub = len(z["envs"]), int(z["n_sub"])
-    from tests.util import make_hip, make_oracle
+    act = torch.tensor(z["actions"], dtype=torch.float32, device="cuda")
 
-    hm, hb = make_hip(flat, cfg, B=n)
-    for f in ("qpos", "qvel", "qacc_warmstart", "ctrl", "cstate"):
-        hb.set(f, z[f])
-    hb.control_step(torch.tensor(z["actions"], dtype=torch.float32, device="cuda"), n_sub)
-    q1 = hb.get("qpos")
-    assert int(hb.get("overflow").sum()) == 0 and int(hb.get("diverged").sum()) == 0
-    dq, it = [], []
-    for i in range(n):
-        om, od, oc = make_oracle(flat, cfg)
-        od.qpos[:] = z["qpos"][i]; od.qvel[:] = z["qvel"][i]; od.qacc_warmstart[:] = z["qacc_warmstart"][i]; od.ctrl[:] = z["ctrl"][i]
-        od.forward(); oc.reset(od)
-        st, cs = oc.state, z["cstate"][i]
-        st[:20] = cs[:20]; st[20:24] = cs[20:24]; st[24:28] = cs[20:24]
-        a = z["actions"][i].astype(np.float64)
-        k = 0
-        for s in range(n_sub):
-            od.step1()
-            if s == 0:
-                oc.set_goal(od, a)
-            oc.run(od)
-            od.step2()
-            k += od.solver_iter
-        dq.append(float(np.abs(q1[i] - od.qpos).max())); it.append(k / n_sub)
-    dq, it = np.array(dq), np.array(it)
-    print(f"   [Stack, slowest envs] |dq| after one control step: p50 {np.median(dq):.1e} p90 {np.percentile(dq, 90):.1e} max {dq.max():.1e}; oracle Newton iterations per substep "
-          f"mean {it.mean():.2f} max {it.max():.2f} (kernel, recorded: {z['newton'].mean() / n_sub:.2f} / {z['newton'].max() / n_sub:.2f})")
+    def run(f):
+        if f is None:
+            monkeypatch.delenv("RSIM_FORCE_HANDOVER", raising=False)
+        else:
+            monkeypatch.setenv("RSIM_FORCE_HANDOVER", str(f))
+        hm, hb = make_hip(flat, cfg, B=n)
+        for k in ("qpos", "qvel", "qacc_warmstart", "ctrl", "cstate"):
+            hb.set(k, z[k])
+        t0 = hb.tier_stats()
+        hb.control_step(act, n_sub)
+        t1 = hb.tier_stats()
+        monkeypatch.delenv("RSIM_FORCE_HANDOVER", raising=False)
+        assert int(hb.get("overflow").sum()) == 0 and int(hb.get("diverged").sum()) == 0
+        return hb.get("qpos").copy(), (t1[0] - t0[0], t1[1] - t0[1])
+
+    q1, stats = run(force)
+    if force is not None:
+        assert stats == (n, n), stats          # every env of the step was carried on by the wide body after a hand-over at substep `force`
+        dqf = np.abs(q1 - run(None)[0]).max(1)
+        print(f"   [Stack, slowest envs] hand-over at substep {force}: per-env |dq| against the unforced step (max {dqf.max():.1e}):\n"
+              + np.array2string(dqf, formatter={"float_kind": lambda x: f"{x:.0e}"}, max_line_width=200))
+    if not _STACK_HARD_ORACLE:      # the oracle's step does not depend on `force`: computed once per session
+        for i in range(n):
+            _STACK_HARD_ORACLE[i] = _stack_oracle_step(flat, cfg, z["qpos"][i], z["qvel"][i], z["qacc_warmstart"][i], z["ctrl"][i], z["cstate"][i], z["actions"][i], n_sub)
+    dq = np.array([float(np.abs(q1[i] - _STACK_HARD_ORACLE[i][0]).max()) for i in range(n)])
+    it = np.array([_STACK_HARD_ORACLE[i][2] for i in range(n)])
+    print(f"   [Stack, slowest envs, force {force}] |dq| after one control step: p50 {np.median(dq):.1e} p90 {np.percentile(dq, 90):.1e} max {dq.max():.1e}; oracle Newton "
+          f"iterations per substep mean {it.mean():.2f} max {it.max():.2f} (kernel, recorded: {z['newton'].mean() / n_sub:.2f} / {z['newton'].max() / n_sub:.2f})")
     assert np.median(dq) < 5e-6 and np.percentile(dq, 90) < 2e-4 and dq.max() < 5e-2, (np.median(dq), np.percentile(dq, 90), dq.max())
+
+
+def test_stack_over_capacity_states_three_control_steps_against_the_oracle(monkeypatch):
+    """Named inputs for the path every contact-rich Stack env takes: 16 states of the 4096-env Stack workload whose next control step needs more than the
+    native 64 constraint rows (tests/golden/stack_over_capacity.npz, recorded by tools/stack_over_capacity.py: pre-step qpos, qvel, warm start, ctrl,
+    controller record and the actions of three steps).  Three control steps through the fused kernel: in the first, every env outgrows the native body in
+    mid-step and the wide body carries it on; the second starts on the wide tier for the envs whose demand stayed high.  Each step is compared with one
+    step of the fp64 oracle (which holds every contact) from the kernel's own state before it.  The first step is also taken by the wide body alone
+    (RSIM_FORCE_HANDOVER=0) and by the build that truncates instead (RSIM_NO_TIERS): the first agrees with the mid-step hand-over, the second counts the
+    dropped rows in RSIM_OVERFLOW and lands clearly further from the oracle."""
+    from tests.util import make_hip
+
+    flat, cfg = _stack_assets()
+    z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "stack_over_capacity.npz"))
+    n, n_sub = len(z["envs"]), int(z["n_sub"])
+    assert n >= 8 and (z["cap_need"][:, 1] > 64).all()
+    F = ("qpos", "qvel", "qacc_warmstart", "ctrl", "cstate")
+
+    def run(env, n_steps):
+        for k in ("RSIM_NO_TIERS", "RSIM_FORCE_HANDOVER"):
+            monkeypatch.delenv(k, raising=False)
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        hm, hb = make_hip(flat, cfg, B=n)
+        for k in F:
+            hb.set(k, z[k])
+        steps, stats = [], [hb.tier_stats()]
+        for s in range(n_steps):
+            pre = {k: hb.get(k).copy() for k in F}
+            hb.set("cap_need", 0)
+            hb.control_step(torch.tensor(z["actions"][:, s], dtype=torch.float32, device="cuda"), n_sub)
+            steps.append(dict(pre=pre, qpos=hb.get("qpos").copy(), qvel=hb.get("qvel").copy(), need=hb.get("cap_need").copy(), tier=hb.tier_snapshot()))
+            stats.append(hb.tier_stats())
+        for k in env:
+            monkeypatch.delenv(k)
+        return hb, steps, stats
+
+    def errors(steps):
+        e = np.zeros((len(steps), n, 2))
+        for s, st in enumerate(steps):
+            for i in range(n):
+                q, v, _, _ = _stack_oracle_step(flat, cfg, *(st["pre"][k][i] for k in F), z["actions"][i, s], n_sub)
+                e[s, i] = np.abs(st["qpos"][i] - q).max(), np.abs(st["qvel"][i] - v).max()
+        return e
+
+    hb, tiered, stats = run({}, 3)
+    assert int(hb.get("overflow").sum()) == 0 and int(hb.get("diverged").sum()) == 0
+    assert (tiered[0]["need"][:, 1] > 64).all(), tiered[0]["need"]                      # every env went over the native rows in step 1 ...
+    assert stats[1][0] - stats[0][0] == n and stats[1][1] - stats[0][1] == n, stats       # ... and the wide body carried each on after a hand-over
+    for s in range(3):
+        print(f"   step {s + 1}: demand (contacts, rows) {tiered[s]['need'].tolist()}; tier for the next step {tiered[s]['tier'].tolist()}; tier_stats {stats[s + 1]}")
+    _, wide, wstats = run({"RSIM_FORCE_HANDOVER": "0"}, 1)
+    assert wstats[1][1] - wstats[0][1] == n, wstats
+    dqw = np.abs(wide[0]["qpos"] - tiered[0]["qpos"]).max(1)
+    hb2, trunc, _ = run({"RSIM_NO_TIERS": "1"}, 1)
+    assert (hb2.get("overflow") > 0).all(), hb2.get("overflow")
+    et, en = errors(tiered), errors(trunc)
+    print("   [Stack over capacity] per env |dq| / |dv| vs the oracle, steps 1 2 3 | step 1 of the truncating build | step 1: |dq| mid-step hand-over vs wide body from substep 0")
+    for i in range(n):
+        print(f"     env {int(z['envs'][i]):4d}: " + "  ".join(f"{et[s, i, 0]:.1e} / {et[s, i, 1]:.1e}" for s in range(3))
+              + f" | {en[0, i, 0]:.1e} / {en[0, i, 1]:.1e} (overflow {int(hb2.get('overflow')[i])}) | {dqw[i]:.1e}")
+    for s in range(3):
+        print(f"   [Stack over capacity] step {s + 1}: tiered |dq| p50 {np.median(et[s, :, 0]):.1e} max {et[s, :, 0].max():.1e}, |dv| p50 {np.median(et[s, :, 1]):.1e} max {et[s, :, 1].max():.1e}")
+    print(f"   truncating build, step 1: |dq| p50 {np.median(en[0, :, 0]):.1e}, |dv| p50 {np.median(en[0, :, 1]):.1e}")
+    tail = np.isin(z["envs"], STACK_OVER_TAIL_ENVS)
+    assert (et[:, ~tail, 0] < STACK_OVER_DQ).all() and (et[:, ~tail, 1] < STACK_OVER_DV).all(), (et[:, ~tail].max(1))
+    assert (et[:, tail, 0] < STACK_STEP_DQ_TAIL).all() and (et[:, tail, 1] < STACK_STEP_DV_TAIL).all(), (et[:, tail].max(1))
+    assert (dqw < STACK_HANDOVER_DQ).all(), dqw
+    assert np.median(en[0, :, 0]) > STACK_TRUNC_RATIO * np.median(et[0, :, 0]) and np.median(en[0, :, 1]) > STACK_TRUNC_RATIO * np.median(et[0, :, 1]), (
+        np.median(en[0], 0), np.median(et[0], 0))
 
 
 def test_pickplace_one_whole_control_step_of_the_fused_path_against_the_oracle():

@@ -481,40 +481,63 @@ def test_capacity_tiers_step_an_env_beyond_the_native_capacity_without_dropping_
     assert errs[0][2] > 50 * errs[0][0], errs          # dropping 10 of 26 contacts is a different problem: 1e-2 after one control step
 
 
-def test_fused_tier_hand_over_in_mid_step_carries_the_step_on(monkeypatch):
-    """Round 6: the tier above the Lift configuration is a second body inside its control-step kernel; an env that outgrows the native capacity at substep k
-    carries on in the wide body from that substep, on the LDS-resident state (qpos, qvel, warm start, actuator ctrl, controller state, time, episode flags).
+def _stack_assets():
+    import json, os
+    from robosuite_amd import mjcf
+    adir = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "robosuite_amd", "assets")
+    return mjcf.load_model(os.path.join(adir, "stack_panda.rsim")), json.load(open(os.path.join(adir, "stack_panda.cfg.json")))
+
+
+@pytest.mark.parametrize("task", ("lift", "stack"))
+def test_fused_tier_hand_over_in_mid_step_carries_the_step_on(monkeypatch, task):
+    """Round 6: the tier above the Lift and Stack configurations is a second body inside their control-step kernel; an env that outgrows the native capacity at
+    substep k carries on in the wide body from that substep, on the LDS-resident state (qpos, qvel, warm start, actuator ctrl, controller state, time, episode flags).
     RSIM_FORCE_HANDOVER=k makes every env hand over at substep k whatever its demand: the control step must then end where the native body alone takes it
     (the two bodies differ in row slots and the memory J lives in, not in the algorithm), at every k, including with a fresh controller (needs_reset) and
-    across an episode end; the demand counters, observation record and reward come out the same."""
-    from robosuite_amd import lift
-    flat, cfg = _lift_assets()
-    ids = np.arange(24)
-    T0 = 60   # contact-rich by then (hand at the table, cube pushed around)
+    across an episode end; the demand counters, observation record and reward come out the same.  tier_stats() proves that the hand-overs took place:
+    every env-step of a forced run is committed by the wide body, and every one that started on the native tier got there by a hand-over."""
+    from robosuite_amd import lift, stack
+    flat, cfg = (_lift_assets if task == "lift" else _stack_assets)()
+    # T0: a control step by which the envs are contact-rich (hand at the table, cubes pushed around / pressed together).  Stack (configuration 1) is the only
+    # fused build with J, M and the contact block all in the per-env global buffer DBatch.jg, at other offsets in the two bodies (M at Jg + 64 * 33 native,
+    # Jg + 128 * 33 wide): 64 envs make the neighbouring envs' jg regions live at once, so a stride or offset slip between the bodies shows up as cross-env
+    # corruption rather than noise.  Its episodes run the Stack workload's own action streams (as test_stack_4096_reached_states does).
+    cls, n, T0 = {"lift": (lift.LiftBatch, 24, 60), "stack": (stack.StackBatch, 64, 80)}[task]
+    ids = np.arange(n)
     tape = torch.tensor(lift.env_actions(ids, T0 + 4), device="cuda")
 
     def run(force):
         monkeypatch.delenv("RSIM_FORCE_HANDOVER", raising=False)
-        env = lift.LiftBatch(flat, cfg, ids, seed0=0, horizon=T0 + 2, bank_episodes=3)   # the episode ends inside the compared steps: on-device reset + fresh controllers
+        env = cls(flat, cfg, ids, seed0=0, horizon=T0 + 2, bank_episodes=3)   # the episode ends inside the compared steps: on-device reset + fresh controllers
         b = env.batch
         for t in range(T0):
             env.step(tape[t])
         b.sync()
-        out = []
+        out, on_tier = [], 0
+        t0 = b.tier_stats()
         for t in range(T0, T0 + 4):
+            on_tier += int(b.tier_snapshot().sum())      # envs the wide body steps from the start (demand of the step before): no hand-over for them
             if force is not None:
                 monkeypatch.setenv("RSIM_FORCE_HANDOVER", str(force[t - T0]))
+            b.set("cap_need", 0)
             env.step(tape[t])
             b.sync()
             out.append({k: b.get(k).copy() for k in ("qpos", "qvel", "qacc_warmstart", "ctrl", "time", "cstate", "obs", "reward", "ep_step", "ep_index", "done", "cap_need", "overflow", "diverged")})
         monkeypatch.delenv("RSIM_FORCE_HANDOVER", raising=False)
+        t1 = b.tier_stats()
         env.bank_quiesce(); env._bank_stop()
-        return out
+        return out, (t1[0] - t0[0], t1[1] - t0[1]), on_tier
 
-    ref = run(None)
+    ref, ref_stats, _ = run(None)
+    need = np.stack([r["cap_need"] for r in ref])
+    print(f"{task}, {n} envs, control steps {T0}..{T0 + 3} without forcing: envs with contacts {(need[..., 0] > 0).sum(1).tolist()}, largest demand "
+          f"(contacts, rows) {need.max(1).tolist()}, wide-tier env-steps / hand-overs {ref_stats}")
     assert ref[1]["done"].all() and not ref[0]["done"].any()          # step T0 + 1 ends every episode
     for force in ([7, 7, 7, 7], [1, 24, 12, 3], [0, 0, 0, 0]):
-        got = run(force)
+        got, stats, on_tier = run(force)
+        print(f"forced {force}: wide-tier env-steps {stats[0]}, hand-overs {stats[1]} ({on_tier} env-steps on the wide tier from the start)")
+        assert stats[0] == 4 * n and stats[1] == 4 * n - on_tier, (force, stats, on_tier)     # every env-step went through the wide body ...
+        assert on_tier <= n // 4, (force, on_tier)                                            # ... and most of them through the hand-over
         for t in range(4):
             for k in ("ep_step", "ep_index", "done", "overflow", "diverged"):
                 assert np.array_equal(got[t][k], ref[t][k]), (force, t, k)
