@@ -204,12 +204,16 @@ enum rsim_field {
                         *               sizes the compiled capacities against a workload (bench.py reports the maxima) */
   RSIM_QFRC_APPLIED,   /* [B,nv]       mjData.qfrc_applied: user-specified generalised forces, added to the smooth forces by rsim_forward / rsim_step1 / rsim_step2 /
                         *               rsim_step (the B = 1 compatibility entries: models/grippers/gripper_tester.py:197-202 writes its gravity compensation
-                        *               there); zeroed by rsim_reset.  The fused rsim_control_step does not read it -- nothing on robosuite's env.step path
-                        *               writes qfrc_applied */
+                        *               there), and by rsim_control_step once rsim_set_applied_forces(b, 1) enabled it; zeroed by rsim_reset and, where it is
+                        *               read, by the on-device episode restart.  By default the fused rsim_control_step does not read it -- nothing on robosuite's
+                        *               env.step path writes qfrc_applied */
   RSIM_POLISH,         /* [B] int32    wide configurations, debug entries: how the fp64 polish behind the Newton iteration of the last substep ended (no MuJoCo counterpart;
                         *               solve_newton in csrc/rsim_step.hip): 10000 x passes + 100000 x floor(-log10 of the scaled fp64 gradient at the accepted point)
                         *               + 10^7 x exit (1 gradient below tolerance, 2 improvement below tolerance, 3 pass budget,
                         *               5 direction was no descent direction, 6 a step raised the objective; 0 not run) */
+  RSIM_XFRC_APPLIED,   /* [B,nbody,6]  mjData.xfrc_applied: a Cartesian wrench per body -- force (3) then torque (3), world coordinates, applied at the body's COM
+                        *               (xipos).  Added as J^T wrench to the smooth forces (mj_xfrcAccumulate) and to the body's cfrc_ext for the <force> / <torque>
+                        *               sensors (mj_rnePostConstraint) wherever RSIM_QFRC_APPLIED is honoured, under the same switch; zeroed like it */
   RSIM_FIELD_COUNT
 };
 #define RSIM_PATCH_TASK_OBJECT (-1)   /* rsim_set_reset_bank patch index: this column of a reset row is the episode's RSIM_TASK_OBJECT, not a float-table entry */
@@ -325,6 +329,12 @@ int rsim_param_offset(const rsim_batch* b, const char* field, int elem);
  * longest in the previous control step (contact-rich envs stay so for many steps) are handed to the first workgroups, which shortens the
  * tail of a launch; 0: env i = workgroup i. */
 int rsim_set_schedule(rsim_batch* b, int longest_first);
+/* External forces in the fused control step (off by default: no control-step kernel reads RSIM_QFRC_APPLIED / RSIM_XFRC_APPLIED and every result is what it
+ * is without them).  enable = 1: every substep of rsim_control_step adds qfrc_applied + J^T xfrc_applied to the smooth forces, as mj_fwdAcceleration does.
+ * The debug entries (rsim_forward, rsim_step*, rsim_step2_last) honour both arrays either way.  Wherever the arrays are read -- the control step with the
+ * switch on, rsim_step2_last always -- the on-device episode restart zeroes both arrays of an env in the launch that reports its RSIM_DONE (mj_resetData, as
+ * rsim_reset does), so a wrench written after that applies to the new episode; with the switch off the control step leaves them as they are. */
+int rsim_set_applied_forces(rsim_batch* b, int enable);
 /* Stream groups of rsim_control_step (no reference counterpart; results do not depend on it).  A control step lasts as long as its slowest env
  * (contact-rich envs take 3-4 x the median) and the envs are independent, so with groups = G > 1 the batch is stepped as G contiguous env
  * blocks, each on its own HIP stream: block g's step t + 1 starts as soon as ITS envs have finished step t, filling the CUs that the other

@@ -19,7 +19,8 @@ _LIB = None
 # enum rsim_field (include/rsim.h)
 FIELDS = ["qpos", "qvel", "qacc_warmstart", "ctrl", "time", "cstate", "xpos", "xquat", "qM", "qfrc_bias", "qfrc_passive", "qfrc_actuator",
           "qfrc_constraint", "qacc", "cdof", "rootcom", "contact", "efc_force", "ncon", "nefc", "niter", "obs", "reward", "success", "done", "ep_step",
-          "ep_index", "diverged", "overflow", "bank_stale", "terminal_obs", "sensordata", "task_object", "cap_need", "qfrc_applied", "polish"]
+          "ep_index", "diverged", "overflow", "bank_stale", "terminal_obs", "sensordata", "task_object", "cap_need", "qfrc_applied", "polish",
+          "xfrc_applied"]
 FIELD_ID = {n: i for i, n in enumerate(FIELDS)}
 INT_FIELDS = {"polish", "ncon", "nefc", "niter", "success", "done", "ep_step", "ep_index", "diverged", "overflow", "bank_stale", "task_object", "cap_need"}
 CON_REC = 24
@@ -243,6 +244,7 @@ def lib():
         L.rsim_wavelog.argtypes = [vp, vp]
         L.rsim_pairlog.argtypes = [vp, vp]
         L.rsim_set_schedule.argtypes = [vp, C.c_int]
+        L.rsim_set_applied_forces.argtypes = [vp, C.c_int]
         L.rsim_set_stream_groups.argtypes = [vp, C.c_int]
         L.rsim_group_stream.restype = vp; L.rsim_group_stream.argtypes = [vp, C.c_int]
         L.rsim_profile_env.argtypes = [vp, C.c_int]
@@ -439,7 +441,8 @@ class HipBatch:
                        "qfrc_actuator": (B, nv), "qfrc_constraint": (B, nv), "qacc": (B, nv), "cdof": (B, nv, 6), "rootcom": (B, nb, 3),
                        "contact": (B, self.maxcon, CON_REC), "efc_force": (B, self.maxefc), "ncon": (B,), "nefc": (B,), "niter": (B,),
                        "obs": (B, model.nobs), "reward": (B,), "success": (B,), "done": (B,), "ep_step": (B,), "ep_index": (B,), "diverged": (B,), "overflow": (B,), "bank_stale": (B,), "terminal_obs": (B, model.nobs),
-                       "sensordata": (B, int(m.arrays["sensor_dim"].sum()) if getattr(m, "nsensor", 0) else 0), "task_object": (B,), "cap_need": (B, 2), "qfrc_applied": (B, m.nv), "polish": (B,)}
+                       "sensordata": (B, int(m.arrays["sensor_dim"].sum()) if getattr(m, "nsensor", 0) else 0), "task_object": (B,), "cap_need": (B, 2), "qfrc_applied": (B, m.nv), "polish": (B,),
+                       "xfrc_applied": (B, nb, 6)}
 
     # ---- state access (host copies) --------------------------------------------------------
     def get(self, name):
@@ -636,6 +639,11 @@ class HipBatch:
         out = np.zeros((self.B, 8), dtype=np.uint64)
         _chk(self._L.rsim_wavelog(self.ptr, out.ctypes.data))
         return out
+
+    def set_applied_forces(self, enable=True):
+        """External forces in control_step (include/rsim.h rsim_set_applied_forces): every substep adds qfrc_applied + J^T xfrc_applied to the smooth
+        forces, and an on-device episode restart zeroes both arrays of the env.  Off by default; the debug entries honour both arrays either way."""
+        _chk(self._L.rsim_set_applied_forces(self.ptr, int(bool(enable))))
 
     def set_schedule(self, longest_first=True):
         """Dispatch order of control_step: slowest envs of the previous step first (default) or identity."""

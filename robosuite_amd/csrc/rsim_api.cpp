@@ -206,6 +206,7 @@ struct rsim_batch {
   int ord_valid[2];   // order2[k] holds a dispatch order (its event has been recorded)
   long nstep;         // one-launch control steps issued since the schedule was (re)started
   int schedule;       // 1 = reorder before every control step (default), 0 = identity order
+  int applied;        // rsim_set_applied_forces: control steps add qfrc_applied + J^T xfrc_applied (RF_APPLIED)
   // stream groups: control steps of env block g run on gstream[g]; `forked` = the group streams hold work the main stream has not waited for
   int groups, ngroups, forked;   // streams created, groups in use (1 = everything on the main stream)
   hipStream_t gstream[RSIM_MAX_GROUPS];
@@ -976,7 +977,7 @@ extern "C" int rsim_batch_create(rsim_model* m, int B, int device, int per_env, 
       {RSIM_BANK_STALE, (void**)&db.bank_stale, (size_t)B, 1}, {RSIM_TERMINAL_OBS, (void**)&db.term_obs, (size_t)B * (m->has_task ? m->task.nobs : 0), 0},
       {RSIM_SENSORDATA, (void**)&db.sensordata, (size_t)B * m->nsensordata, 0}, {RSIM_TASK_OBJECT, (void**)&db.task_object, (size_t)B, 1},
       {RSIM_CAP_NEED, (void**)&db.cap_need, (size_t)B * 2, 1}, {RSIM_QFRC_APPLIED, (void**)&db.qfrc_applied, (size_t)B * nv, 0},
-      {RSIM_POLISH, (void**)&db.polish, (size_t)B, 1}};
+      {RSIM_POLISH, (void**)&db.polish, (size_t)B, 1}, {RSIM_XFRC_APPLIED, (void**)&db.xfrc_applied, (size_t)B * nb * 6, 0}};
   for (auto& fd : fields) {
     if (dalloc((float**)fd.p, fd.n)) return 1;
     b->fptr[fd.id] = *fd.p; b->fcount[fd.id] = fd.n; b->fis_int[fd.id] = fd.is_int;
@@ -1040,6 +1041,7 @@ extern "C" int rsim_reset(rsim_batch* b, const uint8_t* mask) { if (join_groups(
     HIPCHK(hipMemset(b->db.qacc_ws, 0, (size_t)B * nv * sizeof(float)));
     HIPCHK(hipMemset(b->db.ctrl, 0, (size_t)B * nu * sizeof(float)));
     HIPCHK(hipMemset(b->db.qfrc_applied, 0, (size_t)B * nv * sizeof(float)));
+    HIPCHK(hipMemset(b->db.xfrc_applied, 0, (size_t)B * m->nbody * 6 * sizeof(float)));
     HIPCHK(hipMemset(b->db.time, 0, (size_t)B * sizeof(float)));
     HIPCHK(hipMemset(b->db.cstate, 0, (size_t)B * b->cs * sizeof(float)));
     HIPCHK(hipMemset(b->db.ep_step, 0, (size_t)B * sizeof(int))); HIPCHK(hipMemset(b->db.ep_index, 0, (size_t)B * sizeof(int)));
@@ -1052,6 +1054,7 @@ extern "C" int rsim_reset(rsim_batch* b, const uint8_t* mask) { if (join_groups(
       HIPCHK(hipMemset(b->db.qacc_ws + (size_t)e * nv, 0, nv * sizeof(float)));
       HIPCHK(hipMemset(b->db.ctrl + (size_t)e * nu, 0, nu * sizeof(float)));
       HIPCHK(hipMemset(b->db.qfrc_applied + (size_t)e * nv, 0, nv * sizeof(float)));
+      HIPCHK(hipMemset(b->db.xfrc_applied + (size_t)e * m->nbody * 6, 0, m->nbody * 6 * sizeof(float)));
       HIPCHK(hipMemset(b->db.time + e, 0, sizeof(float)));
       HIPCHK(hipMemset(b->db.cstate + (size_t)e * b->cs, 0, b->cs * sizeof(float)));
       HIPCHK(hipMemset(b->db.ep_step + e, 0, sizeof(int))); HIPCHK(hipMemset(b->db.done + e, 0, sizeof(int))); HIPCHK(hipMemset(b->db.needs_reset + e, 0, sizeof(int)));
@@ -1195,6 +1198,7 @@ static int launch(rsim_batch* b, const float* actions, int n_sub, int flags) {
   const int WCN = 2 + 2 * RSIM_MAX_GROUPS;   // list lengths per step parity
   HIPCHK(hipSetDevice(b->device));
   if (sync_controller(b)) return 1;
+  if (b->applied) flags |= RF_APPLIED;
   // capacity tiers apply to the fused control step only (the debug entries keep the native capacity and count what they drop in RSIM_OVERFLOW)
   const bool tiered = b->cfg_w >= 0 && (flags & RF_EPISODE) && (flags & RF_CTRL) && !(flags & RF_DEBUG);
   b->db.tier_cur = tiered ? b->d_tier[b->tier_flip] : nullptr; b->db.tier_next = tiered ? b->d_tier[b->tier_flip ^ 1] : nullptr;
@@ -1626,6 +1630,7 @@ extern "C" int rsim_profile(rsim_batch* b, int enable, unsigned long long* out, 
   return 0;
 }
 
+extern "C" int rsim_set_applied_forces(rsim_batch* b, int enable) { b->applied = enable ? 1 : 0; return 0; }
 extern "C" int rsim_set_schedule(rsim_batch* b, int longest_first) {
   b->schedule = longest_first ? 1 : 0; b->have_cost = 0;
   if (b->ostream) { HIPCHK(hipSetDevice(b->device)); HIPCHK(hipStreamSynchronize(b->ostream)); }

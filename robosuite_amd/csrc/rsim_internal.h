@@ -203,7 +203,10 @@ struct DBatch {
   float* sensordata;     // [B][nsensordata] (debug build of the kernel: rsim_step.hip sensor_acc)
   int* bpl;              // [B][5][64] or null: broadphase pair list (rsim_step.hip collision(): sphere centres at build time, packed pair constants, pair indices)
   int* polish;           // [B] RSIM_POLISH: how the fp64 polish of the last substep's solve ended (debug entries only)
-  float* qfrc_applied;   // [B][nv] mjData.qfrc_applied: added to the smooth forces by the debug form of the kernel (rsim_forward / step1 / step2 / step); the fused control step ignores it
+  float* qfrc_applied;   // [B][nv] mjData.qfrc_applied: added to the smooth forces by the debug form of the kernel (rsim_forward / step1 / step2 / step), and by the
+                         // control step under RF_APPLIED (rsim_set_applied_forces)
+  float* xfrc_applied;   // [B][nbody][6] mjData.xfrc_applied (force, torque; world frame, at the body COM): J^T of each wrenched body's COM added to the same
+                         // smooth forces, under the same conditions; part of cfrc_ext for the force / torque sensors
   float* jg;             // RSIM_JGLOBAL builds: per-env scratch in global memory, [B][jg_stride] floats: the constraint Jacobian, NEFC * (NV + 1), then (RSIM_MGLOBAL) the mass matrix, NV * (NV + 1); null otherwise
   long long jg_stride;   // floats per env = the largest need of the configurations that step this batch (native and wide tier): ONE stride for all of them --
                          // with per-configuration strides the wide pass's env i overlapped the native pass's envs 2 i, 2 i + 1 while both passes were running
@@ -265,4 +268,5 @@ enum {
   RF_EPISODE = 128,  // episode step counter, done flag, on-device reset from the bank
   RF_RESET_ONLY = 256,  // only the envs whose needs_reset flag is set (the reset-observation pass after a control step)
   RF_NOSTORE = 512,     // debug form only: leave the state arrays (qpos .. time, warm start, controller state) as they are -- the refresh of the derived arrays on read
+  RF_APPLIED = 1024,    // control step: add qfrc_applied + J^T xfrc_applied to the smooth forces, zero both at an on-device restart (the debug form: always)
 };

@@ -1821,8 +1821,9 @@ struct Sim {
   // is simply run again (the state has not changed); then lane = body:
   //   cacc_b += sum over the dofs that move b of cdof_i qacc_i;  f_b = cinert_b (cacc_b - g) + cvel_b x* (cinert_b cvel_b) - (contact wrenches on b),
   // all about the subtree COM of b's tree; lane = sensor sums f over the site body's subtree (ancestor masks) and expresses the force / the moment
-  // about the site in the site frame.
-  __device__ __forceinline__ void sensor_acc(V3 xp, Q4 xq, float* out) {
+  // about the site in the site frame.  A body's external wrench (xfa / xmask, as actuation_acceleration takes them) is part of its cfrc_ext, as
+  // mj_rnePostConstraint has it: the sensor lane takes the wrenches of the subtree off its sum.
+  __device__ __forceinline__ void sensor_acc(V3 xp, Q4 xq, float* out, gcf xfa = nullptr, u64 xmask = 0) {
     velocity(xp, xq);
     const LaneConst K = fetchK();
     const int nb = m.nbody, nv = m.nv;
@@ -1863,6 +1864,13 @@ struct Sim {
         V3 wa = v3(0, 0, 0), wl = v3(0, 0, 0);
         for (int d = 1; d < nb; d++)
           if ((mask2(IO_body_ancmask, d) >> b0) & 1ull) { wa = wa + ld3(sm.u.v.cf + FS * d); wl = wl + ld3(sm.u.v.cf + FS * d + 3); }
+        for (u64 bm = xmask; bm; bm &= bm - 1) {   // external wrenches on the subtree: a loop over the wrenched bodies
+          const int d = __builtin_ctzll(bm);
+          if (!((mask2(IO_body_ancmask, d) >> b0) & 1ull)) continue;
+          const V3 f = ld3(xfa + 6 * d), tq = ld3(xfa + 6 * d + 3);
+          const V3 xip = ld3(sm.xpos + 3 * d) + qrot(ldq(sm.xquat + 4 * d), ld3(&FP(FO_body_ipos, 3 * d)));
+          wa = wa - (tq + cross(xip - ld3(sm.rootcom + 3 * cm->broot[d]), f)); wl = wl - f;
+        }
         const M3 R = ldm(sm.smat + 9 * site);
         r = type == 0 ? mtv(R, wl) : mtv(R, wa - cross(ld3(sm.spos + 3 * site) - ld3(sm.rootcom + 3 * cm->broot[b0]), wl));
       }
@@ -2370,7 +2378,6 @@ struct Sim {
   // the 256-register build more in spills than the list saves.
   int task_obj = 0;                     // PickPlace single-object mode 1: this env's object (DBatch.task_object)
   int act_n = -1;                       // pairs on the list (-1: none)
-  float applied = 0.f;   // this lane's dof: mjData.qfrc_applied (RSIM_QFRC_APPLIED), read by the debug form of the kernel only (step_body)
   int __attribute__((address_space(1)))* bpl = nullptr;   // [0..2][lane g]: centre of geom g's bounding sphere when the list was built; [3][lane i]: packed
                                                           // constants (geom1 | geom2 << 8 | enabled << 16) of the i-th listed pair; [4][lane i]: its index
   // one candidate pair: does it pass the broadphase now (pass), could it within `reach` (near: bounding spheres / plane distance only)
@@ -2903,7 +2910,12 @@ struct Sim {
   }
 
   // ---------------------------------------------------------------- actuation / smooth acceleration
-  __device__ __forceinline__ void actuation_acceleration() {
+  // External forces (mj_xfrcAccumulate [3P]), when the caller passes them: qfa = this env's mjData.qfrc_applied row, xfa = its xfrc_applied rows
+  // ([nbody][6]: force, torque in world coordinates at the body COM), xmask = the bodies whose wrench is non-zero (step_body, once per launch).
+  // qfrc_applied is read from global memory here -- not held in a register across the substep loop -- and every wrenched body adds, on the dofs
+  // that move it, the transposed Jacobian of its COM: lane j += cdof_ang_j . torque + (cdof_lin_j + cdof_ang_j x (xipos_b - subtree COM)) . force
+  // (jac_col).  The loop over the bodies is wave-uniform.
+  __device__ __forceinline__ void actuation_acceleration(gcf qfa = nullptr, gcf xfa = nullptr, u64 xmask = 0) {
     const LaneConst K = fetchK();
     const int nv = m.nv;
     if (lane < NV16) sm.qfrc_actuator[lane] = 0.f;
@@ -2920,7 +2932,16 @@ struct Sim {
     SYNC();
     float qs = 0.f;
     if (lane < nv) {
-      qs = sm.qfrc_passive[lane] - sm.qfrc_bias[lane] + sm.qfrc_actuator[lane] + applied;   // mjData.qfrc_applied: the debug form only (0 in the fused kernels)
+      qs = sm.qfrc_passive[lane] - sm.qfrc_bias[lane] + sm.qfrc_actuator[lane];
+      if (qfa) qs += qfa[lane];
+      for (u64 bm = xmask; bm; bm &= bm - 1) {
+        const int bb = __builtin_ctzll(bm);
+        if (!((cm->bdofs[bb] >> lane) & 1)) continue;
+        const V3 f = ld3(xfa + 6 * bb), tq = ld3(xfa + 6 * bb + 3);
+        const V3 xip = ld3(sm.xpos + 3 * bb) + qrot(ldq(sm.xquat + 4 * bb), ld3(&FP(FO_body_ipos, 3 * bb)));
+        const S6 cd = ld6(sm.cdof + CS6 * lane);
+        qs += dot(cd.a, tq) + dot(cd.l + cross(cd.a, xip - ld3(sm.rootcom + 3 * cm->broot[bb])), f);
+      }
       sm.qfrc_smooth[lane] = qs;
     }
     float as;
@@ -4443,7 +4464,20 @@ __device__ __forceinline__ bool step_body(const DModel& m, const DBatch& b, cons
   if constexpr (Sim<SM>::JG) sim.Jg = (gwf)(b.jg + (size_t)env * b.jg_stride);   // one stride for every configuration that steps envs of this batch (the native and the wide pass run side by side)
   if constexpr (Sim<SM>::MG) sim.Mg = sim.Jg + SM::NEFC_ * SM::JS_;
   if (lane < csl) sm.cstate[lane] = resume ? ho->cstate : sim.cst[lane];
-  if constexpr (DBG) if (b.qfrc_applied && lane < m.nv) sim.applied = b.qfrc_applied[(size_t)env * m.nv + lane];   // user forces of the B = 1 shim entries (GripperTester's gravity compensation)
+  // external forces, mjData.qfrc_applied / xfrc_applied: read by the debug form always (the B = 1 shim entries: GripperTester's gravity compensation), by the
+  // control step when the batch enabled them (rsim_set_applied_forces -> RF_APPLIED, a kernel argument).  One lane per body tests its wrench once per launch;
+  // the ballot (an SGPR pair) is what the substeps loop over.  An env handed to the wide body in mid-step tests again there: the same rows, unchanged within a launch.
+  gcf qfa = nullptr, xfa = nullptr;
+  u64 xmask = 0;
+  if (DBG || (flags & RF_APPLIED)) {
+    if (b.qfrc_applied) qfa = (gcf)(b.qfrc_applied + (size_t)env * m.nv);
+    if (b.xfrc_applied) {
+      xfa = (gcf)(b.xfrc_applied + (size_t)env * m.nbody * 6);
+      bool nz = false;
+      if (lane < m.nbody) for (int k = 0; k < 6; k++) nz |= xfa[6 * lane + k] != 0.f;
+      xmask = __ballot(nz);
+    }
+  }
   if (lane == 0) { sm.ncon = 0; sm.nefc = 0; sm.niter = 0; sm.polish = 0; }
   sim.load_opt();
   sim.init_lds();
@@ -4504,7 +4538,7 @@ __device__ __forceinline__ bool step_body(const DModel& m, const DBatch& b, cons
     }
     if (flags & RF_ACTSOLVE) {
       sim.phase();
-      sim.actuation_acceleration();
+      sim.actuation_acceleration(qfa, xfa, xmask);
       sim.pf.mark(RP_ACT);
       sim.phase();
       sim.fwd_constraint();
@@ -4512,7 +4546,7 @@ __device__ __forceinline__ bool step_body(const DModel& m, const DBatch& b, cons
       sim.pf.count(RP_N_CON, sm.ncon);
       sim.pf.count(RP_N_EFC, sm.nefc);
       if constexpr (DBG) {
-        if ((flags & RF_DEBUG) && b.sensordata && m.nsensor > 0 && sub == n_sub - 1) { sim.phase(); sim.sensor_acc(xp, xq, b.sensordata + (size_t)env * m.nsensordata); }
+        if ((flags & RF_DEBUG) && b.sensordata && m.nsensor > 0 && sub == n_sub - 1) { sim.phase(); sim.sensor_acc(xp, xq, b.sensordata + (size_t)env * m.nsensordata, xfa, xmask); }
       }
     }
     if (flags & RF_INTEGRATE) {
@@ -4595,6 +4629,13 @@ __device__ __forceinline__ bool step_body(const DModel& m, const DBatch& b, cons
       time = 0.f;
       st = 0;
       if (sim.mprc) for (int p2 = lane; p2 < m.npair; p2 += 64) sim.mprc[Sim<SM>::MPRC * p2 + 3] = 0.f;   // the new episode's narrow phase starts cold, as after a host reset
+      // mj_resetData: the new episode starts without external forces, wherever they are read -- the control step with the switch on, the debug form (the
+      // host-controller path, rsim_step2_last) always; a wrench the caller writes after seeing `done` acts on it.  With the switch off the control step
+      // neither reads nor writes them.
+      if (DBG || (flags & RF_APPLIED)) {
+        for (int i = lane; i < m.nv; i += 64) b.qfrc_applied[(size_t)env * m.nv + i] = 0.f;
+        for (int i = lane; i < m.nbody * 6; i += 64) b.xfrc_applied[(size_t)env * m.nbody * 6 + i] = 0.f;
+      }
       if (lane == 0) { b.ep_index[env] = ep; b.needs_reset[env] = 1; }
       SYNC();
       // the patched float-table entries change this env's constant block: the host follows this launch with k_prepare over the envs whose

@@ -85,7 +85,7 @@ class KinematicsBackend:
         f64 = lambda n: np.zeros(int(n), dtype=np.float64)   # noqa: E731
         nmocap = int(m.arrays["nmocap"][0]) if "nmocap" in m.arrays else 0
         self.d = {"qpos": np.array(m.qpos0, dtype=np.float64).ravel().copy(), "qvel": f64(m.nv), "qacc": f64(m.nv), "qacc_warmstart": f64(m.nv), "ctrl": f64(m.nu),
-                  "qfrc_applied": f64(m.nv), "mocap_pos": f64(3 * nmocap), "mocap_quat": f64(4 * nmocap), "xpos": f64(3 * m.nbody), "xquat": f64(4 * m.nbody),
+                  "qfrc_applied": f64(m.nv), "xfrc_applied": f64(6 * m.nbody), "mocap_pos": f64(3 * nmocap), "mocap_quat": f64(4 * nmocap), "xpos": f64(3 * m.nbody), "xquat": f64(4 * m.nbody),
                   "xmat": f64(9 * m.nbody), "xipos": f64(3 * m.nbody), "ximat": f64(9 * m.nbody), "geom_xpos": f64(3 * m.ngeom), "geom_xmat": f64(9 * m.ngeom),
                   "site_xpos": f64(3 * m.nsite), "site_xmat": f64(9 * m.nsite), "subtree_com": f64(3 * m.nbody), "qM": f64(m.nv * m.nv), "qfrc_bias": f64(m.nv),
                   "qfrc_passive": f64(m.nv), "qfrc_actuator": f64(m.nv), "qfrc_constraint": f64(m.nv), "actuator_force": f64(m.nu),
@@ -123,7 +123,7 @@ class KinematicsBackend:
     def reset(self):
         d = self.d
         d["qpos"][:] = np.asarray(self.flat.qpos0).ravel()
-        for k in ("qvel", "qacc", "qacc_warmstart", "ctrl", "qfrc_applied", "time"):
+        for k in ("qvel", "qacc", "qacc_warmstart", "ctrl", "qfrc_applied", "xfrc_applied", "time"):
             d[k][:] = 0
 
     def jac(self, kind, idx):

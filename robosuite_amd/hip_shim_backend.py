@@ -29,7 +29,7 @@ class HipShimBackend:
         f64 = lambda n: np.zeros(n, dtype=np.float64)
         self.d = {
             "qpos": np.array(m.qpos0, dtype=np.float64).ravel().copy(), "qvel": f64(m.nv), "qacc": f64(m.nv), "qacc_warmstart": f64(m.nv),
-            "ctrl": f64(m.nu), "qfrc_applied": f64(m.nv), "mocap_pos": f64(3 * int(m.arrays["nmocap"][0]) if "nmocap" in m.arrays else 0),
+            "ctrl": f64(m.nu), "qfrc_applied": f64(m.nv), "xfrc_applied": f64(6 * m.nbody), "mocap_pos": f64(3 * int(m.arrays["nmocap"][0]) if "nmocap" in m.arrays else 0),
             "mocap_quat": f64(4 * int(m.arrays["nmocap"][0]) if "nmocap" in m.arrays else 0), "xpos": f64(3 * m.nbody), "xquat": f64(4 * m.nbody),
             "xmat": f64(9 * m.nbody), "xipos": f64(3 * m.nbody), "ximat": f64(9 * m.nbody), "geom_xpos": f64(3 * m.ngeom), "geom_xmat": f64(9 * m.ngeom),
             "site_xpos": f64(3 * m.nsite), "site_xmat": f64(9 * m.nsite), "subtree_com": f64(3 * m.nbody), "qM": f64(m.nv * m.nv), "qfrc_bias": f64(m.nv),
@@ -56,8 +56,8 @@ class HipShimBackend:
 
     def _push(self):
         b = self.batch
-        for k in ("qpos", "qvel", "ctrl", "qacc_warmstart", "qfrc_applied"):
-            b.set(k, self.d[k][None])
+        for k in ("qpos", "qvel", "ctrl", "qacc_warmstart", "qfrc_applied", "xfrc_applied"):
+            b.set(k, self.d[k].reshape(b.shapes[k]))
         b.set("time", self.d["time"])
 
     def _pull(self, stepped, acc=True):
@@ -103,7 +103,7 @@ class HipShimBackend:
         self.batch.reset()
         d = self.d
         d["qpos"][:] = np.asarray(self.flat.qpos0).ravel()
-        for k in ("qvel", "qacc", "qacc_warmstart", "ctrl", "qfrc_applied", "time"):
+        for k in ("qvel", "qacc", "qacc_warmstart", "ctrl", "qfrc_applied", "xfrc_applied", "time"):
             d[k][:] = 0
 
     def jac(self, kind, idx):

@@ -85,10 +85,10 @@ _MODEL_FIELDS = [
 _MODEL_SIZES = ["nq", "nv", "nu", "na", "nbody", "njnt", "ngeom", "nsite", "ncam", "nlight", "nsensor", "ntendon", "nmesh", "nmocap"]
 _NAME_ADRS = ["name_bodyadr", "name_jntadr", "name_geomadr", "name_siteadr", "name_lightadr", "name_camadr", "name_actuatoradr",
               "name_sensoradr", "name_tendonadr", "name_meshadr"]
-_DATA_FIELDS = ["qpos", "qvel", "qacc", "qacc_warmstart", "ctrl", "qfrc_applied", "mocap_pos", "mocap_quat", "xpos", "xquat", "xmat",
+_DATA_FIELDS = ["qpos", "qvel", "qacc", "qacc_warmstart", "ctrl", "qfrc_applied", "xfrc_applied", "mocap_pos", "mocap_quat", "xpos", "xquat", "xmat",
                 "xipos", "ximat", "geom_xpos", "geom_xmat", "site_xpos", "site_xmat", "subtree_com", "qM", "qfrc_bias",
                 "qfrc_passive", "qfrc_actuator", "qfrc_constraint", "actuator_force", "sensordata"]
-_DATA_SHAPES = {"mocap_pos": 3, "mocap_quat": 4, "xpos": 3, "xquat": 4, "xmat": 9, "xipos": 3, "ximat": 9, "geom_xpos": 3,
+_DATA_SHAPES = {"xfrc_applied": 6, "mocap_pos": 3, "mocap_quat": 4, "xpos": 3, "xquat": 4, "xmat": 9, "xipos": 3, "ximat": 9, "geom_xpos": 3,
                 "geom_xmat": 9, "site_xpos": 3, "site_xmat": 9, "subtree_com": 3}
 
 

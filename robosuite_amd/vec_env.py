@@ -60,6 +60,7 @@ class VecEnv:
         e._bank_stop()      # the upkeep thread draws from the same per-env generators (EpisodeStreams): it must be gone before they are re-keyed / replayed
         if seed is not None and int(seed) != e.seed0:
             e.seed0, e._streams = int(seed), None
+        e.batch.set("qfrc_applied", 0.0); e.batch.set("xfrc_applied", 0.0)   # mj_resetData: episodes start without external forces (before the reset's forward)
         e.reset(block=0)
         b = e.batch
         b.set("ep_step", 0); b.set("ep_index", 0); b.set("done", 0)
@@ -74,6 +75,35 @@ class VecEnv:
         # last record of the finished one is in info["terminal_obs"] (rows of envs that did not finish are stale)
         return self.env.obs(), self.env.reward(), self.env.batch.tensor("done"), {"success": self.env.success(), "terminal_obs": self.env.batch.tensor("terminal_obs")}
 
+    def enable_applied_forces(self, on: bool = True):
+        """Honour `qfrc_applied` and `xfrc_applied` in `step` (off by default: the control step then reads neither).  An env that reports `done`
+        has both rows zeroed for its next episode, in the same step, so a force written after seeing `done` acts on the new episode."""
+        self.env.batch.set_applied_forces(on)
+
+    @property
+    def qfrc_applied(self):
+        """mjData.qfrc_applied of every env, [n_envs, nv]: a device tensor aliasing the batch; an in-place write on the current stream lands before the next `step`."""
+        return self.env.batch.tensor("qfrc_applied")
+
+    @property
+    def xfrc_applied(self):
+        """mjData.xfrc_applied of every env, [n_envs, nbody, 6] (force, torque; world frame, at the body COM): a device tensor aliasing the batch."""
+        return self.env.batch.tensor("xfrc_applied")
+
+    def set_body_wrench(self, body_name: str, wrench, envs=None):
+        """xfrc_applied[envs, body] = wrench (6 values: force then torque, world frame, at the body COM; or one row of 6 per selected env).
+        Takes effect in `step` once `enable_applied_forces()` was called."""
+        import torch
+
+        bid = body_wrench_id(self.env.model, body_name)
+        x = self.xfrc_applied
+        w = torch.as_tensor(wrench, dtype=torch.float32, device=x.device)
+        idx = slice(None) if envs is None else torch.as_tensor(envs, dtype=torch.long, device=x.device)
+        n = self.n_envs if envs is None else int(idx.numel())
+        if tuple(w.shape) not in ((6,), (n, 6)):
+            raise ValueError(f"set_body_wrench: wrench must have shape (6,) or ({n}, 6), got {tuple(w.shape)}")
+        x[idx, bid] = w
+
     def key(self, obs, name: str):
         return obs[:, self.obs_slices[name]]
 
@@ -83,6 +113,14 @@ class VecEnv:
 
         keys = self._object_keys + self._proprio_keys if keys is None else keys
         return torch.cat([obs[:, self.obs_slices[k]] for k in keys], dim=1)
+
+
+def body_wrench_id(model, body_name: str) -> int:
+    """Index of `body_name` for xfrc_applied: raises on an unknown name (where mj_name2id would give -1)."""
+    bid = model.name2id("body", body_name)
+    if bid < 0:
+        raise KeyError(f"no body named {body_name!r} in the model")
+    return bid
 
 
 class AlternatingVecEnv:
