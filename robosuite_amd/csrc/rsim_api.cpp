@@ -34,21 +34,18 @@ extern "C" int rsim_launch_ctrl_reset_cfg3(const DModel* m, const DBatch* b, con
 extern "C" int rsim_launch_ctrl_reset_cfg4(const DModel* m, const DBatch* b, const unsigned char* mask, hipStream_t stream);
 extern "C" int rsim_limits_cfg3(int* lim);
 extern "C" int rsim_limits_cfg4(int* lim);
-// configuration 5 serves no model of its own: it is the capacity tier above configuration 3 (64 contacts x 256 rows, rsim_step.hip)
-#define RSIM_NCFG_ALL 8
-#define RSIM_TIER_DECL(c) \
-  extern "C" int rsim_limits_cfg##c(int* lim); extern "C" int rsim_cmem_bytes_cfg##c(void); \
-  extern "C" int rsim_launch_prepare_cfg##c(const DModel* m, const DBatch* b, int nblocks, int reset_only, hipStream_t stream); \
-  extern "C" int rsim_launch_step_list_cfg##c(const DModel* m, const DBatch* b, const float* actions, int n_sub, int flags, int grid, hipStream_t stream);
-RSIM_TIER_DECL(5) RSIM_TIER_DECL(6) RSIM_TIER_DECL(7)
-extern "C" int rsim_launch_step_list_cfg3(const DModel* m, const DBatch* b, const float* actions, int n_sub, int flags, int grid, hipStream_t stream);
+// configuration 5 serves no model of its own: it is the capacity tier above configuration 3 (64 contacts x 256 rows, rsim_step.hip), a kernel that walks a list of envs
+#define RSIM_NCFG_ALL 6
+extern "C" int rsim_limits_cfg5(int* lim);
+extern "C" int rsim_cmem_bytes_cfg5(void);
+extern "C" int rsim_launch_prepare_cfg5(const DModel* m, const DBatch* b, int nblocks, int reset_only, hipStream_t stream);
+extern "C" int rsim_launch_step_list_cfg5(const DModel* m, const DBatch* b, const float* actions, int n_sub, int flags, int grid, hipStream_t stream);
 extern "C" int rsim_launch_tier_list(const int* tier, int* list, int* count, int* zero_next, int env0, int n, hipStream_t stream);
-extern "C" int rsim_limits_w_cfg0(int* lim);   // limits of the wide body compiled into configuration 0's / 1's control-step kernel (fused tier); 0: this build has none
+extern "C" int rsim_limits_w_cfg0(int* lim);   // limits of the wide body compiled into configuration 0's / 1's / 2's control-step kernel (fused tier)
 extern "C" int rsim_limits_w_cfg1(int* lim);
 extern "C" int rsim_limits_w_cfg2(int* lim);
 typedef int (*limits_w_fn)(int*);
 static const limits_w_fn k_limits_w[3] = {rsim_limits_w_cfg0, rsim_limits_w_cfg1, rsim_limits_w_cfg2};
-typedef int (*step_list_fn)(const DModel*, const DBatch*, const float*, int, int, int, hipStream_t);
 typedef int (*step_fn)(const DModel*, const DBatch*, const float*, int, int, hipStream_t);
 typedef int (*creset_fn)(const DModel*, const DBatch*, const unsigned char*, hipStream_t);
 typedef int (*limits_fn)(int*);
@@ -75,18 +72,7 @@ typedef int (*prepare_fn)(const DModel*, const DBatch*, int, int, hipStream_t);
 typedef int (*cmem_fn)(void);
 static const prepare_fn k_prepare_launch[RSIM_NCFG] = {rsim_launch_prepare_cfg0, rsim_launch_prepare_cfg1, rsim_launch_prepare_cfg2, rsim_launch_prepare_cfg3, rsim_launch_prepare_cfg4};
 static const cmem_fn k_cmem_bytes[RSIM_NCFG] = {rsim_cmem_bytes_cfg0, rsim_cmem_bytes_cfg1, rsim_cmem_bytes_cfg2, rsim_cmem_bytes_cfg3, rsim_cmem_bytes_cfg4};
-static const limits_fn k_limits[RSIM_NCFG_ALL] = {rsim_limits_cfg0, rsim_limits_cfg1, rsim_limits_cfg2, rsim_limits_cfg3, rsim_limits_cfg4, rsim_limits_cfg5, rsim_limits_cfg6, rsim_limits_cfg7};
-// the configurations that can serve as the upper capacity tier of a batch, walked in this order: the same lane roles and dense algebra with more
-// contacts / rows first (6 above 0, 7 above 1 -- an env on its tier then runs about as fast as on its native configuration, which matters because the
-// envs that need the tier are the slowest of a launch), then the wide ones
-static const int k_tier_cfgs[4] = {6, 7, 3, 5};
-static step_list_fn step_list_launch(int c) {
-  return c == 3 ? rsim_launch_step_list_cfg3 : (c == 5 ? rsim_launch_step_list_cfg5 : (c == 6 ? rsim_launch_step_list_cfg6 : (c == 7 ? rsim_launch_step_list_cfg7 : nullptr)));
-}
-static prepare_fn prepare_launch_any(int c);
-static int cmem_bytes_any(int c);
-static prepare_fn prepare_launch_any(int c) { return c == 5 ? rsim_launch_prepare_cfg5 : (c == 6 ? rsim_launch_prepare_cfg6 : (c == 7 ? rsim_launch_prepare_cfg7 : k_prepare_launch[c])); }
-static int cmem_bytes_any(int c) { return c == 5 ? rsim_cmem_bytes_cfg5() : (c == 6 ? rsim_cmem_bytes_cfg6() : (c == 7 ? rsim_cmem_bytes_cfg7() : k_cmem_bytes[c]())); }
+static const limits_fn k_limits[RSIM_NCFG_ALL] = {rsim_limits_cfg0, rsim_limits_cfg1, rsim_limits_cfg2, rsim_limits_cfg3, rsim_limits_cfg4, rsim_limits_cfg5};
 extern "C" int rsim_launch_order(const unsigned* cost, int* order, int B, hipStream_t stream);
 extern "C" int rsim_launch_bank_scatter(float* bank, int* tag, const int* env, const int* episode, const float* rows, int n, int E, int W, hipStream_t stream);
 extern "C" int rsim_launch_randomize(const DModel* m, const DBatch* b, const DDr* d, unsigned long long seed, unsigned long long step, hipStream_t stream);
@@ -140,6 +126,8 @@ struct rsim_model {
   size_t count(const char* n) const { auto it = f.find(n); return it == f.end() ? 0 : it->second.count; }
 };
 
+enum { TIER_NONE, TIER_FUSED, TIER_LIST };   // rsim_batch.tier
+
 struct rsim_batch {
   rsim_model* m;
   int B, device, per_env;
@@ -173,37 +161,34 @@ struct rsim_batch {
   DCtrl cm_ctrl;      // controller the blocks were built for
   // Capacity tiers of the fused control step.  MuJoCo never drops a contact (nconmax = 5000, models/assets/base.xml:5); a kernel configuration has a
   // fixed contact / row capacity that decides its LDS footprint and with it the occupancy of the whole batch.  Instead of sizing every env for the
-  // worst substep of the worst env, an env whose substep needs more than the native capacity is stepped -- for as long as it does -- by a WIDER
-  // configuration (cfg_w: the same source compiled with more contacts / rows) from the same DModel / DBatch: envs near the native capacity move up
-  // between steps (tier_next), an env that runs out of capacity in mid-step commits nothing and is redone by the wide configuration inside the same
-  // rsim_control_step (redo list).  -1: no tier above this batch's configuration.
-  int cfg_w;
-  int share_cm;       // the tier's kernel reads the NATIVE constant blocks: its configuration differs from the batch's in contact / row capacity only, and the block layout
-                      // (Cmem) depends on neither -- no wide blocks to build before a wide pass (round 6: PickPlace's 256-row tier rebuilt its listed envs' blocks
-                      // three times per control step under per-step DR, 3 ms a launch, one of them on the critical path behind the native pass)
-  int fused;          // the tier above the batch's configuration is compiled into its control-step kernel (limits bit 5): an env that needs it is stepped -- or carried on
-                      // from the substep in which it outgrew the native capacity -- by the wide body inside its own workgroup; no list, no wide launch, no redo
-  int lim_w[10];
-  void* d_cm_w;       // constant blocks of the wide configuration: one shared, one per env (built on demand for the envs a wide pass steps)
-  size_t cm_bytes_w;
+  // worst substep of the worst env, an env whose substep needs more than the native capacity is stepped -- for as long as it does -- with more contacts /
+  // rows (lim_w).  rsim_batch_create decides the kind once:
+  //   TIER_FUSED (configurations 0-2, limits bit 5): the tier is a second body of the batch's control-step kernel; an env that needs it is stepped -- or carried
+  //     on from the substep in which it outgrew the native capacity -- by the wide body inside its own workgroup: no list, no wide launch, no redo
+  //   TIER_LIST (configuration 3): configuration 5, the same source compiled with more contacts / rows, steps the listed envs from the same DModel / DBatch:
+  //     envs near the native capacity move up between steps (tier_next), an env that runs out of capacity in mid-step commits nothing and is redone by
+  //     configuration 5 inside the same rsim_control_step (redo list)
+  //   TIER_NONE: every other batch (configuration 4, controller state beyond LDS, RSIM_NO_TIERS): drops are counted in RSIM_OVERFLOW
+  int tier;
+  int lim_w[10];      // limits of the tier's wide body / configuration
   int* d_tier[2];     // [B] each: tier of every env for the current / the next control step (swapped after every step)
   int tier_flip;
+  // TIER_LIST only
+  int share_cm;       // configuration 5 reads the NATIVE constant blocks: it differs from configuration 3 in contact / row capacity only, and the block layout
+                      // (Cmem) depends on neither -- no wide blocks to build before a wide pass (round 6: PickPlace's 256-row tier rebuilt its listed envs' blocks
+                      // three times per control step under per-step DR, 3 ms a launch, one of them on the critical path behind the native pass)
+  void* d_cm_w;       // without share_cm (RSIM_NO_SHARE_CM): configuration 5's own constant blocks, one shared, one per env (built on demand for the envs a wide pass steps)
+  size_t cm_bytes_w;
   int* d_wlist[2];    // [B] each: envs of the wide pass (tier 1), redo list
   int* d_wcount;      // [2][2 + 2 * RSIM_MAX_GROUPS]: list lengths, double-buffered by the parity of the control step (whole batch: 0, 1; env block g: 2 + 2 g, 3 + 2 g);
                       // the tier-list kernel of a step zeroes the lengths of the next one
-  hipStream_t wstream;
+  hipStream_t wstream;   // the wide pass beside the native one
   hipEvent_t wfork, wjoin;
-  int tier_mode;      // 0 (default): the wide pass beside the native one, on its own stream; 1 (RSIM_TIER_MODE=1, measurements): before it, on the batch's stream
   int have_cost;      // d_cost holds the costs of a previous control step
-  // one-launch-per-step batches: the dispatch order of step t + 1 is sorted from the costs of step t - 1 on a side stream WHILE step t runs (envs that are
-  // slow stay slow for hundreds of steps, so costs one step old order as well), which takes the sort and its two kernel boundaries off the critical
-  // path of a control step.  Double-buffered: step t reads order2[t & 1], writes cost2[t & 1]; the sort beside it reads cost2[(t - 1) & 1], writes order2[(t + 1) & 1].
+  // one-launch-per-step batches: the dispatch order of step t is sorted on the batch's stream from the costs of step t - 1 (launch()).
+  // Double-buffered: step t reads order2[t & 1] and writes cost2[t & 1]; the sort before it reads cost2[(t - 1) & 1].
   int* d_order2[2];
   unsigned* d_cost2[2];
-  hipStream_t ostream;
-  int order_fresh;    // 1: the dispatch order of step t is sorted on the batch's stream from the costs of step t - 1 (RSIM_ORDER_FRESH, default); 0: beside step t - 1 from the costs of step t - 2
-  hipEvent_t step_done[2], ord_done[2];
-  int ord_valid[2];   // order2[k] holds a dispatch order (its event has been recorded)
   long nstep;         // one-launch control steps issued since the schedule was (re)started
   int schedule;       // 1 = reorder before every control step (default), 0 = identity order
   int applied;        // rsim_set_applied_forces: control steps add qfrc_applied + J^T xfrc_applied (RF_APPLIED)
@@ -765,17 +750,6 @@ static int pick_config(const rsim_model* m, int* lim_out) {
   }
   return -1;
 }
-// the configuration that steps the envs of a batch of configuration `cfg` which outgrow its contact / row capacity: the first tier configuration
-// that holds the model and more contacts or rows; -1 if there is none (or RSIM_NO_TIERS is set: drops are then counted in RSIM_OVERFLOW, as before round 4)
-static int pick_wide(const rsim_model* m, int cfg, const int* lim, int* lim_out) {
-  if (getenv("RSIM_NO_TIERS")) return -1;
-  for (int c : k_tier_cfgs) {
-    int lw[10];
-    k_limits[c](lw);
-    if (c != cfg && config_holds(m, lw) && lw[5] >= lim[5] && lw[6] >= lim[6] && (lw[5] > lim[5] || lw[6] > lim[6])) { memcpy(lim_out, lw, sizeof(lw)); return c; }
-  }
-  return -1;
-}
 extern "C" int rsim_model_config(const rsim_model* m, int* limits) { return pick_config(m, limits); }
 
 // mj_name2id / mj_id2name (binding_utils.py:296-360: body_name2id, joint_name2id, geom_name2id, site_name2id, actuator_name2id, ... and their inverses)
@@ -836,10 +810,9 @@ extern "C" int rsim_batch_create(rsim_model* m, int B, int device, int per_env, 
   b->d_order = nullptr; b->d_cost = nullptr; b->schedule = 1; b->have_cost = 0;
   if (dalloc(&b->d_order, (size_t)B)) return 1;
   if (dalloc(&b->d_cost, (size_t)B)) return 1;
-  b->ostream = nullptr; b->nstep = 0;
-  { const char* e = getenv("RSIM_ORDER_FRESH"); b->order_fresh = e ? atoi(e) : 1; }
+  b->nstep = 0;
   for (int k = 0; k < 2; k++) {
-    b->d_order2[k] = nullptr; b->d_cost2[k] = nullptr; b->step_done[k] = nullptr; b->ord_done[k] = nullptr; b->ord_valid[k] = 0;
+    b->d_order2[k] = nullptr; b->d_cost2[k] = nullptr;
     if (dalloc(&b->d_order2[k], (size_t)B) || dalloc(&b->d_cost2[k], (size_t)B)) return 1;
   }
   if (dalloc(&b->db.needs_reset, (size_t)B)) return 1;
@@ -903,12 +876,14 @@ extern "C" int rsim_batch_create(rsim_model* m, int B, int device, int per_env, 
   dm.ctrl = m->ctrl;
   b->cs = m->ctrl.enabled ? m->ctrl.cs_size : RSIM_CS_SIZE;
   dm.ctrl.cs_size = b->cs;
-  // capacity tiers: only for controllers whose state lives in LDS for the whole launch (a step that is handed over must not have written anything)
-  b->cfg_w = b->cs <= RSIM_CS_LDS ? pick_wide(m, b->cfg, b->lim, b->lim_w) : -1;
-  b->fused = 0; b->share_cm = 0;
-  if (b->cfg >= 0 && b->cfg <= 2 && (b->lim[9] & 32) && b->cs <= RSIM_CS_LDS && !getenv("RSIM_NO_TIERS")) {
+  // capacity tiers: only for controllers whose state lives in LDS for the whole launch (a step that is handed over must not have written anything);
+  // RSIM_NO_TIERS: none, drops are then counted in RSIM_OVERFLOW (as before round 4)
+  b->tier = TIER_NONE;
+  if (b->cs <= RSIM_CS_LDS && !getenv("RSIM_NO_TIERS") && b->cfg <= 3) {
     int lw[10];
-    if (k_limits_w[b->cfg](lw) && config_holds(m, lw)) { memcpy(b->lim_w, lw, sizeof(lw)); b->fused = 1; if (b->cfg_w < 0) b->cfg_w = b->cfg; }   // (cfg_w only marks "tiered" from here on: a fused batch launches no tier kernel)
+    if (b->cfg <= 2) k_limits_w[b->cfg](lw);   // the wide body of the configuration's own kernel (limits bit 5)
+    else k_limits[5](lw);
+    if (config_holds(m, lw)) { b->tier = b->cfg <= 2 ? TIER_FUSED : TIER_LIST; memcpy(b->lim_w, lw, sizeof(lw)); }
   }
   {
     // builds that keep the constraint Jacobian in global memory (RSIM_JGLOBAL: limits bit 2) get their per-env buffer, [B][NEFC * (NV + 1)] floats
@@ -919,27 +894,29 @@ extern "C" int rsim_batch_create(rsim_model* m, int B, int device, int per_env, 
       return (size_t)lim[6] * (size_t)(lim[2] + 1) + ((lim[9] & 8) ? (size_t)lim[2] * (size_t)(lim[2] + 1) : 0) + ((lim[9] & 16) ? (size_t)lim[5] * 22 : 0);
     };
     size_t jgf = jg_need(b->lim);
-    if (b->cfg_w >= 0) jgf = std::max(jgf, jg_need(b->lim_w));
+    if (b->tier != TIER_NONE) jgf = std::max(jgf, jg_need(b->lim_w));
     b->db.jg_stride = (long long)jgf;
     if (jgf && dalloc(&b->db.jg, (size_t)B * jgf)) return 1;
   }
-  b->d_cm_w = nullptr; b->d_tier[0] = b->d_tier[1] = nullptr; b->d_wlist[0] = b->d_wlist[1] = nullptr; b->d_wcount = nullptr; b->wstream = nullptr; b->tier_flip = 0;
-  if (b->cfg_w >= 0) {
-    b->cm_bytes_w = (size_t)cmem_bytes_any(b->cfg_w);
+  b->d_tier[0] = b->d_tier[1] = nullptr; b->tier_flip = 0;
+  b->share_cm = 0; b->d_cm_w = nullptr; b->cm_bytes_w = 0; b->d_wlist[0] = b->d_wlist[1] = nullptr; b->d_wcount = nullptr; b->wstream = nullptr; b->wfork = b->wjoin = nullptr;
+  if (b->tier != TIER_NONE) {
+    for (int k = 0; k < 2; k++) if (dalloc(&b->d_tier[k], (size_t)B)) return 1;
+    if (dalloc(&b->db.tstat, (size_t)2)) return 1;
+  }
+  if (b->tier == TIER_LIST) {
+    b->cm_bytes_w = (size_t)rsim_cmem_bytes_cfg5();
     b->share_cm = b->cm_bytes_w == b->cm_bytes && b->lim_w[0] == b->lim[0] && b->lim_w[1] == b->lim[1] && b->lim_w[2] == b->lim[2] && b->lim_w[3] == b->lim[3] &&
                   b->lim_w[4] == b->lim[4] && b->lim_w[7] == b->lim[7] && !getenv("RSIM_NO_SHARE_CM");
-    if (dalloc((char**)&b->d_cm_w, b->cm_bytes_w * (1 + (b->per_env ? (size_t)B : 0)))) return 1;
-    for (int k = 0; k < 2; k++) if (dalloc(&b->d_tier[k], (size_t)B) || dalloc(&b->d_wlist[k], (size_t)B)) return 1;
+    if (!b->share_cm && dalloc((char**)&b->d_cm_w, b->cm_bytes_w * (1 + (b->per_env ? (size_t)B : 0)))) return 1;
+    for (int k = 0; k < 2; k++) if (dalloc(&b->d_wlist[k], (size_t)B)) return 1;
     if (dalloc(&b->d_wcount, (size_t)2 * (2 + 2 * RSIM_MAX_GROUPS))) return 1;
-    if (dalloc(&b->db.tstat, (size_t)2)) return 1;
-    HIPCHK(hipMemset(b->db.tstat, 0, 2 * sizeof(unsigned long long)));
     {
       // the wide pass runs beside the native one on a stream of the highest priority (its few workgroups are the slowest envs of the step)
       int lo = 0, hi = 0;
       HIPCHK(hipDeviceGetStreamPriorityRange(&lo, &hi));
       HIPCHK(hipStreamCreateWithPriority(&b->wstream, hipStreamNonBlocking, hi));
     }
-    b->tier_mode = getenv("RSIM_TIER_MODE") ? atoi(getenv("RSIM_TIER_MODE")) : 0;
     HIPCHK(hipEventCreateWithFlags(&b->wfork, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&b->wjoin, hipEventDisableTiming));
   }
@@ -995,10 +972,15 @@ extern "C" void rsim_batch_free(rsim_batch* b) {
   if (b->mev) hipEventDestroy(b->mev);
   for (int i = 0; i < RSIM_FIELD_COUNT; i++) if (b->fptr[i]) hipFree(b->fptr[i]);
   hipFree(b->d_cm);
-  if (b->cfg_w >= 0) {
+  if (b->tier != TIER_NONE) {
+    hipFree(b->db.tstat);
+    for (int k = 0; k < 2; k++) hipFree(b->d_tier[k]);
+  }
+  if (b->tier == TIER_LIST) {
     hipStreamSynchronize(b->wstream); hipStreamDestroy(b->wstream); hipEventDestroy(b->wfork); hipEventDestroy(b->wjoin);
-    hipFree(b->d_cm_w); hipFree(b->d_wcount); hipFree(b->db.tstat);
-    for (int k = 0; k < 2; k++) { hipFree(b->d_tier[k]); hipFree(b->d_wlist[k]); }
+    if (b->d_cm_w) hipFree(b->d_cm_w);
+    hipFree(b->d_wcount);
+    for (int k = 0; k < 2; k++) hipFree(b->d_wlist[k]);
   }
   if (b->db.mprc) hipFree(b->db.mprc);
   if (b->db.jg) hipFree(b->db.jg);
@@ -1006,11 +988,7 @@ extern "C" void rsim_batch_free(rsim_batch* b) {
   hipFree(b->d_it); hipFree(b->d_lt); hipFree(b->d_ft); hipFree(b->d_ft0); if (b->d_obsprog) hipFree(b->d_obsprog);
   if (b->d_bank) hipFree(b->d_bank); if (b->d_bank_tag) hipFree(b->d_bank_tag); if (b->d_patch) hipFree(b->d_patch); hipFree(b->db.needs_reset); if (b->d_ft_base) hipFree(b->d_ft_base); hipFree(b->d_mesh); hipFree(b->d_mask);
   if (b->d_order) hipFree(b->d_order); if (b->d_cost) hipFree(b->d_cost);
-  if (b->ostream) { hipStreamSynchronize(b->ostream); hipStreamDestroy(b->ostream); }
-  for (int k = 0; k < 2; k++) {
-    if (b->d_order2[k]) hipFree(b->d_order2[k]); if (b->d_cost2[k]) hipFree(b->d_cost2[k]);
-    if (b->step_done[k]) hipEventDestroy(b->step_done[k]); if (b->ord_done[k]) hipEventDestroy(b->ord_done[k]);
-  }
+  for (int k = 0; k < 2; k++) { if (b->d_order2[k]) hipFree(b->d_order2[k]); if (b->d_cost2[k]) hipFree(b->d_cost2[k]); }
   if (b->db.prof) hipFree(b->db.prof);
   if (b->bstream) { hipStreamSynchronize(b->bstream); hipStreamDestroy(b->bstream); }
   if (b->bev) hipEventDestroy(b->bev);
@@ -1108,7 +1086,7 @@ extern "C" int rsim_set_stream_groups(rsim_batch* b, int groups) {
   }
   if (!b->mev) HIPCHK(hipEventCreateWithFlags(&b->mev, hipEventDisableTiming));
   if (groups > b->groups) b->groups = groups;
-  if (b->cfg_w >= 0) HIPCHK(hipMemset(b->d_wcount, 0, (size_t)2 * (2 + 2 * RSIM_MAX_GROUPS) * sizeof(int)));   // another partition of the batch: no list length of the old one survives
+  if (b->tier == TIER_LIST) HIPCHK(hipMemset(b->d_wcount, 0, (size_t)2 * (2 + 2 * RSIM_MAX_GROUPS) * sizeof(int)));   // another partition of the batch: no list length of the old one survives
   b->ngroups = groups;
   b->have_cost = 0;
   return 0;
@@ -1142,19 +1120,16 @@ static int ensure_constants(rsim_batch* b) {
     int e = k_prepare_launch[b->cfg](&b->dm, &b->db, b->B, 0, b->stream);
     if (e) return fail("constant-block kernel launch failed: %s", hipGetErrorString((hipError_t)e));
   }
-  if (b->cfg_w >= 0 && !b->fused && !b->share_cm) {   // the shared block of the wide configuration (its per-env blocks are built on demand, right before a wide pass; a fused wide body reads the native blocks)
+  if (b->tier == TIER_LIST && !b->share_cm) {   // the shared block of configuration 5 (its per-env blocks are built on demand, right before a wide pass)
     DModel dm0 = b->dm; DBatch db0 = b->db;
     dm0.fenv = 0; db0.cm_env = b->d_cm_w; db0.cm_stride = 0;
-    int e = prepare_launch_any(b->cfg_w)(&dm0, &db0, 1, 0, b->stream);
+    int e = rsim_launch_prepare_cfg5(&dm0, &db0, 1, 0, b->stream);
     if (e) return fail("constant-block kernel launch failed: %s", hipGetErrorString((hipError_t)e));
   }
   b->cm_ctrl = b->dm.ctrl;
   b->cm_dirty = 0;
   return 0;
 }
-
-// One wide pass of a tiered control step on `stream`: the constant blocks of the listed envs (only when envs have blocks of their own), then the step.
-// pass 1 = the envs whose tier is 1 (list built by rsim_launch_tier_list), pass 2 = the redo list the native pass appended to.
 
 // RSIM_TRACE_STEPS=N: HIP events at fixed points of the main stream in N consecutive control steps, mean intervals printed to stderr once -- where the time
 // between two control-step kernels goes WITHOUT a profiler attached (rocprofv3 changes the cross-queue behaviour it is supposed to show)
@@ -1179,6 +1154,8 @@ static void tr_mark(rsim_batch* b, int point) {
 }
 
 static inline bool sched1_trace(int flags) { return (flags & RF_EPISODE) && (flags & RF_CTRL); }
+// One wide pass of a TIER_LIST control step on `stream`: the constant blocks of the listed envs (only when envs have blocks of their own), then the step.
+// pass 1 = the envs whose tier is 1 (list built by rsim_launch_tier_list), pass 2 = the redo list the native pass appended to.
 static int wide_pass(rsim_batch* b, const float* actions, int n_sub, int flags, int pass, const int* list, const int* count, hipStream_t stream) {
   DBatch dw = b->db;
   if (!b->share_cm) { dw.cm = b->d_cm_w; dw.cm_env = (char*)b->d_cm_w + b->cm_bytes_w; dw.cm_stride = b->db.cm_stride ? (long long)b->cm_bytes_w : 0; }   // else: the native blocks, as b->db has them
@@ -1186,10 +1163,10 @@ static int wide_pass(rsim_batch* b, const float* actions, int n_sub, int flags, 
   dw.tier_pass = pass; dw.wlist = list; dw.wcount = count; dw.tier_con = b->lim[5]; dw.tier_efc = b->lim[6];
   const int grid = b->B < 512 ? b->B : 512;
   if (dw.cm_stride && !b->share_cm) {
-    int e = prepare_launch_any(b->cfg_w)(&b->dm, &dw, grid, 2, stream);
+    int e = rsim_launch_prepare_cfg5(&b->dm, &dw, grid, 2, stream);
     if (e) return fail("constant-block kernel launch failed: %s", hipGetErrorString((hipError_t)e));
   }
-  int e = step_list_launch(b->cfg_w)(&b->dm, &dw, actions, n_sub, flags, grid, stream);
+  int e = rsim_launch_step_list_cfg5(&b->dm, &dw, actions, n_sub, flags, grid, stream);
   if (e) return fail("wide-tier kernel launch failed: %s", hipGetErrorString((hipError_t)e));
   return 0;
 }
@@ -1200,7 +1177,7 @@ static int launch(rsim_batch* b, const float* actions, int n_sub, int flags) {
   if (sync_controller(b)) return 1;
   if (b->applied) flags |= RF_APPLIED;
   // capacity tiers apply to the fused control step only (the debug entries keep the native capacity and count what they drop in RSIM_OVERFLOW)
-  const bool tiered = b->cfg_w >= 0 && (flags & RF_EPISODE) && (flags & RF_CTRL) && !(flags & RF_DEBUG);
+  const bool tiered = b->tier != TIER_NONE && (flags & RF_EPISODE) && (flags & RF_CTRL) && !(flags & RF_DEBUG);
   b->db.tier_cur = tiered ? b->d_tier[b->tier_flip] : nullptr; b->db.tier_next = tiered ? b->d_tier[b->tier_flip ^ 1] : nullptr;
   // how close to its native capacity an env moves up BEFORE it overflows.  A flagged env is stepped by the wide pass, whose workgroups only find room once the
   // native launch has no workgroup pending (a freed 20 KB slot never fits a 32 - 116 KB workgroup): it starts ~2 ms into the step and, being one of the most
@@ -1214,7 +1191,7 @@ static int launch(rsim_batch* b, const float* actions, int n_sub, int flags) {
   b->db.tier_up_efc = getenv("RSIM_TIER_UP_EFC") ? atoi(getenv("RSIM_TIER_UP_EFC")) : (no_advance ? 0 : 6);
   b->db.tier_pass = tiered ? 0 : -1; b->db.wlist = nullptr; b->db.wcount = nullptr; b->db.wlist2 = nullptr; b->db.wcount2 = nullptr;
   // fused tier: k_step picks the body per env and hands over in place; the thresholds at which the wide body lets an env go back are the native capacity's
-  const bool fused = tiered && b->fused;
+  const bool fused = tiered && b->tier == TIER_FUSED, listed = tiered && b->tier == TIER_LIST;
   if (fused) {
     b->db.tier_con = b->lim[5]; b->db.tier_efc = b->lim[6];
     if (const char* e = getenv("RSIM_FORCE_HANDOVER")) b->db.tier_pass = 100 + atoi(e);   // test hook: every native-tier env hands over to the wide body at this substep (tests/test_hip_edge_cases.py)
@@ -1240,7 +1217,7 @@ static int launch(rsim_batch* b, const float* actions, int n_sub, int flags) {
         }
         db.cost = b->d_cost;
       }
-      if (tiered && !fused) {   // this env block's lists; every pass of the block runs on the block's own stream, one after the other
+      if (listed) {   // this env block's lists; every pass of the block runs on the block's own stream, one after the other
         int* cnt = b->d_wcount + b->tier_flip * WCN + 2 + 2 * g;
         int el = rsim_launch_tier_list(b->db.tier_cur, b->d_wlist[0] + e0, cnt, b->d_wcount + (b->tier_flip ^ 1) * WCN + 2 + 2 * g, e0, e1 - e0, b->gstream[g]);
         if (el) return fail("tier-list kernel launch failed: %s", hipGetErrorString((hipError_t)el));
@@ -1248,7 +1225,7 @@ static int launch(rsim_batch* b, const float* actions, int n_sub, int flags) {
       }
       int e = k_step_launch[b->cfg](&b->dm, &db, actions, n_sub, flags, b->gstream[g]);
       if (e) return fail("kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-      if (tiered && !fused) {
+      if (listed) {
         int* cnt = b->d_wcount + b->tier_flip * WCN + 2 + 2 * g;
         if (wide_pass(b, actions, n_sub, flags, 1, b->d_wlist[0] + e0, cnt, b->gstream[g])) return 1;
         if (wide_pass(b, actions, n_sub, flags, 2, b->d_wlist[1] + e0, cnt + 1, b->gstream[g])) return 1;
@@ -1278,67 +1255,44 @@ static int launch(rsim_batch* b, const float* actions, int n_sub, int flags) {
   const bool traced = sched1_trace(flags);
   if (traced) tr_mark(b, 0);
   if (sched1) {
-    if (!b->ostream) {
-      HIPCHK(hipStreamCreateWithFlags(&b->ostream, hipStreamNonBlocking));
-      for (int k = 0; k < 2; k++) { HIPCHK(hipEventCreateWithFlags(&b->step_done[k], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&b->ord_done[k], hipEventDisableTiming)); }
+    // on the batch's stream, from the costs of the step just before this one: 12-16 us on the critical path, no cross-stream dependency.  A side-stream
+    // sort beside step t - 1 would have to use the costs of step t - 2; an env's duration correlates 0.55 with its duration one step earlier and 0.40-0.52
+    // with two steps earlier, and replaying the measured durations through a list scheduler puts the launch 3.4 % (Lift) / 3.7 % (Stack) shorter with the
+    // fresher order (tools/sched_study.py, profiles/r04_x3_sched_study.txt); measured against the side-stream sort: Lift +5.6 %, Stack +3.6 %, TwoArmPegInHole
+    // +5.5 % (profiles/r04_x_order_and_tiers.txt)
+    if (b->nstep >= 1) {
+      int eo = rsim_launch_order(b->d_cost2[prev], b->d_order2[cur], b->B, b->stream);
+      if (eo) return fail("dispatch-order kernel launch failed: %s", hipGetErrorString((hipError_t)eo));
+      b->db.order = b->d_order2[cur];
     }
-    if (b->order_fresh) {
-      // on the batch's stream, from the costs of the step just before this one: 12-16 us on the critical path, no cross-stream dependency.  The side-stream
-      // form below sorts the costs of step t - 2; an env's duration correlates 0.55 with its duration one step earlier and 0.40-0.52 with two steps
-      // earlier, and replaying the measured durations through a list scheduler puts the launch 3.4 % (Lift) / 3.7 % (Stack) shorter with the fresher
-      // order (tools/sched_study.py, profiles/r04_x3_sched_study.txt)
-      if (b->nstep >= 1) {
-        int eo = rsim_launch_order(b->d_cost2[prev], b->d_order2[cur], b->B, b->stream);
-        if (eo) return fail("dispatch-order kernel launch failed: %s", hipGetErrorString((hipError_t)eo));
-        b->db.order = b->d_order2[cur];
-      }
-    } else if (b->ord_valid[cur]) { HIPCHK(hipStreamWaitEvent(b->stream, b->ord_done[cur], 0)); b->db.order = b->d_order2[cur]; }
     b->db.cost = b->d_cost2[cur];
   }
   if (traced) tr_mark(b, 1);
-  if (tiered && !fused) {
-    // beside the native pass, on a stream of its own: the envs whose tier is 1 (they were close to the native capacity, or beyond it, last step)
+  if (listed) {
+    // beside the native pass, on a stream of its own: the envs whose tier is 1 (they were close to the native capacity, or beyond it, last step).  Ahead of the
+    // native pass on the batch's stream instead: 8.1 against 6.31 ms per control step (Stack, when its tier was a kernel of its own: profiles/r05_s14_ab_many_stack.txt)
     int* cnt = b->d_wcount + b->tier_flip * WCN;
-    if (b->tier_mode == 1) {   // everything on the batch's stream: list, wide pass, then the native pass
-      int el = rsim_launch_tier_list(b->db.tier_cur, b->d_wlist[0], cnt, b->d_wcount + (b->tier_flip ^ 1) * WCN, 0, b->B, b->stream);
-      if (el) return fail("tier-list kernel launch failed: %s", hipGetErrorString((hipError_t)el));
-      if (wide_pass(b, actions, n_sub, flags, 1, b->d_wlist[0], cnt, b->stream)) return 1;
-    } else {
-      HIPCHK(hipEventRecord(b->wfork, b->stream));
-      HIPCHK(hipStreamWaitEvent(b->wstream, b->wfork, 0));
-      int el = rsim_launch_tier_list(b->db.tier_cur, b->d_wlist[0], cnt, b->d_wcount + (b->tier_flip ^ 1) * WCN, 0, b->B, b->wstream);
-      if (el) return fail("tier-list kernel launch failed: %s", hipGetErrorString((hipError_t)el));
-      if (wide_pass(b, actions, n_sub, flags, 1, b->d_wlist[0], cnt, b->wstream)) return 1;
-      HIPCHK(hipEventRecord(b->wjoin, b->wstream));
-    }
+    HIPCHK(hipEventRecord(b->wfork, b->stream));
+    HIPCHK(hipStreamWaitEvent(b->wstream, b->wfork, 0));
+    int el = rsim_launch_tier_list(b->db.tier_cur, b->d_wlist[0], cnt, b->d_wcount + (b->tier_flip ^ 1) * WCN, 0, b->B, b->wstream);
+    if (el) return fail("tier-list kernel launch failed: %s", hipGetErrorString((hipError_t)el));
+    if (wide_pass(b, actions, n_sub, flags, 1, b->d_wlist[0], cnt, b->wstream)) return 1;
+    HIPCHK(hipEventRecord(b->wjoin, b->wstream));
     b->db.wlist2 = b->d_wlist[1]; b->db.wcount2 = cnt + 1;
   }
   if (traced) tr_mark(b, 2);
   int e = k_step_launch[b->cfg](&b->dm, &b->db, actions, n_sub, flags, b->stream);
   if (e) return fail("kernel launch failed: %s", hipGetErrorString((hipError_t)e));
   if (traced) tr_mark(b, 3);
-  if (tiered && !fused) {
+  if (listed) {
     // after both: the envs the native pass had to hand over in mid-step (rare: most move up between steps), redone from their unchanged state
-    if (b->tier_mode != 1) HIPCHK(hipStreamWaitEvent(b->stream, b->wjoin, 0));
+    HIPCHK(hipStreamWaitEvent(b->stream, b->wjoin, 0));
     if (traced) tr_mark(b, 4);
     if (wide_pass(b, actions, n_sub, flags, 2, b->d_wlist[1], b->d_wcount + b->tier_flip * WCN + 1, b->stream)) return 1;
-    b->tier_flip ^= 1;
-  } else {
-    if (fused) b->tier_flip ^= 1;
-    if (traced) tr_mark(b, 4);
-  }
+  } else if (traced) tr_mark(b, 4);
+  if (tiered) b->tier_flip ^= 1;
   if (traced) tr_mark(b, 5);
-  if (sched1) {
-    if (!b->order_fresh) HIPCHK(hipEventRecord(b->step_done[cur], b->stream));
-    if (!b->order_fresh && b->nstep >= 1) {   // beside the step just launched: sort the costs of the PREVIOUS step into the order of the NEXT one
-      HIPCHK(hipStreamWaitEvent(b->ostream, b->step_done[prev], 0));
-      int eo = rsim_launch_order(b->d_cost2[prev], b->d_order2[prev], b->B, b->ostream);   // order2[(t + 1) & 1] == order2[prev]
-      if (eo) return fail("dispatch-order kernel launch failed: %s", hipGetErrorString((hipError_t)eo));
-      HIPCHK(hipEventRecord(b->ord_done[prev], b->ostream));
-      b->ord_valid[prev] = 1;
-    }
-    b->nstep++;
-  }
+  if (sched1) b->nstep++;
   if ((flags & RF_EPISODE) && b->db.bank && b->db.horizon > 0) {
     if (b->db.bank_P > 0 && b->db.cm_stride) {
       // envs whose episode just ended were re-initialised from the reset bank, float-table patches included: rebuild their constant blocks
@@ -1633,8 +1587,7 @@ extern "C" int rsim_profile(rsim_batch* b, int enable, unsigned long long* out, 
 extern "C" int rsim_set_applied_forces(rsim_batch* b, int enable) { b->applied = enable ? 1 : 0; return 0; }
 extern "C" int rsim_set_schedule(rsim_batch* b, int longest_first) {
   b->schedule = longest_first ? 1 : 0; b->have_cost = 0;
-  if (b->ostream) { HIPCHK(hipSetDevice(b->device)); HIPCHK(hipStreamSynchronize(b->ostream)); }
-  b->nstep = 0; b->ord_valid[0] = b->ord_valid[1] = 0;
+  b->nstep = 0;
   return 0;
 }
 extern "C" int rsim_pairlog(rsim_batch* b, unsigned long long* out) { if (join_groups(b)) return 1;
@@ -1645,41 +1598,40 @@ extern "C" int rsim_pairlog(rsim_batch* b, unsigned long long* out) { if (join_g
   return 0;
 }
 extern "C" int rsim_profile_env(rsim_batch* b, int env) { b->db.prof_env = env; return 0; }
-// Capacity tier of every env for the NEXT control step (0: the native configuration steps it, 1: the wider one), host int32 [B]; all zeros for a batch without a
-// tier above its configuration.  Diagnostics (tools/window_trace.py, bench.py's per-step record): an env whose entry went 0 -> 1 over a control step was handed
-// over in mid-step (redone), an env at 1 is on next step's wide list.
 // Everything outside a kernel's code object that decides what a control step dispatches and how its solver behaves: the compiled-in defaults and the RSIM_*
 // environment overrides in force.  PMC evidence under profiles/ carries the sha of this string next to the code-object sha (round-5 advisor finding: a host-only
 // change -- polish passes, tier thresholds -- left the code sha equal and the evidence was reported as current).
 extern "C" const char* rsim_tuning_defaults(void) {
-  static std::string s;
+  static thread_local std::string s;   // the returned pointer stays valid until the calling thread calls again
   char buf[1024];
   snprintf(buf, sizeof(buf), "newton_ns=%g;newton_na=%g;newton_ls=%g;newton_ng=%g;newton_wide=1;newton_exact=1;newton_refine(cfg>=3)=16;polish_tol=1;polish_gate=0;"
-           "bp_reach=%g;near_thresh=%g;near_gain=%g;mpr_cone=%g;mpr_warmstart=1;mpr_portal=1;tier_up(cfg0,cfg1)=0/0;tier_up(other)=2/6;tier_mode=0;order_fresh=1;fused_tier_cfg0=%d;fused_tier_cfg1=%d;fused_tier_cfg2=%d",
-           (double)RSIM_NEWTON_NS, (double)RSIM_NEWTON_NA, (double)RSIM_NEWTON_LS, (double)RSIM_NEWTON_NG, (double)RSIM_BP_REACH, (double)RSIM_NEAR_THRESH, (double)RSIM_NEAR_GAIN, (double)RSIM_MPR_CONE,
-           []{ int lw[10]; return rsim_limits_w_cfg0(lw); }(), []{ int lw[10]; return rsim_limits_w_cfg1(lw); }(), []{ int lw[10]; return rsim_limits_w_cfg2(lw); }());
+           "bp_reach=%g;near_thresh=%g;near_gain=%g;mpr_cone=%g;mpr_warmstart=1;mpr_portal=1;tier_up(cfg0,cfg1)=0/0;tier_up(other)=2/6",
+           (double)RSIM_NEWTON_NS, (double)RSIM_NEWTON_NA, (double)RSIM_NEWTON_LS, (double)RSIM_NEWTON_NG, (double)RSIM_BP_REACH, (double)RSIM_NEAR_THRESH, (double)RSIM_NEAR_GAIN, (double)RSIM_MPR_CONE);
   s = buf;
   static const char* const envs[] = {"RSIM_NEWTON_NS", "RSIM_NEWTON_NA", "RSIM_NEWTON_LS", "RSIM_NEWTON_NG", "RSIM_NEWTON_WIDE", "RSIM_NEWTON_EXACT", "RSIM_NEWTON_REFINE",
                                      "RSIM_POLISH_TOL", "RSIM_POLISH_GATE", "RSIM_BP_REACH", "RSIM_NEAR_THRESH", "RSIM_NEAR_GAIN", "RSIM_MPR_CONE", "RSIM_NO_MPR_WARMSTART", "RSIM_NO_MPR_PORTAL_WARMSTART",
-                                     "RSIM_TIER_UP_CON", "RSIM_TIER_UP_EFC", "RSIM_TIER_MODE", "RSIM_NO_TIERS", "RSIM_ORDER_FRESH", "RSIM_EULER_FULL", "RSIM_FORCE_HANDOVER"};
+                                     "RSIM_TIER_UP_CON", "RSIM_TIER_UP_EFC", "RSIM_NO_TIERS", "RSIM_NO_SHARE_CM", "RSIM_EULER_FULL", "RSIM_FORCE_HANDOVER"};
   for (const char* e : envs) if (const char* v = getenv(e)) { s += ";env:"; s += e; s += "="; s += v; }
   return s.c_str();
 }
-// {env-steps the wider capacity tier stepped, env-steps of these that were handed over (fused tier) / redone (tier kernels) in mid-step} since the batch was created
+// {env-steps the wider capacity tier stepped, env-steps of these that were handed over (TIER_FUSED) / redone (TIER_LIST) in mid-step} since the batch was created
 extern "C" int rsim_tier_stats(rsim_batch* b, unsigned long long* out2) {
   if (!out2) return fail("rsim_tier_stats: null destination");
   out2[0] = out2[1] = 0;
-  if (b->cfg_w < 0 || !b->db.tstat) return 0;
+  if (b->tier == TIER_NONE) return 0;
   HIPCHK(hipSetDevice(b->device));
   if (join_groups(b)) return 1;
   HIPCHK(hipStreamSynchronize(b->stream));
   HIPCHK(hipMemcpy(out2, b->db.tstat, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
   return 0;
 }
+// Capacity tier of every env for the NEXT control step (0: the native configuration steps it, 1: the wider one), host int32 [B]; all zeros for a batch without a
+// tier above its configuration.  Diagnostics (tools/window_trace.py, bench.py's per-step record): an env whose entry went 0 -> 1 over a control step was handed
+// over in mid-step (redone), an env at 1 is on next step's wide list.
 extern "C" int rsim_tier_snapshot(rsim_batch* b, int* host_tier) {
   if (!host_tier) return fail("rsim_tier_snapshot: null destination");
   HIPCHK(hipSetDevice(b->device));
-  if (b->cfg_w < 0 || !b->d_tier[0]) { memset(host_tier, 0, (size_t)b->B * sizeof(int)); return 0; }
+  if (b->tier == TIER_NONE) { memset(host_tier, 0, (size_t)b->B * sizeof(int)); return 0; }
   if (join_groups(b)) return 1;
   HIPCHK(hipStreamSynchronize(b->stream));
   HIPCHK(hipMemcpy(host_tier, b->d_tier[b->tier_flip], (size_t)b->B * sizeof(int), hipMemcpyDeviceToHost));

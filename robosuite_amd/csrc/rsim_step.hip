@@ -15,7 +15,7 @@
 #include "../../include/rsim.h"
 #include "rsim_internal.h"
 
-// Eight builds of this file (0-4 serve models, 5-7 are the capacity tiers above 3, 0 and 1): RSIM_CFG 0 = 32 bodies x 16 dofs (Lift/Panda; tree products as incidence-matrix MFMAs with compile-time bit
+// Six builds of this file (0-4 serve models, 5 is the capacity tier above 3): RSIM_CFG 0 = 32 bodies x 16 dofs (Lift/Panda; tree products as incidence-matrix MFMAs with compile-time bit
 // fields, every dense nv x nv product on one 16x16 MFMA tile, register-resident Cholesky), 1 = 32 x 32 (Stack/Panda: two free cubes),
 // 2 = 64 x 16 (Baxter), 3 = 64 x 48 (PickPlace / IIWA + Robotiq140), 4 = 64 x 64.  The larger builds keep the lane roles, the collision
 // pipeline, the constraint rows and the Newton algorithm; beyond 32 x 16 the tree products use per-lane 64-bit incidence words
@@ -27,25 +27,19 @@
 #if RSIM_CFG == 0
 #define RSIM_DIMS 32, 16, 16, 24, 16, 16, 64, 192
 #define RSIM_SYM(x) x##_cfg0
-#ifdef RSIM_FUSED_TIER
-// The capacity tier above this configuration (32 contacts x 128 rows: the dimensions of configuration 6) compiled INTO this configuration's control-step kernel:
+// The capacity tier above this configuration (32 contacts x 128 rows) compiled INTO this configuration's control-step kernel (RSIM_DIMS_W):
 // an env that outgrows 16 contacts / 64 rows in mid-step carries on with the wide body from the substep it is in, inside the same workgroup (k_step below), instead
 // of being redone by another kernel after the launch.  The wide body keeps its Jacobian and contact block in the per-env global buffer so that both bodies
 // fit the same 20 KB of LDS (eight envs per CU).
 #define RSIM_DIMS_W 32, 16, 16, 24, 16, 32, 128, 192
-#endif
 #elif RSIM_CFG == 1
 #define RSIM_DIMS 32, 16, 32, 24, 16, 32, 64, 192
 #define RSIM_SYM(x) x##_cfg1
-#ifdef RSIM_FUSED_TIER   /* the Stack-class tier (32 contacts x 128 rows: the dimensions of configuration 7) as a second body of this configuration's kernel, as for configuration 0 */
-#define RSIM_DIMS_W 32, 16, 32, 24, 16, 32, 128, 192
-#endif
+#define RSIM_DIMS_W 32, 16, 32, 24, 16, 32, 128, 192   /* the Stack-class tier (32 contacts x 128 rows) as a second body of this configuration's kernel, as for configuration 0 */
 #elif RSIM_CFG == 2  // 64 bodies x 16 dofs (Baxter: 36 bodies, 29 colliding geoms, 17 sites, 299 candidate pairs): tree products as mask loops, dense ones on one tile
 #define RSIM_DIMS 64, 16, 16, 32, 32, 32, 64, 320
 #define RSIM_SYM(x) x##_cfg2
-#ifdef RSIM_FUSED_TIER   /* the tier above this configuration as a second body of its kernel: the same lane roles with 128 rows (before: the 64 x 48 build's kernel served as its tier) */
-#define RSIM_DIMS_W 64, 16, 16, 32, 32, 32, 128, 320
-#endif
+#define RSIM_DIMS_W 64, 16, 16, 32, 32, 32, 128, 320   /* the tier above this configuration as a second body of its kernel: the same lane roles with 128 rows */
 #elif RSIM_CFG == 3  // 64 bodies x 48 dofs x 128 constraint rows (PickPlace / IIWA + Robotiq140: 36 bodies, 37 dofs, 41 colliding geoms, 622 candidate
        // pairs, tendon rows; a closed Robotiq gripper alone holds ~30 rows of self-contact).  Three 16-dof tiles instead of four: the dense matrices
        // (M, H, J) shrink to 75 KB of LDS per environment = TWO environments per CU
@@ -54,12 +48,6 @@
 #elif RSIM_CFG == 4  // 64 bodies x 64 dofs x 128 constraint rows: the widest configuration (one environment per CU)
 #define RSIM_DIMS 64, 32, 64, 64, 32, 32, 128, 640
 #define RSIM_SYM(x) x##_cfg4
-#elif RSIM_CFG == 6  // capacity tier above configuration 0 (Lift class: 32 bodies x 16 dofs): 32 contacts x 128 rows, the same one-tile algebra with two rows per lane
-#define RSIM_DIMS 32, 16, 16, 24, 16, 32, 128, 192
-#define RSIM_SYM(x) x##_cfg6
-#elif RSIM_CFG == 7  // capacity tier above configuration 1 (Stack class: 32 bodies x 32 dofs): 32 contacts x 128 rows
-#define RSIM_DIMS 32, 16, 32, 24, 16, 32, 128, 192
-#define RSIM_SYM(x) x##_cfg7
 #else  // 64 bodies x 48 dofs with 64 contacts x 256 constraint rows (four per lane), one environment per CU: the capacity tier ABOVE configuration 3.  No
        // model is assigned to it; the PickPlace envs whose substep asks for more than 32 contacts / 128 rows (a handful of 8192 at any time: objects
        // wedged between fingers, bin walls and each other) are stepped by it for as long as they do (rsim_api.cpp launch(): capacity tiers)
@@ -128,7 +116,7 @@ typedef unsigned long long u64;
 #else
 #define RSIM_CG_ENABLED 0
 #endif
-#ifdef RSIM_FUSED_TIER
+#ifdef RSIM_DIMS_W   /* configurations 0-2: the capacity tier above the configuration is a second body of its control-step kernel */
 #define RSIM_FUSED_ENABLED 1
 #else
 #define RSIM_FUSED_ENABLED 0
@@ -4719,9 +4707,6 @@ __global__ RSIM_KSTEP_ATTR __launch_bounds__(64, RSIM_MINWAVES) void k_step(DMod
   Handover ho;
   ho.sub0 = 0; ho.time = 0.f; ho.fresh_ctrl = false; ho.handed = false; ho.ndiverged = 0; ho.need_con = 0; ho.need_efc = 0; ho.cstate = 0.f; ho.t_launch = 0u;
   bool wide = false;
-#ifdef RSIM_FUSED_TEST_WIDE_ONLY
-  step_body<RSIM_DIMS_W, false, 2>(m, b, actions, n_sub, flags, slot, &ho); return;
-#endif
   if (b.tier_cur) {
     if (slot >= (b.nenv ? b.nenv : b.B)) return;
     wide = b.tier_cur[uni((b.order ? b.order[slot] : slot) + b.env0)] != 0;
@@ -4729,9 +4714,6 @@ __global__ RSIM_KSTEP_ATTR __launch_bounds__(64, RSIM_MINWAVES) void k_step(DMod
   if (!wide) {
     const int over = uni(step_body<NB, NJ, NV, NG, NS, NCON, NEFC, NPAIR, false, 1>(m, b, actions, n_sub, flags, slot, &ho) ? 1 : 0);
     if (!over) return;
-#ifdef RSIM_FUSED_TEST_NATIVE_ONLY
-    return;
-#endif
     // wave-uniform by construction; said so explicitly (the compiler sees them leave a branch on a vector condition)
     ho.sub0 = uni(ho.sub0); ho.time = __builtin_bit_cast(float, uni(__builtin_bit_cast(int, ho.time))); ho.fresh_ctrl = uni(ho.fresh_ctrl ? 1 : 0) != 0; ho.handed = true;
     ho.ndiverged = uni(ho.ndiverged); ho.need_con = uni(ho.need_con); ho.need_efc = uni(ho.need_efc); ho.t_launch = (unsigned)uni((int)ho.t_launch);
@@ -4935,24 +4917,20 @@ extern "C" int rsim_launch_order(const unsigned* cost, int* order, int B, hipStr
 }
 #endif  // RSIM_CFG == 0
 
-#if RSIM_CFG == 0 || RSIM_CFG == 1 || RSIM_CFG == 2
-// limits of the wide body of a fused-tier build (layout of rsim_limits); returns 0 when this build has none
-extern "C" int RSIM_SYM(rsim_limits_w)(int* lim) {
 #ifdef RSIM_DIMS_W
+// limits of the wide body of this fused-tier build (layout of rsim_limits)
+extern "C" int RSIM_SYM(rsim_limits_w)(int* lim) {
   const int dims[8] = {RSIM_DIMS_W};
   for (int i = 0; i < 8; i++) lim[i] = dims[i];
   lim[8] = SmemW::NROOT_; lim[9] = (SmemW::TENDONS_ ? 1 : 0) | (SmemW::NB_ > 32 ? 2 : 0) | (SmemW::JG_ ? 4 : 0) | (SmemW::MG_ ? 8 : 0) | (SmemW::CG_ ? 16 : 0) | 32;
   static_assert(sizeof(Cmem<RSIM_DIMS_W>) == sizeof(Cmem0), "the wide body reads the native configuration's constant blocks");
   return 1;
-#else
-  (void)lim; return 0;
-#endif
 }
 #endif
 // explicit instantiations + launchers (one set per configuration build) ----------------------------------------------------------
 template __global__ void k_step<RSIM_DIMS>(DModel, DBatch, const float*, int, int);
 template __global__ void k_step_dbg<RSIM_DIMS>(DModel, DBatch, const float*, int, int);
-#if RSIM_CFG == 3 || RSIM_CFG >= 5   // the configurations that serve as the upper capacity tier of narrower ones (rsim_api.cpp pick_wide)
+#if RSIM_CFG == 5   // the list-walking form of the tier above configuration 3 (rsim_api.cpp launch(): TIER_LIST)
 template __global__ void k_step_list<RSIM_DIMS>(DModel, DBatch, const float*, int, int);
 extern "C" int RSIM_SYM(rsim_launch_step_list)(const DModel* m, const DBatch* b, const float* actions, int n_sub, int flags, int grid, hipStream_t stream) {
   hipLaunchKernelGGL((k_step_list<RSIM_DIMS>), dim3(grid), dim3(64), 0, stream, *m, *b, actions, n_sub, flags);

@@ -433,9 +433,9 @@ def _jammed_lift_state():
 
 def test_capacity_tiers_step_an_env_beyond_the_native_capacity_without_dropping_a_contact(monkeypatch):
     """MuJoCo never drops a contact (nconmax = 5000, models/assets/base.xml:5).  rsim_control_step hands an env whose substep needs more than the native
-    16 contacts / 64 rows to the wider configuration (32 / 128): in the step in which it happens nothing of the native pass is committed and the wide
-    configuration redoes the step from the same state (redo list); from the next step on the env is on the wide pass's list until its demand has
-    dropped.  Checked on the round-3 overflow state: RSIM_OVERFLOW stays 0, RSIM_CAP_NEED shows the demand, the states after three control steps
+    16 contacts / 64 rows to the wide body (32 / 128) compiled into the same control-step kernel: in the substep in which it happens the env carries on in
+    the wide body of its own workgroup from the state the earlier substeps left (fused hand-over); from the next step on the wide body steps it from the
+    start until its demand has dropped.  Checked on the round-3 overflow state: RSIM_OVERFLOW stays 0, RSIM_CAP_NEED shows the demand, the states after three control steps
     agree with the fp64 oracle (which holds 64 contacts) as closely as an ordinary contact state does -- and differ from what the truncating build
     (RSIM_NO_TIERS) computes; an env that never leaves the native capacity is bitwise what it is without tiers."""
     from tests.util import load_golden, make_hip, make_oracle

@@ -18,17 +18,18 @@ STEP_BUDGET = {"ILi32ELi16ELi16ELi24ELi16ELi16ELi64ELi192E": (8, 256, 32),    # 
                "ILi64ELi16ELi16ELi32ELi32ELi32ELi64ELi320E": (5, 256, 32),   # round 6: 31 892 B = 25 granules, 247 registers: five envs per CU (before: 32 084 B = 26 granules = four, whatever the registers)
                 "ILi64ELi32ELi48ELi64ELi32ELi32ELi128ELi640E": (4, 512, 0),   # J and M in global memory (RSIM_JGLOBAL round 4: 74.8 -> 49.7 KB = 3; RSIM_MGLOBAL round 5: 40.3 KB = 4, one wavefront per SIMD)
                "ILi64ELi32ELi64ELi64ELi32ELi32ELi128ELi640E": (1, 512, 0),
-               # the capacity tiers (round 4): above 64 x 48, above the Lift configuration, above the Stack configuration.  The 256-row tier (four rows per lane, J in
-               # global memory since round 5: two per CU) spills in the polish's fp64 line search (424 B); it steps the few envs beyond 128 rows
-               # round 6: the row staging holds one slot (64 rows) at a time -- the 256-row tier 65 972 -> 54 516 B (still two per CU, see below), the Stack-class tier's own unit 28 276 -> 23 124 B = six (granule)
-               "ILi64ELi32ELi48ELi64ELi32ELi64ELi256ELi640E": (2, 512, 512),   # (54 516 B: 244 B over three per CU at the 512-B allocation granule)
-                "ILi32ELi16ELi16ELi24ELi16ELi32ELi128ELi192E": (5, 512, 0), "ILi32ELi16ELi32ELi24ELi16ELi32ELi128ELi192E": (6, 512, 64)}   # Stack tier: J and M in global memory (50.1 -> 28.3 KB), native-style entry held to 256 registers (60 B)
+               # the capacity tier above 64 x 48 (round 4; the tiers above the other configurations are second bodies of their kernels since round 6).  The 256-row tier
+               # (four rows per lane, J in global memory since round 5: two per CU) spills in the polish's fp64 line search (424 B); it steps the few envs beyond 128 rows
+               # round 6: the row staging holds one slot (64 rows) at a time -- 65 972 -> 54 516 B (still two per CU, see below)
+               "ILi64ELi32ELi48ELi64ELi32ELi64ELi256ELi640E": (2, 512, 512)}   # (54 516 B: 244 B over three per CU at the 512-B allocation granule)
 
 
-def test_fused_kernel_configurations_keep_their_lds_and_register_budgets():
+def test_the_six_control_step_kernels_keep_their_lds_and_register_budgets():
+    """One k_step per compiled configuration (0-4 serve models, 5 is the tier above 3; the tiers above 0-2 are second bodies of their own k_step):
+    every one within the LDS, register and scratch budget of STEP_BUDGET."""
     ks = kernels(LIB)
     steps = {n: r for n, r in ks.items() if n.startswith("_Z6k_stepI")}
-    assert len(steps) == 8
+    assert len(steps) == 6
     for tag, (envs, regs, scratch) in STEP_BUDGET.items():
         (name,) = [n for n in steps if tag in n]
         r = steps[name]
@@ -44,17 +45,17 @@ def test_fused_kernel_configurations_keep_their_lds_and_register_budgets():
 def test_auxiliary_kernels_use_no_scratch():
     for name, r in kernels(LIB).items():
         if name.startswith("_Z11k_reset_obs") or name.startswith("_Z10k_step_dbg"):
-            # (the Lift-class tier's own translation unit, 32 x 16 with 128 rows, is not on the Lift path any more -- round 6: that tier is a body of the native
-            # kernel -- and its reset / debug kernels are never launched: the reset observation of every env comes from the native build)
-            assert r["scratch"] <= (64 if "ELi256E" not in name else 1024) or "ILi32ELi16ELi16ELi24ELi16ELi32ELi128ELi192E" in name, (name, r)   # the reset-observation pass (a few envs per control step) and the B = 1 debug entries share the step body (256-row tier: see STEP_BUDGET)
+            assert r["scratch"] <= (64 if "ELi256E" not in name else 1024), (name, r)   # the reset-observation pass (a few envs per control step) and the B = 1 debug entries share the step body (256-row tier: see STEP_BUDGET)
         elif not (name.startswith("_Z6k_step") or name.startswith("_Z11k_step_list")):
             assert r["scratch"] == 0, (name, r)
 
 
-def test_pmc_evidence_is_keyed_to_the_machine_code_of_its_configuration(tmp_path, monkeypatch):
+def test_pmc_evidence_is_keyed_to_the_machine_code_its_workload_runs(tmp_path, monkeypatch):
     """profiles/valu_count*.json / hbm_traffic*.json carry the sha of the library they were measured on AND of the machine code (.text + kernel descriptors) of
     their configuration's code object.  bench.py accepts a figure when either matches the library it runs -- a build that changed another configuration runs the
-    bit-identical kernel for this one -- and says "stale:<sha>" otherwise (never a silent null).  The committed evidence must be valid for the in-tree build."""
+    bit-identical kernel for this one -- and says "stale:<sha>" otherwise (never a silent null).  The committed evidence must be valid for the in-tree build.
+    The key includes the code object of the capacity tier the workload's envs move to: a body of the native kernel for Lift, Stack and Peg ("same-object"),
+    configuration 5's own object for PickPlace."""
     import hashlib
     import json
     import sys
@@ -92,4 +93,6 @@ def test_pmc_evidence_is_keyed_to_the_machine_code_of_its_configuration(tmp_path
     json.dump(rec, open(tmp_path / "profiles" / "valu_count.json", "w"))
     assert bench.pmc_evidence("valu_count.json", "valu_per_env_substep", lib_sha, "lift") == "stale:0123456789abcdef"
     monkeypatch.delenv("RSIM_NEWTON_REFINE")
-    assert wide_code_sha16(LIB, "stack") not in (None, "same-object", shas["stack"]) and wide_code_sha16(LIB, "pickplace") not in (None, shas["pickplace"])
+    # the tiers of Lift, Stack and Peg are bodies of their native kernels (Peg's workload runs without one); PickPlace's is configuration 5's own code object
+    assert wide_code_sha16(LIB, "stack") == wide_code_sha16(LIB, "peg") == "same-object"
+    assert wide_code_sha16(LIB, "pickplace") not in (None, "same-object", shas["pickplace"])

@@ -57,13 +57,14 @@ def config_code_sha16(lib, config):
     return hashlib.sha256(code).hexdigest()[:16]
 
 
-# the configuration whose own kernel (k_step_list) steps the envs of a bench configuration that outgrow its capacity; lift: the tier is a second body inside the
-# native code object (round 6), so the native sha covers it
-WIDE_TAG = {"stack": "ILi32ELi16ELi32ELi24ELi16ELi32ELi128ELi192E", "peg": "ILi64ELi32ELi48ELi64ELi32ELi32ELi128ELi640E", "pickplace": "ILi64ELi32ELi48ELi64ELi32ELi64ELi256ELi640E"}
+# the configuration whose own kernel (k_step_list) steps the envs of a bench configuration that outgrow its capacity: PickPlace's 256-row tier (configuration 5).
+# Lift, Stack and Peg have their tier as a second body inside the native code object (round 6), so the native sha covers it (Peg's JOINT_VELOCITY workload runs
+# without a tier at all: its controller state does not fit LDS)
+WIDE_TAG = {"pickplace": "ILi64ELi32ELi48ELi64ELi32ELi64ELi256ELi640E"}
 
 
 def wide_code_sha16(lib, config):
-    """sha256[:16] of the machine code of the code object that holds the capacity tier's kernel of a bench configuration ("same-object" for lift)."""
+    """sha256[:16] of the machine code of the code object that holds the capacity tier's kernel of a bench configuration ("same-object" for lift, stack and peg)."""
     import hashlib
     if config not in WIDE_TAG:
         return "same-object"
