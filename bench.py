@@ -20,6 +20,11 @@ o_i = (197 i) mod 500 and `--preroll` (default: the horizon) untimed launches ar
 from the ring) and then sits o_i genuine steps into its second episode.  Every timed launch then sees the steady-state mix of an RL rollout,
 including the ~B/500 on-device episode resets per launch and the asynchronous upkeep of the reset ring (`config.reset_ring`).
 
+A plain run does only what the headline figure needs: set-up, pre-roll, warm-up, the timed region, `--dump-outputs` and the result line.  `--full` adds
+everything else the benchmark measures: the open-loop and double-buffered regions of the same envs, the secondary regions of BASELINE configs[2..4]
+(Lift only, `config.other_configs`) and the CPU baseline; the `--no-*` options leave single parts of it out.  The line has the same fields either way
+(null where a part did not run), and the timed region gets the same inputs either way.
+
 Prints ONE JSON line on rank 0.  See DESIGN.md section 6 for the roofline / cpu_baseline definitions.
 """
 import argparse
@@ -165,7 +170,7 @@ def pmc_evidence(name, key, lib_sha, config=None):
     return f"stale:{d.get('lib_sha16')}"
 
 
-# (timed steps, untimed pre-roll launches) of the secondary regions of the default command: the quick-bench protocol of tools/ab_many.sh where a control step takes a few
+# (timed steps, untimed pre-roll launches) of the secondary regions of a --full run: the quick-bench protocol of tools/ab_many.sh where a control step takes a few
 # milliseconds (2 - 3 s per region), a shorter one for PickPlace (91 ms per step).  Round 5, session 15: ten steps after fifty said 603 K for Stack where the longer
 # protocols say 647 K (quick) / 620 - 650 K (full): the first control steps after a cold start carry the redo passes in which envs find their capacity tier.
 # Round 6: the pre-roll of every secondary region is the horizon, as for the headline -- every env has then passed an on-device reset and sits at its staggered
@@ -316,17 +321,19 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", choices=sorted(CONFIGS), default="lift", help="BASELINE configuration (module docstring); the driver's default is lift = configs[1]")
     ap.add_argument("--envs-per-gpu", type=int, default=0, help="default: the configuration's BASELINE batch size")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: the open-loop and double-buffered regions, the "
+                                                         "secondary regions of BASELINE configs[2..4] (lift only) and the CPU baseline (module docstring)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--phase", choices=("staggered", "fresh"), default="staggered", help="episode phase of the envs when the timed region starts (module docstring)")
     ap.add_argument("--preroll", type=int, default=-1, help="untimed launches before the warm-up in the staggered phase (default: the horizon)")
-    ap.add_argument("--groups", type=int, default=16, help="env blocks on their own HIP streams for the secondary open-loop figure; 1 = skip it")
-    ap.add_argument("--no-open-loop", action="store_true", help="skip the second and third timed regions (the same K steps with stream groups; two half-batches alternating)")
-    ap.add_argument("--no-double-buffer", action="store_true", help="skip the third timed region (two half-batches stepped alternately, closed-loop compatible)")
-    ap.add_argument("--no-other-configs", action="store_true", help="lift only: skip the short secondary regions of BASELINE configs[2..4] (config.other_configs)")
+    ap.add_argument("--groups", type=int, default=16, help="--full: env blocks on their own HIP streams for the secondary open-loop figure; 1 = skip it")
+    ap.add_argument("--no-open-loop", action="store_true", help="--full: skip the second and third timed regions (the same K steps with stream groups; two half-batches alternating)")
+    ap.add_argument("--no-double-buffer", action="store_true", help="--full: skip the third timed region (two half-batches stepped alternately, closed-loop compatible)")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full, lift only: skip the short secondary regions of BASELINE configs[2..4] (config.other_configs)")
     ap.add_argument("--other-steps", type=int, default=-1, help="timed lockstep control steps of each secondary configuration (default: OTHER_REGION, 50 where a step takes a few ms, 10 for PickPlace)")
     ap.add_argument("--other-preroll", type=int, default=-1, help="untimed launches before each secondary region (episode steps staggered as in the headline region; default: OTHER_REGION, 300 / 50)")
     ap.add_argument("--strict-collective", action="store_true", help="N > 1: exit with code 4 if the C-ABI RCCL communicator cannot be formed (default: reduce the rollout statistics through torch.distributed and say so at top level, \"collective\": \"fallback: ...\", and on stderr)")
-    ap.add_argument("--secondary-only", choices=sorted(CONFIGS), default=None, help="internal: run one secondary region and print its record (the default run starts one child per configuration)")
+    ap.add_argument("--secondary-only", choices=sorted(CONFIGS), default=None, help="internal: run one secondary region and print its record (a --full run of lift starts one child per configuration)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last step of the headline region returned as DIR/<name>.npy (dump_outputs)")
     args = ap.parse_args()
 
@@ -364,7 +371,9 @@ def main():
     K, W = args.steps, args.warmup
     P = (HORIZON if args.preroll < 0 else args.preroll) if args.phase == "staggered" else 0   # untimed pre-roll launches
     G = max(1, args.groups)
-    K2 = 0 if (args.no_open_loop or G == 1) else K   # second region: the same number of steps with stream groups (open loop)
+    K2 = 0 if (args.no_open_loop or G == 1) else K   # second region of --full: the same number of steps with stream groups (open loop)
+    # the reset ring (its slot of an episode is the episode mod its size) and the action tape are sized for the --full run whether or not this is one: a plain
+    # run's timed region gets exactly the inputs of a --full run's
     env = build_env(args.config, flat, cfg, ids, local_rank, 3 + (P + W + K + K2) // HORIZON)
     adim = env.model.action_dim
     tape = torch.tensor(lift.env_actions(ids, P + K + W + K2, action_dim=adim), device=dev)  # whole action tape resident in HBM
@@ -412,13 +421,13 @@ def main():
         dump_outputs(env, ids, args.dump_outputs, rank, world)
     if os.environ.get("RSIM_BENCH_TRACE"):
         print("per-step ms:", " ".join(f"{r[0]:.2f}" for r in evms), file=sys.stderr)
-    # ---- secondary regions: BASELINE configs[2..4] at their stated batch sizes, a short lockstep region each, so that the clock of whoever runs the
-    # default command also covers them.  After the headline region (which they cannot disturb) and BEFORE the open-loop / double-buffered regions of the headline
+    # ---- secondary regions (--full): BASELINE configs[2..4] at their stated batch sizes, a short lockstep region each.
+    # After the headline region (which they cannot disturb) and BEFORE the open-loop / double-buffered regions of the headline
     # configuration: behind those (sixteen stream groups, two more batches) the children of session 16 read 6 - 9 % lower than the same regions stand-alone or
     # behind a parent that had run the headline region only (session 17: identical); 12 s of sustained load alone costs 1 % (session 18, tools/sustained_load.py).
     # Every rank takes part (weak scaling like the headline).
     other = None
-    if args.config == "lift" and not args.no_other_configs:
+    if args.full and args.config == "lift" and not args.no_other_configs:
         env.bank_quiesce()
         other = {}
         for oc in ("stack", "peg", "pickplace"):
@@ -441,7 +450,7 @@ def main():
                     other[oc] = {"error": f"{type(e).__name__}: {e}"}
 
     open_loop = None
-    if K2:
+    if args.full and K2:
         env.batch.set_stream_groups(G)
         dt2, ev2 = timed(W + K, K2, [torch.cuda.ExternalStream(env.batch.group_stream(g), device=dev) for g in range(G)])
         env.batch.set_stream_groups(1)
@@ -452,7 +461,7 @@ def main():
     # ---- double-buffered closed loop: the batch as two halves stepped alternately, each half's step t + 1 issued only after the HOST has seen its
     # step t complete (stream synchronisation = the point where a policy would read that half's observations) -- while the other half is stepping
     double_buffered = None
-    if K2 and not args.no_double_buffer:
+    if args.full and K2 and not args.no_double_buffer:
         dt3, stale3, hl = double_buffered_region(args.config, flat, cfg, ids, local_rank, dev, world, dr, P + W, K, adim)
         double_buffered = {"value": B * world * K / dt3, "ms_per_step": 1e3 * dt3 / K, "steps": K, "halves": hl, "bank_stale": stale3,
                            "note": "closed-loop compatible: two half-batches (two rsim batches on their own streams) stepped alternately; the host waits for a half's "
@@ -537,7 +546,7 @@ def main():
                          # when profiles/valu_count.json was measured on another build
                          "issue": issue},
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args.config, flat, cfg)
         elif world == 1:
             out["cpu_baseline"] = None

@@ -1,7 +1,8 @@
 """bench.py's control flow and output contract, run on the CPU against a stand-in batch (no kernel, no oracle): the driver parses ONE JSON line from rank 0, so a
 NameError on a path only a GPU box reaches would cost the round its measurement.  Everything device-side is replaced (torch.cuda, the env the factory would build, the
-child processes of the secondary regions); what runs is main() itself: argument handling, pre-roll / warm-up / timed regions, the order of the regions (the secondary
-configurations directly behind the headline region, ahead of the open-loop and double-buffered ones), statistics, PMC evidence lookup and the JSON assembly."""
+child processes of the secondary regions); what runs is main() itself: argument handling, pre-roll / warm-up / timed regions, the headline region alone in a plain run,
+the order of the regions of a --full run (the secondary configurations directly behind the headline region, ahead of the open-loop and double-buffered ones),
+statistics, PMC evidence lookup and the JSON assembly."""
 import json
 import os
 import subprocess
@@ -69,15 +70,17 @@ class _Batch:
 
 
 class _Env:
-    def __init__(self, n, log):
+    def __init__(self, n, log, episodes):
         self.batch = _Batch(n, log)
         self.model = types.SimpleNamespace(action_dim=7, nobs=60, cstate_size=32, int=lambda name: 128)
         self.n, self.log, self.steps = n, log, 0
+        log.append(("env", n, episodes))
 
     def step(self, a):
         assert a.shape == (self.n, 7)
         self.steps += 1
         self.log.append(("step", self.n))
+        self.log.append(("action", a.numpy().tobytes()))
 
     def bank_stats(self):
         return {"steps": self.steps, "polls": self.steps // 2, "rows": 3 * self.steps, "tick_s": 1e-6 * self.steps, "upkeep_s": 2e-6 * self.steps}
@@ -115,7 +118,7 @@ def _run_main(monkeypatch, capsys, argv, child=None):
             return torch.device("cpu")
 
     monkeypatch.setattr(bench, "torch", _Torch())
-    monkeypatch.setattr(bench, "build_env", lambda config, flat, cfg, ids, device, episodes: _Env(len(ids), log))
+    monkeypatch.setattr(bench, "build_env", lambda config, flat, cfg, ids, device, episodes: _Env(len(ids), log, episodes))
     monkeypatch.setattr(bench.shard, "max_over_ranks", lambda x, device="cpu": float(x))
 
     def default_child(cmd, **kw):
@@ -135,7 +138,7 @@ def _run_main(monkeypatch, capsys, argv, child=None):
 
 
 def test_default_command_flow_and_contract(monkeypatch, capsys):
-    d, log = _run_main(monkeypatch, capsys, ["--steps", "4", "--warmup", "2", "--preroll", "3", "--envs-per-gpu", "8", "--groups", "2", "--no-cpu-baseline"])
+    d, log = _run_main(monkeypatch, capsys, ["--full", "--steps", "4", "--warmup", "2", "--preroll", "3", "--envs-per-gpu", "8", "--groups", "2", "--no-cpu-baseline"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
     assert d["n_gpus"] == 1 and d["steps"] == 4 and d["warmup"] == 2 and d["higher_is_better"] is True and d["scaling"] == "weak" and d["dtype"] == "f32"
@@ -159,15 +162,39 @@ def test_default_command_flow_and_contract(monkeypatch, capsys):
     assert [e for e in log[groups_on:] if e == ("step", 8)] == [("step", 8)] * 4 and sum(e == ("step", 4) for e in log) == 2 * (3 + 2 + 4)
 
 
+def test_plain_run_is_the_headline_region_alone(monkeypatch, capsys):
+    """Without --full the run is set-up, pre-roll, warm-up, the timed region and the line: no child process, no stream groups, no half batches, no CPU
+    baseline.  Its line has the fields of a --full line, and its timed region the inputs of a --full run: the same actions and a reset ring of the same size
+    (493 + 2 + 4 launches stay inside one horizon, the --full run's 4 open-loop launches go past it)."""
+    import bench
+
+    monkeypatch.setattr(bench, "cpu_baseline", lambda *a, **k: pytest.fail("a plain run timed the CPU baseline"))
+    argv = ["--steps", "4", "--warmup", "2", "--preroll", "493", "--envs-per-gpu", "8", "--groups", "2"]
+    d, log = _run_main(monkeypatch, capsys, argv)
+    assert {e[0] for e in log} == {"env", "set", "step", "action"} and [e for e in log if e[0] == "step"] == [("step", 8)] * (493 + 2 + 4)
+    c = d["config"]
+    assert d["cpu_baseline"] is None and c["open_loop"] is None and c["double_buffered"] is None and c["other_configs"] is None
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["steps"] == 4 and d["warmup"] == 2 and c["episode_window"] == [495, 499]
+
+    monkeypatch.setattr(bench, "cpu_baseline", lambda *a, **k: {"value": 1.0})
+    f, full_log = _run_main(monkeypatch, capsys, argv + ["--full"])
+    assert set(f) == set(d) and set(f["config"]) == set(c) and f["cpu_baseline"] == {"value": 1.0}
+    assert f["config"]["open_loop"] and f["config"]["double_buffered"] and set(f["config"]["other_configs"]) == {"stack", "peg", "pickplace"}
+    envs = [e for e in log if e[0] == "env"]
+    assert envs == [("env", 8, 4)] and [e for e in full_log if e[0] == "env"][0] == envs[0]
+    actions = [e for e in log if e[0] == "action"]
+    assert actions == [e for e in full_log if e[0] == "action"][:len(actions)]
+
+
 def test_other_config_line_and_a_failing_child(monkeypatch, capsys):
-    d, log = _run_main(monkeypatch, capsys, ["--config", "stack", "--steps", "2", "--warmup", "1", "--preroll", "0", "--envs-per-gpu", "4", "--no-open-loop", "--no-cpu-baseline"])
+    d, log = _run_main(monkeypatch, capsys, ["--full", "--config", "stack", "--steps", "2", "--warmup", "1", "--preroll", "0", "--envs-per-gpu", "4", "--no-open-loop", "--no-cpu-baseline"])
     assert "Stack" in d["metric"] and d["config"]["other_configs"] is None and d["config"]["open_loop"] is None and not any(e[0] == "child" for e in log)
 
     # a child that dies (a fault of the GPU queue aborts the process that owns it) is reported in the record; the headline line stands
     def dying(cmd, **kw):
         return types.SimpleNamespace(returncode=-6, stderr="Memory access fault by GPU node-2\n", stdout="")
 
-    d, log = _run_main(monkeypatch, capsys, ["--steps", "2", "--warmup", "1", "--preroll", "0", "--envs-per-gpu", "4", "--no-open-loop", "--no-cpu-baseline"], child=dying)
+    d, log = _run_main(monkeypatch, capsys, ["--full", "--steps", "2", "--warmup", "1", "--preroll", "0", "--envs-per-gpu", "4", "--no-open-loop", "--no-cpu-baseline"], child=dying)
     oc = d["config"]["other_configs"]
     assert set(oc) == {"stack", "peg", "pickplace"} and all("Memory access fault" in v["error"] for v in oc.values()) and d["value"] > 0
 
@@ -178,7 +205,7 @@ def test_dump_outputs_holds_the_last_timed_step(monkeypatch, capsys, tmp_path):
     import bench
 
     names = ("env_ids", "obs", "reward", "done", "success", "terminal_obs")
-    argv = ["--steps", "3", "--warmup", "1", "--preroll", "0", "--envs-per-gpu", "8", "--groups", "2", "--no-other-configs", "--no-cpu-baseline", "--dump-outputs"]
+    argv = ["--full", "--steps", "3", "--warmup", "1", "--preroll", "0", "--envs-per-gpu", "8", "--groups", "2", "--no-other-configs", "--no-cpu-baseline", "--dump-outputs"]
     d, log = _run_main(monkeypatch, capsys, argv + [str(tmp_path / "all")])
     first_get = log.index(("get", "obs"))
     assert [e for e in log[:first_get] if e[0] == "step"] == [("step", 8)] * (1 + 3) and first_get < log.index(("groups", 2))

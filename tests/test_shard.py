@@ -131,7 +131,7 @@ def test_bench_launches_its_own_ranks(config):
 
 
 def test_bench_secondary_region_child_fails_loudly_without_a_gpu():
-    """The default `python bench.py` times BASELINE configs[2..4] in one child process each (`--secondary-only <config>`); a child that dies -- a fault of the GPU queue
+    """`python bench.py --full` times BASELINE configs[2..4] in one child process each (`--secondary-only <config>`); a child that dies -- a fault of the GPU queue
     aborts the process that owns it -- must leave a non-zero exit code and no JSON record, which the parent reports as `{"error": ...}` in config.other_configs."""
     import torch
     if torch.cuda.is_available():

@@ -7,7 +7,7 @@
 # steps (arguments after ':' are passed on):
 #   probe                       tools/box_probe.py; a faulty box ends the session (exit 3)
 #   tests[:pytest args]         python -m pytest tests -m gpu -q
-#   bench:<cfg>[:args]          python bench.py --config <cfg> args           -> <tag>_bench_<cfg>.json
+#   bench:<cfg>[:args]          python bench.py --full --config <cfg> args    -> <tag>_bench_<cfg>.json
 #   quick:<cfg>[:args]          bench without the cpu / open-loop / double-buffered legs (lockstep figure only) -> <tag>_quick_<cfg>.json
 #   stats:<cfg>[:args]          rocprofv3 --kernel-trace --stats of a short quick bench   -> <tag>_kernel_stats_<cfg>.csv
 #   pmc:<cfg>[:sets]            tools/pmc_pass.sh (default sets: sq1 hbm1 hbm2), then valu_count / hbm_traffic json keyed to this build
@@ -43,7 +43,7 @@ for step in "$@"; do
     tests)
       timeout 1200 python -m pytest tests -m gpu -q ${a1:-} > $O/${tag}_pytest_gpu.txt 2>&1; tail -15 $O/${tag}_pytest_gpu.txt | cut -c1-300;;
     bench)
-      timeout 900 python bench.py --config $a1 ${a2:-$(bench_extra $a1)} > $O/${tag}_bench_$a1.json 2> $O/${tag}_bench_$a1.err; line $O/${tag}_bench_$a1.json; tail -3 $O/${tag}_bench_$a1.err | cut -c1-300;;
+      timeout 900 python bench.py --full --config $a1 ${a2:-$(bench_extra $a1)} > $O/${tag}_bench_$a1.json 2> $O/${tag}_bench_$a1.err; line $O/${tag}_bench_$a1.json; tail -3 $O/${tag}_bench_$a1.err | cut -c1-300;;
     quick)
       timeout 400 python bench.py --config $a1 ${a2:-$(quick_extra $a1)} --no-open-loop --no-cpu-baseline --no-double-buffer --no-other-configs > $O/${tag}_quick_$a1.json 2> $O/${tag}_quick_$a1.err; line $O/${tag}_quick_$a1.json; tail -3 $O/${tag}_quick_$a1.err | cut -c1-300;;
     stats)

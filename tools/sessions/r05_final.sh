@@ -8,7 +8,7 @@ RSIM_PARITY_SAMPLE=256 timeout 900 python -m pytest tests/test_full_size_parity.
 grep -E "polish exits|oracle fed|unfinished|stopped short|passed|failed|^E  " $O/r05_z_parity_pickplace.txt | cut -c1-420 | head -10
 for k in gripper objects "rel dforce" "objective gap"; do grep -E "$k per env" $O/r05_z_parity_pickplace.txt | awk '{n=NF; printf "   %s tail:", $1; for(i=n-9;i<=n;i++) printf " %s", $i; print ""}'; done
 echo "=== driver-like bench"
-( time timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/r05_z_bench_driver_like.json 2> $O/r05_z_bench_driver_like.err ) 2>&1 | tail -3
+( time timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/r05_z_bench_driver_like.json 2> $O/r05_z_bench_driver_like.err ) 2>&1 | tail -3
 python - <<'PY'
 import json
 d = json.loads(open("gpurun_out/r05_z_bench_driver_like.json").read().strip().splitlines()[-1])

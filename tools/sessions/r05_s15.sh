@@ -9,7 +9,7 @@ timeout 150 python -m pytest tests -m gpu -q > $O/${T}_pytest_gpu.txt 2>&1
 grep -E "passed|failed" $O/${T}_pytest_gpu.txt | tail -2 | cut -c1-300 | tee -a $O/${T}_log.txt
 echo "[s15] suite done at $SECONDS s" | tee -a $O/${T}_log.txt
 if [ $(left) -gt 60 ]; then
-  timeout $(( $(left) - 5 )) python bench.py > $O/${T}_bench_default.json 2> $O/${T}_bench_default.err
+  timeout $(( $(left) - 5 )) python bench.py --full > $O/${T}_bench_default.json 2> $O/${T}_bench_default.err
   python - <<'PY' | tee -a gpurun_out/r05_s15_log.txt
 import json
 try:

@@ -3,7 +3,7 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT && mkdir -p gpurun_out
 O=gpurun_out; T=r05_s16
 sha256sum robosuite_amd/librsim_hip.so | cut -c1-16 | tee $O/${T}_log.txt
-timeout 100 python bench.py > $O/${T}_bench_lift.json 2> $O/${T}_bench_lift.err
+timeout 100 python bench.py --full > $O/${T}_bench_lift.json 2> $O/${T}_bench_lift.err
 python - <<'PY' | tee -a gpurun_out/r05_s16_log.txt
 import json
 try:

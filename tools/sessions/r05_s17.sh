@@ -6,7 +6,7 @@ O=gpurun_out; T=r05_s17
 one() { timeout 60 python bench.py --secondary-only stack 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$1 stand-alone stack', round(d['value']), d['ms_per_step'], d['steps'], d['preroll'])" | tee -a $O/${T}_log.txt; }
 : > $O/${T}_log.txt
 one first
-timeout 70 python bench.py --no-cpu-baseline --steps 20 --warmup 5 --preroll 50 --no-open-loop 2>/dev/null | tail -1 | python -c "
+timeout 70 python bench.py --full --no-cpu-baseline --steps 20 --warmup 5 --preroll 50 --no-open-loop 2>/dev/null | tail -1 | python -c "
 import json,sys; d=json.loads(sys.stdin.read())
 for k, v in d['config']['other_configs'].items(): print('child of the default command', k, round(v.get('value', 0)), v.get('ms_per_step'), v.get('error'))" | tee -a $O/${T}_log.txt
 [ $SECONDS -lt 75 ] && one second

@@ -12,4 +12,4 @@ for R in 1 3 8; do
   echo "=== parity, $R polish passes"; grep -E "per env, relative, sorted|objective gap per env|rel dforce per env|passed|failed" $O/r05_b_parity_pickplace_R$R.txt | cut -c1-1800
 done
 echo "=== driver-like bench"
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/r05_b_bench_driver_like.json 2> $O/r05_b_bench_driver_like.err; tail -c 3000 $O/r05_b_bench_driver_like.json; tail -3 $O/r05_b_bench_driver_like.err
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/r05_b_bench_driver_like.json 2> $O/r05_b_bench_driver_like.err; tail -c 3000 $O/r05_b_bench_driver_like.json; tail -3 $O/r05_b_bench_driver_like.err

@@ -9,7 +9,7 @@ bash tools/gpu_session.sh ${TAG} probe tests pmc:lift pmc:stack pmc:peg pmc:pick
 echo "=== windows"
 timeout 600 python tools/window_trace.py --prerolls 500,700,900,1100 --out $O/${TAG}_window_trace.json > $O/${TAG}_window_trace.txt 2>&1; grep -v amdgpu.ids $O/${TAG}_window_trace.txt | cut -c1-200
 echo "=== driver-like bench"
-( time timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/${TAG}_bench_driver_like.json 2> $O/${TAG}_bench_driver_like.err ) 2>&1 | tail -3
+( time timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/${TAG}_bench_driver_like.json 2> $O/${TAG}_bench_driver_like.err ) 2>&1 | tail -3
 python - <<'PY'
 import json, os
 d = json.loads(open(os.environ["TAG_FILE"]).read().strip().splitlines()[-1])

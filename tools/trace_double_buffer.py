@@ -1,4 +1,4 @@
-"""How two alternating half-batches fill the chip: from a `rocprofv3 --kernel-trace` of bench.py, the k_step dispatches of the double-buffered region (the last
+"""How two alternating half-batches fill the chip: from a `rocprofv3 --kernel-trace` of `bench.py --full`, the k_step dispatches of the double-buffered region (the last
 2 K control-step launches of the run, 2048-env grids on two queues) -- how long a launch lasts, how much of it overlaps the other half's launch, and the
 fraction of the region during which 0 / 1 / 2 control-step kernels are in flight.  For comparison the lockstep region (4096-env grids).
 Usage (GPU box): python tools/trace_double_buffer.py <rocprof output dir> <K>"""
