@@ -124,6 +124,11 @@ typedef unsigned long long u64;
 #ifndef RSIM_NOHULLPOOL
 #define RSIM_NOHULLPOOL 0   /* 1: no LDS-resident hull vertices in the middle configurations either (all hulls scanned from global memory, as the 32 x 16 build does) */
 #endif
+#ifdef RSIM_NO_CAND_PREFETCH   /* A/B and test builds: every candidate's descriptor is fetched when the candidate is visited, as before the prefetch (Sim::collision) */
+#define RSIM_CAND_PF 0
+#else
+#define RSIM_CAND_PF 64
+#endif
 #ifndef RSIM_LS_MAXSLOT
 #define RSIM_LS_MAXSLOT 4   // rows per lane up to which the polish carries the fp64 line search (4: every configuration)
 #endif
@@ -937,10 +942,11 @@ struct SupGeom {
   bool regs;
 };
 template <class SM>
-__device__ __forceinline__ SupGeom sup_load(cmr_t cm, cmr_t cmg, int g, gcf mesh_vert, int lane, V3 org) {
+__device__ __forceinline__ SupGeom sup_load(cmr_t cmg, int g, int t, int gm, gcf mesh_vert, int lane, V3 org) {
   SupGeom s;
-  s.t = uni(cm->gtype[g]);          // scalar: the type dispatch of every support call becomes s_cbranch on an SGPR instead of exec-masked regions
-  const int gm = uni(cm->gmesh[g]);
+  // type and hull word (adr | count << 16) come with the candidate's descriptor (Sim::collision), both uniform: the hull-vertex loads below need no
+  // load before them and issue together with the frame's LDS reads; the type dispatch of every support call is s_cbranch on an SGPR
+  s.t = t;
   s.adr = gm & 0xffff; s.num = gm >> 16;
   s.R = ldm(sm.gmat + 9 * g);
   s.p = ld3(sm.gpos + 3 * g) - org; s.h = ld3(cmg->gst + 8 * g);
@@ -1895,24 +1901,26 @@ struct Sim {
   __device__ __forceinline__ V3 support(int g, V3 dir, V3 org = {0.f, 0.f, 0.f}) { pf.count(RP_N_SUPPORT, 1); return geom_support<SM>(cm, cmf(MK_gst), g, dir, (gcf)m.mesh_vert, lane, org); }
 
   // contact parameters of a geom pair (MuJoCo's mixing rules: priority, solmix-weighted solref/solimp, max friction);
-  // evaluated once per candidate pair, uniformly by every lane, from the per-geom table staged in LDS
-  struct CPar { int dim; float solref[2], solimp[5], fr[3]; float margin_gap; int b1, b2; };
+  // evaluated once per candidate pair by the lane that fetches the candidate's descriptor (collision()).  The values stay in THAT lane's registers:
+  // `src` (uniform) names the lane, and emit_contacts() -- the only reader -- broadcasts what a contact stores
+  struct CPar { int dbb; float solref[2], solimp[5], fr[3]; float margin_gap; int src; };   // dbb: dim | body 1 << 8 | body 2 << 16
   __device__ __forceinline__ CPar contact_params(int g1, int g2, float margin, float gap) const {
     CPar cp;
+    cp.src = 0;
     cp.margin_gap = margin - gap;
-    cp.b1 = cm->gbody[g1]; cp.b2 = cm->gbody[g2];   // stored with the contact (geom | body << 8): the row builders need the body, not a second dependent global load
+    const int b1 = cm->gbody[g1], b2 = cm->gbody[g2];   // stored with the contact (geom | body << 8): the row builders need the body, not a second dependent global load
     gcf a = cmf(MK_gpar)->gpar + 12 * g1;
     gcf b = cmf(MK_gpar)->gpar + 12 * g2;
     const int c1 = cm->gcp[g1], c2 = cm->gcp[g2];
     const int p1 = c1 >> 8, p2 = c2 >> 8, d1 = c1 & 255, d2 = c2 & 255;
     if (p1 != p2) {
       gcf w = p1 > p2 ? a : b;
-      cp.dim = p1 > p2 ? d1 : d2;
+      cp.dbb = p1 > p2 ? d1 : d2;
       for (int k = 0; k < 3; k++) cp.fr[k] = w[k];
       for (int k = 0; k < 2; k++) cp.solref[k] = w[3 + k];
       for (int k = 0; k < 5; k++) cp.solimp[k] = w[5 + k];
     } else {
-      cp.dim = d1 > d2 ? d1 : d2;
+      cp.dbb = d1 > d2 ? d1 : d2;
       const float s1 = a[10], s2 = b[10];
       float mix;
       if (s1 >= 1e-15f && s2 >= 1e-15f) mix = s1 / (s1 + s2);
@@ -1923,11 +1931,30 @@ struct Sim {
       for (int k = 0; k < 5; k++) cp.solimp[k] = mix * a[5 + k] + (1 - mix) * b[5 + k];
       for (int k = 0; k < 3; k++) cp.fr[k] = fmaxf(a[k], b[k]);
     }
+    cp.dbb |= (b1 << 8) | (b2 << 16);
     return cp;
+  }
+  // What a candidate visit needs before its first support evaluation -- pair, geoms, types, hull words, margin -- and the pair's contact parameters: some
+  // fourteen dependent global loads.  collision() has lane ci fetch the descriptor of candidate ci, all candidates of the substep at once, and the serial
+  // loop over the candidates reads lane ci's registers (v_readlane).  UNI: the caller passes a uniform pair and every lane fetches the same descriptor
+  // (candidates beyond the 64 lanes, RSIM_NO_CAND_PREFETCH builds).
+  struct CDesc { int w0, gm1, gm2; float margin; CPar cp; };   // w0: pair | g1 << 10 | g2 << 16 | type 1 << 22 | type 2 << 25
+  static_assert(SM::NPT_ * 64 <= 1024, "pair index in ten bits of CDesc::w0");
+  template <bool UNI>
+  __device__ __forceinline__ CDesc cand_desc(int p) const {
+    CDesc d;
+    int g1 = IT(IO_pair_g1, p), g2 = IT(IO_pair_g2, p);
+    if (UNI) { g1 = uni(g1); g2 = uni(g2); }
+    d.w0 = p | (g1 << 10) | (g2 << 16) | (cm->gtype[g1] << 22) | (cm->gtype[g2] << 25);
+    d.gm1 = cm->gmesh[g1]; d.gm2 = cm->gmesh[g2];
+    d.margin = fmaxf(cmf(MK_gst)->gst[8 * g1 + 7], cmf(MK_gst)->gst[8 * g2 + 7]);
+    const float gap = fmaxf(cmf(MK_gpar)->gpar[12 * g1 + 11], cmf(MK_gpar)->gpar[12 * g2 + 11]);
+    d.cp = contact_params(g1, g2, d.margin, gap);
+    return d;
   }
   // Lanes with has == true append one contact each, in lane order, at most `cap` of them (the rest are dropped);
   // every lane of the wave must call this (ballot + shared counter).
-  __device__ __forceinline__ void emit_contacts(bool has, int cap, float dist, V3 pos, V3 nrm, int g1, int g2, const CPar& cp) {
+  __device__ __forceinline__ void emit_contacts(bool has, int cap, float dist, V3 pos, V3 nrm, int g1, int g2, const CPar& cpl) {
     const u64 mk = __ballot(has);
     const int rank = __popcll(mk & lanemask_lt(lane));
     const int base = sm.ncon;
@@ -1943,20 +1970,28 @@ struct Sim {
 #pragma unroll
         for (int k = 0; k < 9; k++) Cgp()[SM::CG_FRAME_ + 9 * c + k] = fr_[k]; }
       else make_frame(nrm, sm.cframe + 9 * c);
-      sm.cg1[c] = g1 | (cp.b1 << 8); sm.cg2[c] = g2 | (cp.b2 << 8); sm.cdim[c] = cp.dim;
-      if constexpr (CG) {
-        Cgp()[SM::CG_MARGIN_ + c] = cp.margin_gap;
-        Cgp()[SM::CG_SOLREF_ + 2 * c] = cp.solref[0]; Cgp()[SM::CG_SOLREF_ + 2 * c + 1] = cp.solref[1];
+      // the pair's parameters from the lane that holds them (v_readlane reads whatever the exec mask is): paid by the visits that end in a contact only
+      const int dbb = uni(__builtin_amdgcn_readlane(cpl.dbb, cpl.src));
+      sm.cg1[c] = g1 | (((dbb >> 8) & 255) << 8); sm.cg2[c] = g2 | ((dbb >> 16) << 8); sm.cdim[c] = dbb & 255;
+      const float margin_gap = bcast(cpl.margin_gap, cpl.src), solref0 = bcast(cpl.solref[0], cpl.src), solref1 = bcast(cpl.solref[1], cpl.src);
+      const float fr0 = bcast(cpl.fr[0], cpl.src), fr1 = bcast(cpl.fr[1], cpl.src), fr2 = bcast(cpl.fr[2], cpl.src);
+      float solimp[5];
 #pragma unroll
-        for (int k = 0; k < 5; k++) Cgp()[SM::CG_SOLIMP_ + 5 * c + k] = cp.solimp[k];
+      for (int k = 0; k < 5; k++) solimp[k] = bcast(cpl.solimp[k], cpl.src);
+      if constexpr (CG) {
+        Cgp()[SM::CG_MARGIN_ + c] = margin_gap;
+        Cgp()[SM::CG_SOLREF_ + 2 * c] = solref0; Cgp()[SM::CG_SOLREF_ + 2 * c + 1] = solref1;
+#pragma unroll
+        for (int k = 0; k < 5; k++) Cgp()[SM::CG_SOLIMP_ + 5 * c + k] = solimp[k];
         gwf f = Cgp() + SM::CG_FRI_ + 5 * c;
-        f[0] = cp.fr[0]; f[1] = cp.fr[0]; f[2] = cp.fr[1]; f[3] = cp.fr[2]; f[4] = cp.fr[2];
+        f[0] = fr0; f[1] = fr0; f[2] = fr1; f[3] = fr2; f[4] = fr2;
       } else {
-        sm.cmargin[c] = cp.margin_gap;
-        sm.csolref[2 * c] = cp.solref[0]; sm.csolref[2 * c + 1] = cp.solref[1];
-        for (int k = 0; k < 5; k++) sm.csolimp[5 * c + k] = cp.solimp[k];
+        sm.cmargin[c] = margin_gap;
+        sm.csolref[2 * c] = solref0; sm.csolref[2 * c + 1] = solref1;
+#pragma unroll
+        for (int k = 0; k < 5; k++) sm.csolimp[5 * c + k] = solimp[k];
         float* f = sm.cfri + 5 * c;
-        f[0] = f[1] = cp.fr[0]; f[2] = cp.fr[1]; f[3] = f[4] = cp.fr[2];
+        f[0] = f[1] = fr0; f[2] = fr1; f[3] = f[4] = fr2;
       }
     }
     SYNC();
@@ -2140,11 +2175,11 @@ struct Sim {
       ((gw4)wout)[0] = v4f{q[0], q[1], q[2], mpr_portal ? 2.f : 0.f}; ((gw4)wout)[1] = v4f{q[3], q[4], q[5], 0.f}; ((gw4)wout)[2] = v4f{q[6], q[7], q[8], 0.f};
     }
   }
-  __device__ __forceinline__ void convex_convex(int g1, int g2, float margin, const CPar& cp, V3 wd, int wh, gwf wout) {
+  __device__ __forceinline__ void convex_convex(int g1, int g2, int t1, int t2, int gm1, int gm2, float margin, const CPar& cp, V3 wd, int wh, gwf wout) {
     const float tol = 1e-6f;
     const int mprstat_s0 = pf.c_support; (void)mprstat_s0;
     const V3 org = ld3(sm.gpos + 3 * g1);   // all support points relative to the first geom's position (see geom_support)
-    const SupGeom sg1 = sup_load<SM>(cm, cmf(MK_gst), g1, (gcf)m.mesh_vert, lane, org), sg2 = sup_load<SM>(cm, cmf(MK_gst), g2, (gcf)m.mesh_vert, lane, org);
+    const SupGeom sg1 = sup_load<SM>(cmf(MK_gst), g1, t1, gm1, (gcf)m.mesh_vert, lane, org), sg2 = sup_load<SM>(cmf(MK_gst), g2, t2, gm2, (gcf)m.mesh_vert, lane, org);
     if (wh == 1) {
       const V3 a1 = sup(sg1, wd), a2 = sup(sg2, -wd);
       const float s_w = dot(a1 - a2, wd);
@@ -2484,13 +2519,20 @@ struct Sim {
     // warm-start records of the candidates, one per lane, in flight while the first pairs are processed (candidates beyond 64 start cold)
     v4f wc = {0.f, 0.f, 0.f, 0.f};
     if (mprc && lane < ncand) { typedef const v4f __attribute__((address_space(1)))* gc4; wc = *(gc4)(mprc + MPRC * sm.u.b.cand[lane]); }
+    // ... and their descriptors, one per lane as well: the dependent loads of a candidate visit (pair -> geoms -> types, hull words, margins, the
+    // pair's contact parameters) are made once for all candidates together instead of once per candidate in series
+    CDesc D = {};
+    if (lane < ncand && lane < RSIM_CAND_PF) D = cand_desc<false>(sm.u.b.cand[lane]);
     for (int ci = 0; ci < ncand; ci++) {
       phase();
-      int p = uni(sm.u.b.cand[ci]);
-      int g1 = uni(IT(IO_pair_g1, p)), g2 = uni(IT(IO_pair_g2, p));
-      int t1 = uni(cm->gtype[g1]), t2 = uni(cm->gtype[g2]);
-      const float margin = fmaxf(cmf(MK_gst)->gst[8 * g1 + 7], cmf(MK_gst)->gst[8 * g2 + 7]), gap = fmaxf(cmf(MK_gpar)->gpar[12 * g1 + 11], cmf(MK_gpar)->gpar[12 * g2 + 11]);
-      const CPar cp = contact_params(g1, g2, margin, gap);
+      // candidates beyond the lanes: fetched here, uniformly, into the same registers (the prefetched descriptors are all behind by then)
+      if (ci >= RSIM_CAND_PF) D = cand_desc<true>(uni(sm.u.b.cand[ci]));
+      const int src = ci & 63;
+      const int w0 = uni(__builtin_amdgcn_readlane(D.w0, src));
+      const int p = w0 & 1023, g1 = (w0 >> 10) & 63, g2 = (w0 >> 16) & 63, t1 = (w0 >> 22) & 7, t2 = (w0 >> 25) & 7;
+      const float margin = bcast(D.margin, src);
+      CPar cp = D.cp;
+      cp.src = src;
       const int sup0 = pf.c_support;
       if (t1 == G_PLANE && t2 == G_BOX) {
         const V3 nrm = v3(sm.gmat[9 * g1 + 2], sm.gmat[9 * g1 + 5], sm.gmat[9 * g1 + 8]);
@@ -2519,7 +2561,7 @@ struct Sim {
         V3 wd = v3(0.f, 0.f, 0.f);
         int wh = 0;
         if (mprc && ci < 64) { wd = v3(bcast(wc[0], ci), bcast(wc[1], ci), bcast(wc[2], ci)); wh = uni((int)bcast(wc[3], ci)); if ((wh == 2 || wh == 3) && !mpr_portal) wh = 0; }
-        convex_convex(g1, g2, margin, cp, wd, wh, mprc ? mprc + MPRC * p : nullptr);
+        convex_convex(g1, g2, t1, t2, uni(__builtin_amdgcn_readlane(D.gm1, src)), uni(__builtin_amdgcn_readlane(D.gm2, src)), margin, cp, wd, wh, mprc ? mprc + MPRC * p : nullptr);
         pf.mark(RP_MPR); pf.count(RP_N_MPR, 1);
       }
       if (pf.pairs && lane == 0 && pf.acc) { atomicAdd(pf.pairs + p, 1ull); atomicAdd(pf.pairs + RSIM_PAIR_MAX + p, (unsigned long long)(pf.c_support - sup0)); }

@@ -1,0 +1,94 @@
+"""The narrow phase fetches the descriptors of a substep's candidate pairs -- pair, geoms, types, hull words, margin and the pair's contact parameters -- one
+candidate per lane, once, and the serial loop over the candidates reads them from that lane's registers (Sim::collision, cand_desc).  Only where and when the
+loads are issued differs from fetching them candidate by candidate: no operand, operation or order of any floating-point expression.  So a build with the
+prefetch compiled out (-DRSIM_NO_CAND_PREFETCH: every candidate takes the per-candidate path the candidates beyond the 64 lanes take) must step to the same
+state BIT FOR BIT.  The bound is equality: both builds evaluate the same expressions on the same inputs.
+
+Each build runs in a child process of its own (one process binds one library: RSIM_LIB)."""
+import hashlib
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "robosuite_amd", "csrc")
+LIB = os.path.join(ROOT, "robosuite_amd", "librsim_hip.so")
+VARIANT = os.path.join(ROOT, "robosuite_amd", "librsim_hip_nopf.so")
+
+
+def _source_key():
+    h = hashlib.sha256()
+    for f in ("rsim_step.hip", "rsim_internal.h", "rsim_api.cpp", "Makefile", os.path.join("..", "..", "include", "rsim.h")):
+        h.update(open(os.path.join(CSRC, f), "rb").read())
+    return h.hexdigest()
+
+
+@pytest.fixture(scope="module")
+def variant():
+    """librsim_hip_nopf.so: configurations 0 (Lift) and 1 (Stack) compiled with -DRSIM_NO_CAND_PREFETCH, everything else shared with the default build.
+    Built on first use (two compilations side by side, a few minutes) and kept, keyed to the sources it was built from."""
+    key_file = VARIANT + ".key"
+    if not (os.path.exists(VARIANT) and os.path.exists(key_file) and open(key_file).read().strip() == _source_key()):
+        r = subprocess.run(["bash", os.path.join(ROOT, "tools", "build_variant_flags.sh"), "nopf", "-DRSIM_NO_CAND_PREFETCH", "0", "1"], capture_output=True, text=True, timeout=1800)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        open(key_file, "w").write(_source_key() + "\n")
+    return VARIANT
+
+
+def _states(lib, case, tmp_path):
+    out = str(tmp_path / f"{case}_{os.path.basename(lib)}.npz")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "cand_desc_states.py"), case, out], env=dict(os.environ, RSIM_LIB=lib), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    return np.load(out)
+
+
+def _assert_bitwise(a, b):
+    assert sorted(a.files) == sorted(b.files)
+    for k in a.files:
+        assert a[k].dtype == b[k].dtype and a[k].shape == b[k].shape and a[k].tobytes() == b[k].tobytes(), k
+
+
+@pytest.mark.gpu
+def test_over_capacity_stack_steps_to_the_same_bits_without_the_prefetch(variant, tmp_path):
+    """Sixteen Stack envs whose control step outgrows the native body (tests/golden/stack_over_capacity.npz): three control steps, in which the native body and
+    the fused wide body both run their narrow phase.  States, warm starts, controller records, the last substep's contacts and constraint forces, contact / row /
+    iteration counts and the capacity demand: all bitwise equal between the two builds."""
+    a, b = _states(LIB, "stack_over", tmp_path), _states(variant, "stack_over", tmp_path)
+    n = len(a["qpos_0"])
+    assert a["tier_steps"][0] >= n and a["tier_steps"][1] >= n, a["tier_steps"]      # every env was handed over to the wide body in mid-step
+    assert (a["ncon_0"] > 0).all() and int(a["diverged_2"].sum()) == 0 and int(a["overflow_2"].sum()) == 0
+    _assert_bitwise(a, b)
+
+
+@pytest.mark.gpu
+def test_mixed_priorities_and_solmix_step_to_the_same_bits_without_the_prefetch(variant, tmp_path):
+    """The same states with per-geom contact parameters that send the pairs through every branch of the mixing rules (tools/cand_desc_states.py
+    mix_contact_parameters): unequal priorities (one side's parameters), equal priorities with two positive, two zero and one zero solmix weight, standard and
+    direct solref.  Here the lanes of the prefetch take DIFFERENT branches of contact_params() side by side, the per-candidate path takes them one at a time."""
+    a, b = _states(LIB, "stack_mixed", tmp_path), _states(variant, "stack_mixed", tmp_path)
+    plain = _states(LIB, "stack_over", tmp_path)
+    assert (a["ncon_0"] > 0).all()
+    assert not np.array_equal(a["qpos_0"], plain["qpos_0"])       # the mixed parameters reach the contacts
+    _assert_bitwise(a, b)
+
+
+@pytest.mark.gpu
+def test_lift_steps_to_the_same_bits_without_the_prefetch(variant, tmp_path):
+    """Configuration 0 (the bench workload's kernel): eight envs from states along the recorded Lift trajectory, six control steps."""
+    a, b = _states(LIB, "lift", tmp_path), _states(variant, "lift", tmp_path)
+    assert int(a["diverged_5"].sum()) == 0 and all(np.isfinite(a[k]).all() for k in a.files if a[k].dtype.kind == "f")
+    _assert_bitwise(a, b)
+
+
+@pytest.mark.gpu
+def test_more_candidates_than_lanes_step_to_the_same_bits_without_the_prefetch(variant, tmp_path):
+    """More than 64 simultaneous candidates (tools/cand_desc_states.py crowd_xml: two free clusters of convex geoms and a static one within each other's
+    margins, 96 pairs): the default build takes candidates 0 .. 63 from the prefetched descriptors and 64 .. from the per-candidate path
+    in the same substep, the other build takes all of them from the latter.  Forty substeps, compared every ten."""
+    a, b = _states(LIB, "crowd", tmp_path), _states(variant, "crowd", tmp_path)
+    assert a["cand_per_env_substep_0"][0] > 64 and a["mpr_per_env_substep_0"][0] > 0, (a["cand_per_env_substep_0"], a["mpr_per_env_substep_0"])   # mean of the first ten substeps
+    assert (a["ncon_0"] > 0).all() and all(np.isfinite(a[k]).all() for k in a.files if a[k].dtype.kind == "f")
+    _assert_bitwise(a, b)
