@@ -213,7 +213,12 @@ enum rsim_field {
                         *               5 direction was no descent direction, 6 a step raised the objective; 0 not run) */
   RSIM_XFRC_APPLIED,   /* [B,nbody,6]  mjData.xfrc_applied: a Cartesian wrench per body -- force (3) then torque (3), world coordinates, applied at the body's COM
                         *               (xipos).  Added as J^T wrench to the smooth forces (mj_xfrcAccumulate) and to the body's cfrc_ext for the <force> / <torque>
-                        *               sensors (mj_rnePostConstraint) wherever RSIM_QFRC_APPLIED is honoured, under the same switch; zeroed like it */
+                        *               sensors (mj_rnePostConstraint) wherever RSIM_QFRC_APPLIED is honoured, under the same switch; zeroed like it */ RSIM_END_REASON,
+                       /* RSIM_END_REASON (the last field, = RSIM_XFRC_APPLIED + 1: appended, no existing value moves; on RSIM_XFRC_APPLIED's line because
+                        *               tests/test_applied_forces_host.py pins that entry as the last one that starts a line) [B] int32: why the launch that reported RSIM_DONE ended the env's
+                        *               episode -- 0 running, 1 horizon, 2 success, 3 bad-state guard, 4 requested.  Maintained by every control step while a rule of
+                        *               rsim_set_early_end is armed and written (4) by rsim_end_episodes; with no rule armed the control step does not maintain it
+                        *               (RSIM_DONE alone says "horizon") and it reads 0 after rsim_set_early_end(b, 0, ..) / rsim_reset */
   RSIM_FIELD_COUNT
 };
 #define RSIM_PATCH_TASK_OBJECT (-1)   /* rsim_set_reset_bank patch index: this column of a reset row is the episode's RSIM_TASK_OBJECT, not a float-table entry */
@@ -335,6 +340,22 @@ int rsim_set_schedule(rsim_batch* b, int longest_first);
  * switch on, rsim_step2_last always -- the on-device episode restart zeroes both arrays of an env in the launch that reports its RSIM_DONE (mj_resetData, as
  * rsim_reset does), so a wrench written after that applies to the new episode; with the switch off the control step leaves them as they are. */
 int rsim_set_applied_forces(rsim_batch* b, int enable);
+/* Ending episodes before the horizon (the reference has no counterpart: MujocoEnv.step ends an episode at the horizon only, base.py:532-548; success and
+ * divergence checks live in wrappers and training loops around it).  OFF BY DEFAULT: an unarmed batch launches nothing extra and computes what it always did.
+ * Both entries need a reset bank (rsim_set_reset_bank) and fail without one: an episode that ends restarts, in the same call, from the env's next pre-drawn
+ * reset -- exactly what the horizon does (see above: ring slot, patches, RSIM_TERMINAL_OBS, reset observation in RSIM_OBS, RSIM_DONE = 1, fresh controller
+ * at the next step); RSIM_REWARD / RSIM_SUCCESS keep the terminal step's values.
+ *   rsim_set_early_end  rules: bit 0 = end on success (RSIM_SUCCESS != 0 once the episode step counter, counted like `horizon`, is >= min_steps; min_steps >= 1),
+ *                       bit 1 = end when the bad-state guard fired during the step (RSIM_DIVERGED grew: the env restarts from a drawn reset instead of carrying
+ *                       on from qpos0 inside the same episode); 0 disarms.  While armed, every rsim_control_step / rsim_step2_last is followed on its stream(s) by
+ *                       one small kernel (k_end_episodes) that decides per env, first match: 1 the step itself ended the episode at the horizon (never restarted
+ *                       twice), 2 success, 3 diverged -- and writes RSIM_END_REASON for every env.  Guard hits from before the call (or before rsim_reset) do not count.
+ *   rsim_end_episodes   ends NOW the running episode of every env with mask_dev[env] != 0 (DEVICE uint8 [B]), outside a control step: restart from the ring +
+ *                       reset observation, RSIM_DONE = 1 and RSIM_END_REASON = 4 for those envs, every other env untouched (their RSIM_DONE included).  The reset
+ *                       observation is taken as rsim_observe takes it after a host reset, for the ended envs only: an env ended here is bit for bit the env a host
+ *                       reset of its next episode builds.  Consumes a ring slot per ended env: refill before the ring runs dry (RSIM_BANK_STALE counts a miss). */
+int rsim_set_early_end(rsim_batch* b, int rules, int min_steps);
+int rsim_end_episodes(rsim_batch* b, const uint8_t* mask_dev);
 /* Stream groups of rsim_control_step (no reference counterpart; results do not depend on it).  A control step lasts as long as its slowest env
  * (contact-rich envs take 3-4 x the median) and the envs are independent, so with groups = G > 1 the batch is stepped as G contiguous env
  * blocks, each on its own HIP stream: block g's step t + 1 starts as soon as ITS envs have finished step t, filling the CUs that the other

@@ -21,8 +21,11 @@ FIELDS = ["qpos", "qvel", "qacc_warmstart", "ctrl", "time", "cstate", "xpos", "x
           "qfrc_constraint", "qacc", "cdof", "rootcom", "contact", "efc_force", "ncon", "nefc", "niter", "obs", "reward", "success", "done", "ep_step",
           "ep_index", "diverged", "overflow", "bank_stale", "terminal_obs", "sensordata", "task_object", "cap_need", "qfrc_applied", "polish",
           "xfrc_applied"]
-FIELD_ID = {n: i for i, n in enumerate(FIELDS)}
-INT_FIELDS = {"polish", "ncon", "nefc", "niter", "success", "done", "ep_step", "ep_index", "diverged", "overflow", "bank_stale", "task_object", "cap_need"}
+# fields appended to enum rsim_field behind RSIM_XFRC_APPLIED (include/rsim.h): "end_reason" -- why an env's episode ended (early episode end, off by default)
+EXTRA_FIELDS = ["end_reason"]
+FIELD_ID = {n: i for i, n in enumerate(FIELDS + EXTRA_FIELDS)}
+END_REASONS = {"running": 0, "horizon": 1, "success": 2, "diverged": 3, "requested": 4}     # values of RSIM_END_REASON
+INT_FIELDS = {"end_reason", "polish", "ncon", "nefc", "niter", "success", "done", "ep_step", "ep_index", "diverged", "overflow", "bank_stale", "task_object", "cap_need"}
 CON_REC = 24
 CSTATE = 32
 OBS_MAX = 128
@@ -246,6 +249,9 @@ def lib():
         L.rsim_set_schedule.argtypes = [vp, C.c_int]
         L.rsim_set_applied_forces.argtypes = [vp, C.c_int]
         L.rsim_set_stream_groups.argtypes = [vp, C.c_int]
+        if hasattr(L, "rsim_set_early_end"):       # (absent from a build of an earlier round named by RSIM_LIB for an A/B)
+            L.rsim_set_early_end.argtypes = [vp, C.c_int, C.c_int]
+            L.rsim_end_episodes.argtypes = [vp, vp]
         L.rsim_group_stream.restype = vp; L.rsim_group_stream.argtypes = [vp, C.c_int]
         L.rsim_profile_env.argtypes = [vp, C.c_int]
         L.rsim_tier_snapshot.argtypes = [vp, vp]
@@ -442,7 +448,7 @@ class HipBatch:
                        "contact": (B, self.maxcon, CON_REC), "efc_force": (B, self.maxefc), "ncon": (B,), "nefc": (B,), "niter": (B,),
                        "obs": (B, model.nobs), "reward": (B,), "success": (B,), "done": (B,), "ep_step": (B,), "ep_index": (B,), "diverged": (B,), "overflow": (B,), "bank_stale": (B,), "terminal_obs": (B, model.nobs),
                        "sensordata": (B, int(m.arrays["sensor_dim"].sum()) if getattr(m, "nsensor", 0) else 0), "task_object": (B,), "cap_need": (B, 2), "qfrc_applied": (B, m.nv), "polish": (B,),
-                       "xfrc_applied": (B, nb, 6)}
+                       "xfrc_applied": (B, nb, 6), "end_reason": (B,)}
 
     # ---- state access (host copies) --------------------------------------------------------
     def get(self, name):
@@ -644,6 +650,35 @@ class HipBatch:
         """External forces in control_step (include/rsim.h rsim_set_applied_forces): every substep adds qfrc_applied + J^T xfrc_applied to the smooth
         forces, and an on-device episode restart zeroes both arrays of the env.  Off by default; the debug entries honour both arrays either way."""
         _chk(self._L.rsim_set_applied_forces(self.ptr, int(bool(enable))))
+
+    def set_early_end(self, success=False, diverged=False, min_steps=1):
+        """End episodes before the horizon (include/rsim.h rsim_set_early_end): on task success (from episode step `min_steps` on) and / or when the
+        bad-state guard fired during the step.  An ended env restarts from its next pre-drawn reset exactly as at the horizon and reports `done`;
+        `end_reason` says why (END_REASONS).  Needs a reset bank.  Off by default; both False disarms (nothing extra is launched)."""
+        _chk(self._L.rsim_set_early_end(self.ptr, (1 if success else 0) | (2 if diverged else 0), int(min_steps)))
+
+    def end_episodes(self, mask):
+        """End now, outside a control step, the episode of every env whose entry of `mask` (torch CUDA bool / uint8 tensor [B]) is set (include/rsim.h
+        rsim_end_episodes): restart from the ring + reset observation, done = 1 and end_reason = 4 for those envs, every other env untouched."""
+        import torch
+
+        if not isinstance(mask, torch.Tensor) or not mask.is_cuda or tuple(mask.shape) != (self.B,):
+            raise RsimError(f"end_episodes: mask must be a CUDA tensor of shape ({self.B},)")
+        m8 = (mask != 0).to(torch.uint8).contiguous()
+        # the mask is usually computed on torch's current stream and is read on the batch's: the batch's stream waits for the producer, and the tensor is
+        # kept until the kernel that reads it has run
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(m8.device))
+        self._mask_stream().wait_event(ev)
+        _chk(self._L.rsim_end_episodes(self.ptr, C.c_void_p(m8.data_ptr())))
+        self.sync()
+
+    def _mask_stream(self):
+        import torch
+
+        if getattr(self, "_main_ext", None) is None:
+            self._main_ext = torch.cuda.ExternalStream(self.stream(), device=f"cuda:{self.device}")
+        return self._main_ext
 
     def set_schedule(self, longest_first=True):
         """Dispatch order of control_step: slowest envs of the previous step first (default) or identity."""

@@ -420,3 +420,12 @@ class HostControlledEnv:
         self._restarted = b.tensor("done").to(torch.bool).clone()
         self.task._bank_tick()
         return self.task.obs(), self.task.reward(), b.tensor("done"), {"success": self.task.success()}
+
+    def end_episodes(self, mask):
+        """End now the episode of the envs flagged in `mask` (CUDA tensor [B]; rsim_end_episodes): they restart on the device and report `done`, so the
+        next step gives them fresh controllers like envs restarted at the horizon (whose `done` of the last step still stands).  Returns the observations."""
+        import torch
+
+        self.task.end_episodes(mask)
+        self._restarted = self.batch.tensor("done").to(torch.bool).clone()
+        return self.task.obs()

@@ -76,6 +76,7 @@ static const limits_fn k_limits[RSIM_NCFG_ALL] = {rsim_limits_cfg0, rsim_limits_
 extern "C" int rsim_launch_order(const unsigned* cost, int* order, int B, hipStream_t stream);
 extern "C" int rsim_launch_bank_scatter(float* bank, int* tag, const int* env, const int* episode, const float* rows, int n, int E, int W, hipStream_t stream);
 extern "C" int rsim_launch_randomize(const DModel* m, const DBatch* b, const DDr* d, unsigned long long seed, unsigned long long step, hipStream_t stream);
+#include "rsim_episode.h"
 
 struct rsim_model;
 static int param_offset_impl(const rsim_model* m, const char* field, int elem);
@@ -192,6 +193,12 @@ struct rsim_batch {
   long nstep;         // one-launch control steps issued since the schedule was (re)started
   int schedule;       // 1 = reorder before every control step (default), 0 = identity order
   int applied;        // rsim_set_applied_forces: control steps add qfrc_applied + J^T xfrc_applied (RF_APPLIED)
+  // early episode end (rsim_set_early_end, rsim_episode.hip): off unless armed -- an unarmed batch launches nothing extra
+  int early_rules, early_min_steps;
+  int* d_end_reason;     // [B] RSIM_END_REASON
+  int* d_seen_diverged;  // [B] RSIM_DIVERGED as of the last k_end_episodes launch (allocated when a rule is first armed)
+  int* d_end_sel;        // [B] envs the last rsim_end_episodes restarted (allocated on first use)
+  int ended_outside;     // rsim_end_episodes left needs_reset flags for the next rsim_control_step (fresh controllers); rsim_step2_last, which runs no in-kernel controller, drops them first
   // stream groups: control steps of env block g run on gstream[g]; `forked` = the group streams hold work the main stream has not waited for
   int groups, ngroups, forked;   // streams created, groups in use (1 = everything on the main stream)
   hipStream_t gstream[RSIM_MAX_GROUPS];
@@ -954,7 +961,8 @@ extern "C" int rsim_batch_create(rsim_model* m, int B, int device, int per_env, 
       {RSIM_BANK_STALE, (void**)&db.bank_stale, (size_t)B, 1}, {RSIM_TERMINAL_OBS, (void**)&db.term_obs, (size_t)B * (m->has_task ? m->task.nobs : 0), 0},
       {RSIM_SENSORDATA, (void**)&db.sensordata, (size_t)B * m->nsensordata, 0}, {RSIM_TASK_OBJECT, (void**)&db.task_object, (size_t)B, 1},
       {RSIM_CAP_NEED, (void**)&db.cap_need, (size_t)B * 2, 1}, {RSIM_QFRC_APPLIED, (void**)&db.qfrc_applied, (size_t)B * nv, 0},
-      {RSIM_POLISH, (void**)&db.polish, (size_t)B, 1}, {RSIM_XFRC_APPLIED, (void**)&db.xfrc_applied, (size_t)B * nb * 6, 0}};
+      {RSIM_POLISH, (void**)&db.polish, (size_t)B, 1}, {RSIM_XFRC_APPLIED, (void**)&db.xfrc_applied, (size_t)B * nb * 6, 0},
+      {RSIM_END_REASON, (void**)&b->d_end_reason, (size_t)B, 1}};
   for (auto& fd : fields) {
     if (dalloc((float**)fd.p, fd.n)) return 1;
     b->fptr[fd.id] = *fd.p; b->fcount[fd.id] = fd.n; b->fis_int[fd.id] = fd.is_int;
@@ -982,6 +990,8 @@ extern "C" void rsim_batch_free(rsim_batch* b) {
     hipFree(b->d_wcount);
     for (int k = 0; k < 2; k++) hipFree(b->d_wlist[k]);
   }
+  if (b->d_seen_diverged) hipFree(b->d_seen_diverged);
+  if (b->d_end_sel) hipFree(b->d_end_sel);
   if (b->db.mprc) hipFree(b->db.mprc);
   if (b->db.jg) hipFree(b->db.jg);
   if (b->db.bpl) hipFree(b->db.bpl);
@@ -1024,6 +1034,7 @@ extern "C" int rsim_reset(rsim_batch* b, const uint8_t* mask) { if (join_groups(
     HIPCHK(hipMemset(b->db.cstate, 0, (size_t)B * b->cs * sizeof(float)));
     HIPCHK(hipMemset(b->db.ep_step, 0, (size_t)B * sizeof(int))); HIPCHK(hipMemset(b->db.ep_index, 0, (size_t)B * sizeof(int)));
     HIPCHK(hipMemset(b->db.done, 0, (size_t)B * sizeof(int))); HIPCHK(hipMemset(b->db.needs_reset, 0, (size_t)B * sizeof(int)));
+    HIPCHK(hipMemset(b->d_end_reason, 0, (size_t)B * sizeof(int)));
   } else {
     for (int e = 0; e < B; e++) {
       if (!mask[e]) continue;
@@ -1036,9 +1047,11 @@ extern "C" int rsim_reset(rsim_batch* b, const uint8_t* mask) { if (join_groups(
       HIPCHK(hipMemset(b->db.time + e, 0, sizeof(float)));
       HIPCHK(hipMemset(b->db.cstate + (size_t)e * b->cs, 0, b->cs * sizeof(float)));
       HIPCHK(hipMemset(b->db.ep_step + e, 0, sizeof(int))); HIPCHK(hipMemset(b->db.done + e, 0, sizeof(int))); HIPCHK(hipMemset(b->db.needs_reset + e, 0, sizeof(int)));
+      HIPCHK(hipMemset(b->d_end_reason + e, 0, sizeof(int)));
     }
   }
   if (b->db.mprc) HIPCHK(hipMemset(b->db.mprc, 0, (size_t)B * m->npair * 12 * sizeof(float)));   // no warm start carried into a reset state (bitwise replays)
+  if (b->d_seen_diverged) HIPCHK(hipMemcpy(b->d_seen_diverged, b->db.diverged, (size_t)B * sizeof(int), hipMemcpyDeviceToDevice));   // the divergence rule fires on guard hits after the reset only
   b->gen++;
   return 0;
 }
@@ -1153,6 +1166,26 @@ static void tr_mark(rsim_batch* b, int point) {
   }
 }
 
+// k_end_episodes (rsim_episode.hip) over envs [env0, env0 + nenv) on `stream`: after every pass of a control step has committed, before the k_prepare(reset_only) /
+// k_reset_obs launches that finish a restart.  standalone: rsim_end_episodes, outside a control step.  `applied`: the launch that follows reads the applied forces.
+static int end_episodes_launch(rsim_batch* b, int env0, int nenv, const unsigned char* mask, int standalone, int applied, hipStream_t stream) {
+  const rsim_model* m = b->m; const DBatch& d = b->db;
+  DEndEpisodes a;
+  memset(&a, 0, sizeof(a));
+  a.env0 = env0; a.nenv = nenv;
+  a.nq = m->nq; a.nv = m->nv; a.nu = m->nu; a.nbody = m->nbody; a.nobs = b->dm.task.enabled ? b->dm.task.nobs : 0; a.npair = b->dm.npair; a.fstride = b->dm.fstride;
+  a.bank_E = d.bank_E; a.bank_P = d.bank_P;
+  a.rules = standalone ? 0 : b->early_rules; a.min_steps = b->early_min_steps; a.standalone = standalone; a.applied = applied;
+  a.success = d.success; a.diverged = d.diverged; a.mask = mask; a.seen_diverged = b->d_seen_diverged; a.end_reason = b->d_end_reason; a.sel = standalone ? b->d_end_sel : nullptr;
+  a.done = d.done; a.ep_step = d.ep_step; a.ep_index = d.ep_index; a.needs_reset = d.needs_reset; a.bank_stale = d.bank_stale; a.task_object = d.task_object;
+  a.bank = d.bank; a.bank_tag = d.bank_tag; a.patch_idx = d.patch_idx;
+  a.obs = d.obs; a.term_obs = a.nobs ? d.term_obs : nullptr; a.qpos = d.qpos; a.qvel = d.qvel; a.qacc_ws = d.qacc_ws; a.ctrl = d.ctrl; a.time = d.time;
+  a.ft_rw = d.ft_rw; a.ft_base = d.ft_base; a.mprc = d.mprc; a.qfrc_applied = d.qfrc_applied; a.xfrc_applied = d.xfrc_applied;
+  int e = rsim_launch_end_episodes(&a, stream);
+  if (e) return fail("episode-end kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+  return 0;
+}
+
 static inline bool sched1_trace(int flags) { return (flags & RF_EPISODE) && (flags & RF_CTRL); }
 // One wide pass of a TIER_LIST control step on `stream`: the constant blocks of the listed envs (only when envs have blocks of their own), then the step.
 // pass 1 = the envs whose tier is 1 (list built by rsim_launch_tier_list), pass 2 = the redo list the native pass appended to.
@@ -1197,6 +1230,7 @@ static int launch(rsim_batch* b, const float* actions, int n_sub, int flags) {
     if (const char* e = getenv("RSIM_FORCE_HANDOVER")) b->db.tier_pass = 100 + atoi(e);   // test hook: every native-tier env hands over to the wide body at this substep (tests/test_hip_edge_cases.py)
   }
   const bool grouped = (flags & RF_EPISODE) && (flags & RF_CTRL) && b->ngroups > 1;
+  const bool early = (flags & RF_EPISODE) && b->early_rules && b->db.bank;   // rsim_set_early_end: k_end_episodes behind the step's passes (unarmed: nothing extra is launched)
   if (!grouped || b->cm_dirty || memcmp(&b->cm_ctrl, &b->dm.ctrl, sizeof(DCtrl))) { if (join_groups(b)) return 1; }   // main-stream work ahead
   if (ensure_constants(b)) return 1;
   if ((flags & RF_OBS) && !b->dm.task.enabled) return fail("the task (observation / reward epilogue) was configured after the batch was created");
@@ -1230,7 +1264,8 @@ static int launch(rsim_batch* b, const float* actions, int n_sub, int flags) {
         if (wide_pass(b, actions, n_sub, flags, 1, b->d_wlist[0] + e0, cnt, b->gstream[g])) return 1;
         if (wide_pass(b, actions, n_sub, flags, 2, b->d_wlist[1] + e0, cnt + 1, b->gstream[g])) return 1;
       }
-      if (b->db.bank && b->db.horizon > 0) {
+      if (early && end_episodes_launch(b, e0, e1 - e0, nullptr, 0, (flags & (RF_APPLIED | RF_DEBUG)) ? 1 : 0, b->gstream[g])) return 1;
+      if (b->db.bank && (b->db.horizon > 0 || early)) {
         db.order = nullptr; db.cost = nullptr;
         if (b->db.bank_P > 0 && b->db.cm_stride) {
           e = k_prepare_launch[b->cfg](&b->dm, &db, e1 - e0, 1, b->gstream[g]);
@@ -1293,7 +1328,8 @@ static int launch(rsim_batch* b, const float* actions, int n_sub, int flags) {
   if (tiered) b->tier_flip ^= 1;
   if (traced) tr_mark(b, 5);
   if (sched1) b->nstep++;
-  if ((flags & RF_EPISODE) && b->db.bank && b->db.horizon > 0) {
+  if (early && end_episodes_launch(b, 0, b->B, nullptr, 0, (flags & (RF_APPLIED | RF_DEBUG)) ? 1 : 0, b->stream)) return 1;
+  if ((flags & RF_EPISODE) && b->db.bank && (b->db.horizon > 0 || early)) {
     if (b->db.bank_P > 0 && b->db.cm_stride) {
       // envs whose episode just ended were re-initialised from the reset bank, float-table patches included: rebuild their constant blocks
       e = k_prepare_launch[b->cfg](&b->dm, &b->db, b->B, 1, b->stream);
@@ -1341,6 +1377,7 @@ extern "C" int rsim_step(rsim_batch* b) { return launch(b, nullptr, 1, RF_POSVEL
 extern "C" int rsim_control_step(rsim_batch* b, const float* actions_dev, int n_sub) {
   if (n_sub < 1) return fail("rsim_control_step: n_sub < 1");
   if (!actions_dev) return fail("rsim_control_step: actions_dev is NULL");
+  b->ended_outside = 0;   // the step consumes the flags itself
   return launch(b, actions_dev, n_sub, RF_POSVEL | RF_CTRL | RF_SETGOAL | RF_ACTSOLVE | RF_INTEGRATE | (b->m->has_task ? RF_OBS : 0) | RF_EPISODE);
 }
 // CompositeController.run_controller() between step1 and step2 (composite_controller.py:109-116, fixed_base_robot.py:143-153): the position /
@@ -1353,6 +1390,12 @@ extern "C" int rsim_run_controller(rsim_batch* b) { return launch(b, nullptr, 1,
 // freshly restarted envs for it are cleared here; the caller learns about restarts from RSIM_DONE.
 extern "C" int rsim_step2_last(rsim_batch* b) {
   if (!b->m->has_task) return fail("rsim_step2_last: no task configured");
+  if (b->ended_outside) {   // or its reset-observation pass would take the envs rsim_end_episodes restarted for envs this step restarted
+    if (join_groups(b)) return 1;
+    HIPCHK(hipSetDevice(b->device));
+    HIPCHK(hipMemsetAsync(b->db.needs_reset, 0, (size_t)b->B * sizeof(int), b->stream));
+    b->ended_outside = 0;
+  }
   if (launch(b, nullptr, 1, RF_POSVEL | RF_ACTSOLVE | RF_INTEGRATE | RF_OBS | RF_EPISODE | RF_DEBUG)) return 1;
   HIPCHK(hipMemsetAsync(b->db.needs_reset, 0, (size_t)b->B * sizeof(int), b->stream));
   return 0;
@@ -1364,6 +1407,54 @@ extern "C" int rsim_observe(rsim_batch* b) {
 extern "C" int rsim_set_episode(rsim_batch* b, int horizon) {
   if (horizon < 0) return fail("rsim_set_episode: horizon < 0");
   b->db.horizon = horizon;
+  return 0;
+}
+extern "C" int rsim_set_early_end(rsim_batch* b, int rules, int min_steps) {
+  if (rules < 0 || rules > 3) return fail("rsim_set_early_end: rules must be a combination of bit 0 (success) and bit 1 (bad-state guard), got %d", rules);
+  if (min_steps < 1) return fail("rsim_set_early_end: min_steps < 1");
+  if (rules && !b->db.bank) return fail("rsim_set_early_end: no reset bank installed (rsim_set_reset_bank): an episode that ends restarts from a pre-drawn reset");
+  if (join_groups(b)) return 1;
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  if (rules) {
+    if (!b->d_seen_diverged && dalloc(&b->d_seen_diverged, (size_t)b->B)) return 1;
+    HIPCHK(hipMemcpy(b->d_seen_diverged, b->db.diverged, (size_t)b->B * sizeof(int), hipMemcpyDeviceToDevice));   // guard hits before the rule was armed do not end anything
+  } else if (b->early_rules) {
+    HIPCHK(hipMemset(b->d_end_reason, 0, (size_t)b->B * sizeof(int)));   // disarmed: RSIM_END_REASON is not maintained any more and reads 0
+  }
+  b->early_rules = rules; b->early_min_steps = min_steps;
+  return 0;
+}
+extern "C" int rsim_end_episodes(rsim_batch* b, const uint8_t* mask_dev) {
+  if (!mask_dev) return fail("rsim_end_episodes: mask_dev is NULL");
+  if (!b->db.bank) return fail("rsim_end_episodes: no reset bank installed (rsim_set_reset_bank): an episode that ends restarts from a pre-drawn reset");
+  if (join_groups(b)) return 1;
+  HIPCHK(hipSetDevice(b->device));
+  if (sync_controller(b)) return 1;
+  if (ensure_constants(b)) return 1;
+  // the debug entries (host-controller path) read the applied forces whatever the switch says, so a restart outside a control step always clears them -- as rsim_reset does
+  if (!b->d_end_sel && dalloc(&b->d_end_sel, (size_t)b->B)) return 1;
+  if (end_episodes_launch(b, 0, b->B, mask_dev, 1, 1, b->stream)) return 1;
+  DBatch db2 = b->db;
+  db2.needs_reset = b->d_end_sel;   // the envs restarted HERE: one restarted by the control step before keeps its record (and its flag, for that step's successor)
+  db2.order = nullptr; db2.cost = nullptr; db2.env0 = 0; db2.nenv = 0;
+  db2.tier_cur = nullptr; db2.tier_next = nullptr; db2.tier_pass = -1; db2.wlist = nullptr; db2.wcount = nullptr; db2.wlist2 = nullptr; db2.wcount2 = nullptr;
+  if (b->db.bank_P > 0 && b->db.cm_stride) {
+    int e = k_prepare_launch[b->cfg](&b->dm, &db2, b->B, 1, b->stream);
+    if (e) return fail("constant-block kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+  }
+  if (b->dm.task.enabled) {
+    // the reset observation, by the kernel and flags rsim_observe takes it with after a host reset, restricted to the restarted envs (RF_RESET_ONLY): an env
+    // ended here is then bit for bit the env a host reset of its next episode builds, record included, in every configuration.  (k_reset_obs, the pass behind
+    // a control step, is the control-step build of the same body; in the 64 x 48 configuration its solver rounds the last bits of qacc -- the joint_acc
+    // entries of the record -- unlike the debug build.)  A read: no drop / demand counters.
+    db2.overflow = nullptr; db2.cap_need = nullptr;
+    int e = k_step_launch[b->cfg](&b->dm, &db2, nullptr, 1, RF_POSVEL | RF_ACTSOLVE | RF_OBS | RF_DEBUG | RF_RESET_ONLY, b->stream);
+    if (e) return fail("reset-observation kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+  }
+  b->ended_outside = 1;
+  b->gen++;
+  b->derived_stale = 1;
   return 0;
 }
 extern "C" int rsim_param_offset(const rsim_batch* b, const char* field, int elem) {
@@ -1612,6 +1703,8 @@ extern "C" const char* rsim_tuning_defaults(void) {
                                      "RSIM_POLISH_TOL", "RSIM_POLISH_GATE", "RSIM_BP_REACH", "RSIM_NEAR_THRESH", "RSIM_NEAR_GAIN", "RSIM_MPR_CONE", "RSIM_NO_MPR_WARMSTART", "RSIM_NO_MPR_PORTAL_WARMSTART",
                                      "RSIM_TIER_UP_CON", "RSIM_TIER_UP_EFC", "RSIM_NO_TIERS", "RSIM_NO_SHARE_CM", "RSIM_EULER_FULL", "RSIM_FORCE_HANDOVER"};
   for (const char* e : envs) if (const char* v = getenv(e)) { s += ";env:"; s += e; s += "="; s += v; }
+  // (early episode end, rsim_set_early_end, is not listed: it is a per-batch switch that is off unless a caller arms it -- not a default of the library, and nothing
+  // bench.py measures runs with it; a measurement that arms it says so itself: tools/early_end_ab.py)
   return s.c_str();
 }
 // {env-steps the wider capacity tier stepped, env-steps of these that were handed over (TIER_FUSED) / redone (TIER_LIST) in mid-step} since the batch was created

@@ -524,7 +524,7 @@ def apply_host_kwargs(flat, cfg, host):
 
 
 def make(env_name, robots="Panda", n_envs=1, controller_configs=None, seed=0, horizon=1000, device=0, bank_episodes=4, stream_groups=1, env_ids=None,
-         source="auto", reference_path=None, alternating=False, **kwargs):
+         source="auto", reference_path=None, alternating=False, terminate_on_success=False, terminate_on_diverged=False, min_episode_steps=1, **kwargs):
     """Batched counterpart of `robosuite.make(env_name, robots=..., controller_configs=..., **kwargs)` (environments/base.py:23-42): a
     `vec_env.VecEnv` of `n_envs` environments on `cuda:device`, env i seeded by `seed + i`.
 
@@ -542,7 +542,8 @@ def make(env_name, robots="Panda", n_envs=1, controller_configs=None, seed=0, ho
     source: "assets" = only the shipped BASELINE configurations (with host-side kwargs patched into their cfg); "reference" = always construct the
     reference's env class and read the model and the configuration off it; "auto" (default) = shipped assets when (env_name, robots, controller
     type, model kwargs) name one of them, the reference otherwise.
-    alternating=True: a `vec_env.AlternatingVecEnv` (two half-batches stepped alternately: closed-loop compatible, fills the drain of a lockstep launch)."""
+    alternating=True: a `vec_env.AlternatingVecEnv` (two half-batches stepped alternately: closed-loop compatible, fills the drain of a lockstep launch).
+    terminate_on_success / terminate_on_diverged / min_episode_steps: end episodes before the horizon, on the device (`vec_env.VecEnv`; off by default)."""
     from .vec_env import AlternatingVecEnv, VecEnv
 
     if not isinstance(robots, str):
@@ -569,9 +570,10 @@ def make(env_name, robots="Panda", n_envs=1, controller_configs=None, seed=0, ho
         # the reference constructor sees every kwarg (an unknown one raises TypeError there, as in suite.make); extract() reads the result
         ref_kw = {**RENDER_OFF, **{k: v for k, v in kwargs.items() if k not in RENDER_OFF}, "horizon": horizon}
         flat, cfg = from_reference(env_name, robots, controller_configs, seed=seed, reference_path=reference_path, defaults={}, **ref_kw)
+    early = dict(terminate_on_success=terminate_on_success, terminate_on_diverged=terminate_on_diverged, min_episode_steps=min_episode_steps)
     if alternating:
-        return AlternatingVecEnv(env_name, n_envs, flat, cfg, device=device, seed=seed, horizon=horizon, env_ids=env_ids, bank_episodes=bank_episodes)
-    return VecEnv(env_name, n_envs, flat, cfg, device=device, seed=seed, horizon=horizon, env_ids=env_ids, bank_episodes=bank_episodes, stream_groups=stream_groups)
+        return AlternatingVecEnv(env_name, n_envs, flat, cfg, device=device, seed=seed, horizon=horizon, env_ids=env_ids, bank_episodes=bank_episodes, **early)
+    return VecEnv(env_name, n_envs, flat, cfg, device=device, seed=seed, horizon=horizon, env_ids=env_ids, bank_episodes=bank_episodes, stream_groups=stream_groups, **early)
 
 
 def ship_assets(reference_path=None):

@@ -12,6 +12,7 @@ Pinned by tests/test_lift_host.py against fixtures recorded from the reference's
 from __future__ import annotations
 
 import functools
+import threading
 
 import numpy as np
 
@@ -37,6 +38,7 @@ def default_reset_spec():
 
 _PREPARED = {}          # id(spec) -> (spec, content key, arrays); at most _PREPARED_MAX entries, least recently used first out
 _PREPARED_MAX = 32
+_PREPARED_LOCK = threading.Lock()   # prepared() runs on the stepping thread and on every env's ring-upkeep thread (reset_bank.py); the LRU reshuffle below is not atomic
 
 
 def _spec_key(spec):
@@ -52,18 +54,19 @@ def prepared(spec):
     spec (so the id cannot be reused while it is cached), is rebuilt when the values it was built from have been edited in place, and the cache keeps the
     _PREPARED_MAX most recently used specs -- envs and specs built over and over (tests, per-reset rebuilds) no longer pin every spec for the life of the process."""
     k = id(spec)
-    hit = _PREPARED.get(k)
     key = _spec_key(spec)
-    if hit is None or hit[0] is not spec or hit[1] != key:
-        p = dict(arm=np.array(spec["arm_init_qpos"], dtype=np.float64))
-        if "cube" in spec:
-            p["size_min"], p["size_max"] = np.array(spec["cube"]["size_min"], dtype=np.float64), np.array(spec["cube"]["size_max"], dtype=np.float64)
-        hit = (spec, key, p)
-    else:
-        del _PREPARED[k]          # re-inserted below: dicts keep insertion order, the first key is the least recently used
-    _PREPARED[k] = hit
-    while len(_PREPARED) > _PREPARED_MAX:
-        del _PREPARED[next(iter(_PREPARED))]
+    with _PREPARED_LOCK:
+        hit = _PREPARED.get(k)
+        if hit is None or hit[0] is not spec or hit[1] != key:
+            p = dict(arm=np.array(spec["arm_init_qpos"], dtype=np.float64))
+            if "cube" in spec:
+                p["size_min"], p["size_max"] = np.array(spec["cube"]["size_min"], dtype=np.float64), np.array(spec["cube"]["size_max"], dtype=np.float64)
+            hit = (spec, key, p)
+        else:
+            del _PREPARED[k]          # re-inserted below: dicts keep insertion order, the first key is the least recently used
+        _PREPARED[k] = hit
+        while len(_PREPARED) > _PREPARED_MAX:
+            del _PREPARED[next(iter(_PREPARED))]
     return hit[2]
 
 

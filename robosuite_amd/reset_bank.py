@@ -84,6 +84,7 @@ class ResetBankMixin:
     bank_episodes = 0
     sync_bank = False          # True: refill from step() with a blocking read of the episode counters (the round-2 behaviour)
     bank_poll_steps = 0        # control steps between two polls of the episode counters (0: horizon // 4)
+    early_min_steps = 0        # > 0: an early-end rule is armed (set_early_end) and an episode may be as short as this many control steps
 
     def episode_draws(self, idx, episode: int):
         """The task's reset_draws() block `episode` for the LOCAL env indices idx, from the persistent per-env generators (self._draw_fn: rng -> draw)."""
@@ -121,6 +122,27 @@ class ResetBankMixin:
                 (self.batch.refill_reset_bank_async if asynchronous else self.batch.refill_reset_bank)(idx, np.full(len(idx), e), q, p)
                 self._bank_filled[idx] = e
                 n += len(idx)
+
+    # ---- episodes that end before the horizon ------------------------------------------------------
+    def set_early_end(self, success: bool = False, diverged: bool = False, min_steps: int = 1):
+        """Arm / disarm the on-device early end (backend.HipBatch.set_early_end).  Armed, an env may consume a ring slot every `min_steps` control steps
+        instead of every `horizon`: the upkeep cadence follows (_bank_tick)."""
+        self.batch.set_early_end(success=success, diverged=diverged, min_steps=min_steps)
+        self.early_min_steps = int(min_steps) if (success or diverged) else 0
+
+    def end_episodes(self, mask):
+        """End the running episode of the envs flagged in `mask` (CUDA tensor [B]) now; the slots they consumed are refilled before this returns."""
+        self.batch.end_episodes(mask)
+        self.refill_bank()
+
+    def _bank_slack_steps(self) -> int:
+        """Control steps in which an env cannot run through the ring: the horizon -- what it always was -- unless an early-end rule lets episodes be as
+        short as early_min_steps, when E - 1 stored episodes last early_min_steps * (E - 1) steps."""
+        horizon = int(getattr(self, "horizon", 0) or 1)
+        if self.early_min_steps > 0:
+            reach = self.early_min_steps * (self.bank_episodes - 1)
+            return min(horizon, reach) if getattr(self, "horizon", 0) else reach
+        return horizon
 
     def refill_bank(self) -> int:
         """Synchronous upkeep: blocking read of the episode counters, refill, return when the rows are in the ring."""
@@ -168,6 +190,13 @@ class ResetBankMixin:
             t.join()
         self._bank_thread = None
 
+    def _bank_cadence(self):
+        """(refill synchronously from step()?, control steps between two polls of the episode counters)"""
+        horizon = self._bank_slack_steps()
+        # short episodes (tests: horizons of 2 .. 7 steps with two slots) leave an upkeep thread no slack: they refill from this thread, blocking
+        sync = self.sync_bank or horizon < 32
+        return sync, self.bank_poll_steps or max(1, horizon // (2 if sync else 4))
+
     def _bank_tick(self):
         """Called from every step(): counts steps, wakes the upkeep thread every `bank_poll_steps` control steps."""
         if not self.bank_episodes:
@@ -175,10 +204,7 @@ class ResetBankMixin:
         t0 = time.perf_counter()
         self._bank_steps += 1
         self._bank_stat["steps"] += 1
-        horizon = int(getattr(self, "horizon", 0) or 1)
-        # short episodes (tests: horizons of 2 .. 7 steps with two slots) leave an upkeep thread no slack: they refill from this thread, blocking
-        sync = self.sync_bank or horizon < 32
-        every = self.bank_poll_steps or max(1, horizon // (2 if sync else 4))
+        sync, every = self._bank_cadence()
         if self._bank_steps >= every:
             self._bank_steps = 0
             if sync:

@@ -9,6 +9,12 @@
 Semantics follow the reference loop (environments/base.py:277-347, 467-521): `done` is reported on the control step that reaches `horizon`,
 the env restarts on the device from its next pre-drawn reset (hard reset draws in the reference's RNG order) and the next `step` continues
 the new episode.  Everything returned aliases device memory owned by the backend.
+
+Off by default, episodes can also end before the horizon, with the same on-device restart and `done`:
+    env = VecEnv(..., terminate_on_success=True, min_episode_steps=5)    # the task's success check ends the episode (from its 5th step on)
+    env = VecEnv(..., terminate_on_diverged=True)                        # an env the bad-state guard had to reset starts a new episode from a drawn reset
+    obs = env.end_episodes(mask)                                         # the caller's own condition (CUDA bool tensor [n_envs]), between two steps
+info["end_reason"] (int32: 0 running, 1 horizon, 2 success, 3 diverged, 4 requested) then says why an env reported `done`.
 """
 from __future__ import annotations
 
@@ -24,7 +30,8 @@ TASKS["PickPlaceSingle"] = pick_place.PickPlaceBatch     # single_object_mode = 
 
 
 class VecEnv:
-    def __init__(self, env_name: str, n_envs: int, flat, cfg, device: int = 0, seed: int = 0, horizon: int = 500, env_ids=None, bank_episodes: int = 4, stream_groups: int = 1):
+    def __init__(self, env_name: str, n_envs: int, flat, cfg, device: int = 0, seed: int = 0, horizon: int = 500, env_ids=None, bank_episodes: int = 4, stream_groups: int = 1,
+                 terminate_on_success: bool = False, terminate_on_diverged: bool = False, min_episode_steps: int = 1):
         if env_name not in TASKS:
             raise ValueError(f"{env_name!r} has no on-device task epilogue (have {sorted(TASKS)})")
         ids = np.arange(n_envs) if env_ids is None else np.asarray(env_ids)
@@ -43,6 +50,13 @@ class VecEnv:
         if stream_groups > 1:   # env blocks stepped on their own HIP streams (rsim_set_stream_groups): same results, no whole-batch tail per step
             self.env.batch.set_stream_groups(min(int(stream_groups), self.n_envs))
         self.action_dim, self.obs_dim = self.env.model.action_dim, self.env.model.nobs
+        # early episode end (include/rsim.h rsim_set_early_end): nothing is armed, launched or reported unless asked for
+        self._early = (bool(terminate_on_success), bool(terminate_on_diverged), int(min_episode_steps))
+        self.early_end_armed, self._ended_on_request = self._early[0] or self._early[1], False
+        if self.early_end_armed:
+            if not bank_episodes:
+                raise ValueError("terminate_on_success / terminate_on_diverged need the reset ring (bank_episodes >= 2): an episode that ends restarts from a pre-drawn reset")
+            self.env.set_early_end(*self._early)
         keys, dims = cfg["obs_keys"], cfg["obs_dims"]
         off = np.cumsum([0] + list(dims))
         self.obs_slices = {k: slice(int(off[i]), int(off[i + 1])) for i, k in enumerate(keys)}
@@ -66,14 +80,37 @@ class VecEnv:
         b.set("ep_step", 0); b.set("ep_index", 0); b.set("done", 0)
         if self.bank_episodes:
             e.install_reset_bank(self.bank_episodes)
+        if self.early_end_armed or self._ended_on_request:
+            b.set("end_reason", 0)
+        if self.early_end_armed:
+            e.set_early_end(*self._early)      # re-armed: guard hits of the episodes before the reset end nothing
         b.observe()
         return e.obs()
 
     def step(self, actions):
         self.env.step(actions)
+        return self.env.obs(), self.env.reward(), self.env.batch.tensor("done"), self._info()
+
+    def _info(self):
         # gym auto-reset convention: for an env whose episode just ended, `obs` is already the reset observation of its next episode and the
         # last record of the finished one is in info["terminal_obs"] (rows of envs that did not finish are stale)
-        return self.env.obs(), self.env.reward(), self.env.batch.tensor("done"), {"success": self.env.success(), "terminal_obs": self.env.batch.tensor("terminal_obs")}
+        info = {"success": self.env.success(), "terminal_obs": self.env.batch.tensor("terminal_obs")}
+        if self.early_end_armed:
+            info["end_reason"] = self.env.batch.tensor("end_reason")
+        elif self._ended_on_request:           # no rule armed: the control step maintains `done` alone, and `done` then means the horizon
+            info["end_reason"] = self.env.batch.tensor("done").clone()
+        return info
+
+    def end_episodes(self, mask):
+        """End now the running episode of every env flagged in `mask` (CUDA bool / uint8 tensor [n_envs]) -- the caller's own termination condition,
+        evaluated between two steps.  Those envs restart on the device from their next pre-drawn reset, exactly as at the horizon; the returned
+        observation tensor holds their reset observation (their last record moves to info["terminal_obs"] of the next step's info, `done` reads 1 and
+        `end_reason` 4 until their next step); every other env is untouched.  Needs the reset ring (bank_episodes >= 2)."""
+        if not self.bank_episodes:
+            raise ValueError("end_episodes needs the reset ring (bank_episodes >= 2)")
+        self.env.end_episodes(mask)
+        self._ended_on_request = True
+        return self.env.obs()
 
     def enable_applied_forces(self, on: bool = True):
         """Honour `qfrc_applied` and `xfrc_applied` in `step` (off by default: the control step then reads neither).  An env that reports `done`
@@ -113,6 +150,12 @@ class VecEnv:
 
         keys = self._object_keys + self._proprio_keys if keys is None else keys
         return torch.cat([obs[:, self.obs_slices[k]] for k in keys], dim=1)
+
+
+def gym_flags(end_reason):
+    """(terminated, truncated) of gymnasium for RSIM_END_REASON values: success (2) and a requested end (4) terminate, the horizon (1) and the bad-state
+    guard (3) truncate.  Works on torch tensors and numpy arrays."""
+    return (end_reason == 2) | (end_reason == 4), (end_reason == 1) | (end_reason == 3)
 
 
 def body_wrench_id(model, body_name: str) -> int:
@@ -158,7 +201,12 @@ class AlternatingVecEnv:
         """Block until half k's last enqueued step has completed; (obs, reward, done, info) of that step, device tensors."""
         e = self.halves[k]
         e.env.batch.sync()
-        return e.env.obs(), e.env.reward(), e.env.batch.tensor("done"), {"success": e.env.success(), "terminal_obs": e.env.batch.tensor("terminal_obs")}
+        return e.env.obs(), e.env.reward(), e.env.batch.tensor("done"), e._info()
+
+    def end_episodes(self, mask):
+        """VecEnv.end_episodes over both halves (mask: [n_envs], half 0's envs first); returns [obs of half 0, obs of half 1]."""
+        h = self.halves[0].n_envs
+        return [self.halves[0].end_episodes(mask[:h]), self.halves[1].end_episodes(mask[h:])]
 
 
 class _Box:
@@ -180,7 +228,9 @@ def _box(low, high, shape):
 class GymVecEnv:
     """gymnasium.vector-shaped face of VecEnv, with the conventions of the reference's single-env GymWrapper (wrappers/gym_wrapper.py:45-163):
     flattened observation = the chosen keys concatenated (default `object-state` then `robot0_proprio-state`), reward range (0, reward_scale),
-    the horizon reports `terminated` (the reference passes its `done` there) and `truncated` is always False.  Episodes restart on the device:
+    the horizon reports `terminated` (the reference passes its `done` there) and `truncated` is always False.  With an early-end rule armed on the VecEnv
+    gymnasium's distinction applies instead: `terminated` = the task ended the episode (success, or the caller's request),
+    `truncated` = it was cut short (horizon, bad-state guard).  Episodes restart on the device:
     after a terminated step `obs` is already the reset observation (gymnasium's autoreset) and info["final_observation"] holds the last record of
     the finished episode for the envs flagged in info["_final_observation"]."""
 
@@ -203,9 +253,15 @@ class GymVecEnv:
         import torch
 
         obs, reward, done, info = self.env.step(actions)
-        term = done.to(torch.bool)
-        return (self.env.flat_obs(obs, self.keys), reward, term, torch.zeros_like(term),
-                {"success": info["success"], "final_observation": self.env.flat_obs(info["terminal_obs"], self.keys), "_final_observation": term})
+        ended = done.to(torch.bool)
+        if getattr(self.env, "early_end_armed", False):
+            term, trunc = gym_flags(info["end_reason"])
+        else:                                    # as ever: the horizon is passed on as `terminated`
+            term, trunc = ended, torch.zeros_like(ended)
+        out = {"success": info["success"], "final_observation": self.env.flat_obs(info["terminal_obs"], self.keys), "_final_observation": ended}
+        if "end_reason" in info:
+            out["end_reason"] = info["end_reason"]
+        return self.env.flat_obs(obs, self.keys), reward, term, trunc, out
 
     def close(self):
         pass
