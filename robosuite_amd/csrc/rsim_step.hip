@@ -2160,7 +2160,8 @@ struct Sim {
   // are those of the same facet of the Minkowski difference, the contact POINT is a barycentric blend over a possibly different triangle of that
   // facet (it slides by rounding-level amounts along the contact face; bounds in tests/test_hip_edge_cases.py).  RSIM_NO_MPR_PORTAL_WARMSTART=1
   // (read when the batch is created) keeps only the exact separating-direction part.
-  static constexpr int MPRC = 12;   // floats per candidate pair in DBatch.mprc: (d1 | separating direction, flag) (d2, -) (d3, -)
+  static constexpr float MPR_TOUCH_DEPTH = 1e-5f;   // m: a contact at least this deep at a pair's previous visit skips the primitive pretest (convex_convex)
+  static constexpr int MPRC = 12;   // floats per candidate pair in DBatch.mprc: (d1 | separating direction | depth, flag) (d2, -) (d3, -); flag 0 nothing known, 1 separating direction, 2 portal directions, 3 portal normal, 4 touched (depth)
   __device__ __forceinline__ void mpr_store(gwf wout, V3 d, float valid) const {
     if (wout && lane == 0) { typedef v4f __attribute__((address_space(1)))* gw4; *(gw4)wout = v4f{d.x, d.y, d.z, valid}; }
   }
@@ -2168,11 +2169,12 @@ struct Sim {
   // phase with the highest register pressure of the kernel); LDS operations of one lane execute in program order, so no fence is needed.
   __device__ __forceinline__ float* mpr_dirs() const { return sm.u.b.poly + 48; }   // [3][3] behind the box-box clip polygons (16 x 3 floats)
   __device__ __forceinline__ void mpr_setd(int k, V3 d) const { if (lane == 0) st3(mpr_dirs() + 3 * k, d); }
-  __device__ __forceinline__ void mpr_store_portal(gwf wout) const {
+  __device__ __forceinline__ void mpr_store_portal(gwf wout, float depth) const {
+    if (!mpr_portal) { mpr_store(wout, v3(depth, 0.f, 0.f), 4.f); return; }   // no portal warm start: the pair touched, this deep (flag 4, see the pretest)
     if (wout && lane == 0) {
       typedef v4f __attribute__((address_space(1)))* gw4;
       const float* q = mpr_dirs();
-      ((gw4)wout)[0] = v4f{q[0], q[1], q[2], mpr_portal ? 2.f : 0.f}; ((gw4)wout)[1] = v4f{q[3], q[4], q[5], 0.f}; ((gw4)wout)[2] = v4f{q[6], q[7], q[8], 0.f};
+      ((gw4)wout)[0] = v4f{q[0], q[1], q[2], 2.f}; ((gw4)wout)[1] = v4f{q[3], q[4], q[5], 0.f}; ((gw4)wout)[2] = v4f{q[6], q[7], q[8], 0.f};
     }
   }
   __device__ __forceinline__ void convex_convex(int g1, int g2, int t1, int t2, int gm1, int gm2, float margin, const CPar& cp, V3 wd, int wh, gwf wout) {
@@ -2239,10 +2241,30 @@ struct Sim {
     // scan; from the centre-to-centre direction MPR needs ~6 portal steps (12.5 support calls) to find a separating direction of such a
     // wide, flat pair.  A pair that does touch pays one extra support pair.  Same verdict as the full run for separated pairs (MPR is exact
     // there), so the contact set is unchanged.
+    // A pair whose record says it TOUCHED at its previous visit (flag 4: a contact came out of that run, wd.x is its depth) is the other kind: an arm or
+    // finger hull resting on the mount's cylinder keeps its contact for many control steps, and every one of its runs paid the pretest's frame algebra and
+    // support pair only to start cold anyway (3.6 such runs per substep in the slowest env of a Lift launch, profiles/mpr_touch_record_ab.txt).  Such a
+    // visit goes to the cold run at once: same v0, same first direction, same loops, so every contact it emits is the one the pretest-first path emits, bit
+    // for bit.  What may differ is (a) the separating direction stored in the substep such a contact breaks -- the cold run's own exit instead of the
+    // primitive's axis; it feeds only later exact separation tests (flag 1) -- and (b) near_sep, which the pretest's exit lowers and exits 1 - 4 do not: it
+    // feeds only the dispatch-order key.
+    // Only contacts deeper than MPR_TOUCH_DEPTH skip.  In the substep a contact breaks, the pretest (separated: s_p <= 0) and the cold run (contact: the
+    // origin on the inner side of a portal) are both exact, but in fp32 they can disagree when the true separation is inside their rounding, ~1e-7 m on
+    // metre-sized coordinates: a grazing contact that flickers between +-1e-6 m from substep to substep lands there every few dozen breaks, and PickPlace
+    // @8192 did within 75 control steps (obs and reward of the skipping build differed from the parent's; Lift, Stack and Peg did not).  A pair that was
+    // 1e-5 m deep a substep ago -- ten times the refinement's tolerance, a hundred times the rounding -- is not grazing: to disagree it would have to move
+    // by that much in one substep AND stop inside the 1e-7 m window.  The persistent contacts of the slowest Lift envs are deeper: the gate cost them no skip.
+    // -DRSIM_MPR_PRETEST_ALWAYS writes the flag and does not act on it (tests/test_mpr_touch_record.py holds the two builds to the same bits).
+    // (flags 2 and 3 keep no depth: a visit whose warm portal was rejected takes the pretest, as before.)
+#ifdef RSIM_MPR_PRETEST_ALWAYS
+    const bool touched = false;
+#else
+    const bool touched = wh == 4 && wd.x > MPR_TOUCH_DEPTH;
+#endif
     {
       const int t1 = uni(sg1.t), t2 = uni(sg2.t);
       const bool prim1 = t1 == G_BOX || t1 == G_CYLINDER, prim2 = t2 == G_BOX || t2 == G_CYLINDER;
-      if (prim1 || prim2) {
+      if ((prim1 || prim2) && !touched) {
         const bool first = prim1 && (!prim2 || t1 == G_BOX);   // two primitives: the box's axes
         // the primitive's frame, picked field by field (a reference selected between the two structs would put both into the private segment)
         struct { M3 R; V3 p, h; } sp;
@@ -2357,9 +2379,9 @@ struct Sim {
     {
       const int ta = uni(sg1.t), tb = uni(sg2.t);
       const bool smooth_a = ta == G_CYLINDER || ta == G_CAPSULE || ta == G_SPHERE || ta == G_ELLIPSOID, smooth_b = tb == G_CYLINDER || tb == G_CAPSULE || tb == G_SPHERE || tb == G_ELLIPSOID;
-      if (((ta == G_BOX && tb == G_MESH) || (ta == G_MESH && tb == G_BOX)) && depth < 5e-3f) mpr_store_portal(wout);
+      if (((ta == G_BOX && tb == G_MESH) || (ta == G_MESH && tb == G_BOX)) && depth < 5e-3f) mpr_store_portal(wout, depth);
       else if ((smooth_a || smooth_b) && m.mpr_cone > 0.f && norm(dir) > 0.5f) mpr_store(wout, dot(dir, v1) >= 0.f ? dir : -dir, 3.f);   // the final portal's outward normal (flag 3 above)
-      else mpr_store(wout, v3(0.f, 0.f, 0.f), 0.f);
+      else mpr_store(wout, v3(depth, 0.f, 0.f), 4.f);   // touched, this deep: the next visit may start its cold run at once (see the pretest)
     }
     V3 w1 = p11 * bw.x + p21 * bw.y + p31 * bw.z, w2 = p12 * bw.x + p22 * bw.y + p32 * bw.z;
     emit_contacts(lane == 0, 1, -depth, org + (w1 + w2) * 0.5f, n, g1, g2, cp);
