@@ -378,6 +378,9 @@ int rsim_profile_env(rsim_batch* b, int env);
  * never truncates contacts -- nconmax = 5000, models/assets/base.xml:5 -- so an env that outgrows the native contact / row capacity is stepped with more).
  * Synchronises the batch's stream.  No reference counterpart (diagnostics: which envs a lockstep launch waits for). */
 int rsim_tier_snapshot(rsim_batch* b, int* host_tier);
+/* Restart flag of every env, HOST int32 [B]: 1 = a control step (or rsim_end_episodes) re-initialised the env from its reset ring and the next rsim_control_step
+ * starts it with fresh controller objects (robots/robot.py:271), then clears the flag.  Synchronises the batch's stream.  Diagnostics. */
+int rsim_restart_flags(rsim_batch* b, int* host_flags);
 /* The host-side settings that decide what a control step dispatches and how its solver stops -- compiled-in defaults and the RSIM_* environment overrides in
  * force -- as one string (valid until the next call).  Measurement files carry its sha next to the kernel's: evidence of other settings is not this build's. */
 const char* rsim_tuning_defaults(void);

@@ -256,6 +256,8 @@ def lib():
         L.rsim_profile_env.argtypes = [vp, C.c_int]
         L.rsim_tier_snapshot.argtypes = [vp, vp]
         L.rsim_tier_stats.argtypes = [vp, vp]
+        if hasattr(L, "rsim_restart_flags"):       # (as above: an earlier build named by RSIM_LIB)
+            L.rsim_restart_flags.argtypes = [vp, vp]
         L.rsim_tuning_defaults.restype = C.c_char_p
         L.rsim_name2id.argtypes = [vp, C.c_char_p, C.c_char_p]
         L.rsim_id2name.argtypes = [vp, C.c_char_p, C.c_int]; L.rsim_id2name.restype = C.c_char_p
@@ -632,6 +634,12 @@ class HipBatch:
         """Capacity tier of every env for the next control step (int32 [B]: 0 native configuration, 1 the wider one); synchronises the batch's stream."""
         out = np.zeros(self.B, dtype=np.int32)
         _chk(self._L.rsim_tier_snapshot(self.ptr, out.ctypes.data))
+        return out
+
+    def restart_flags(self):
+        """int32 [B]: 1 for an env a launch restarted from its reset ring, until the next control step has given it fresh controllers; synchronises the stream."""
+        out = np.zeros(self.B, dtype=np.int32)
+        _chk(self._L.rsim_restart_flags(self.ptr, out.ctypes.data))
         return out
 
     def tier_stats(self):

@@ -173,6 +173,10 @@ struct rsim_batch {
   int tier;
   int lim_w[10];      // limits of the tier's wide body / configuration
   int* d_tier[2];     // [B] each: tier of every env for the current / the next control step (swapped after every step)
+  // Restarts behind a control step of a fused-tier build (configurations 0-2, limits bit 5): the workgroup that ended an env's episode rebuilds the env's constant
+  // block and takes its reset observation inside k_step (RF_RESET_INKERNEL) -- no k_prepare(reset_only) / k_reset_obs launch on the step's serial chain.
+  // RSIM_SEPARATE_RESET_PASS=1 when the batch is created keeps the two launches (the reference of tests/test_reset_pass_fused.py and of A/B runs).
+  int separate_reset;
   int tier_flip;
   // TIER_LIST only
   int share_cm;       // configuration 5 reads the NATIVE constant blocks: it differs from configuration 3 in contact / row capacity only, and the block layout
@@ -885,6 +889,7 @@ extern "C" int rsim_batch_create(rsim_model* m, int B, int device, int per_env, 
   dm.ctrl.cs_size = b->cs;
   // capacity tiers: only for controllers whose state lives in LDS for the whole launch (a step that is handed over must not have written anything);
   // RSIM_NO_TIERS: none, drops are then counted in RSIM_OVERFLOW (as before round 4)
+  { const char* e = getenv("RSIM_SEPARATE_RESET_PASS"); b->separate_reset = (e && atoi(e) != 0) ? 1 : 0; }
   b->tier = TIER_NONE;
   if (b->cs <= RSIM_CS_LDS && !getenv("RSIM_NO_TIERS") && b->cfg <= 3) {
     int lw[10];
@@ -1231,6 +1236,10 @@ static int launch(rsim_batch* b, const float* actions, int n_sub, int flags) {
   }
   const bool grouped = (flags & RF_EPISODE) && (flags & RF_CTRL) && b->ngroups > 1;
   const bool early = (flags & RF_EPISODE) && b->early_rules && b->db.bank;   // rsim_set_early_end: k_end_episodes behind the step's passes (unarmed: nothing extra is launched)
+  // the reset pass inside k_step: control steps of a fused-tier build.  With an early-end rule armed k_end_episodes restarts envs AFTER k_step, and the two
+  // launches behind it serve those as well; the debug kernels (rsim_step2_last) keep them too.
+  const bool inkernel = (b->lim[9] & 32) && !b->separate_reset && !early && (flags & RF_EPISODE) && (flags & RF_CTRL) && !(flags & RF_DEBUG);
+  if (inkernel) flags |= RF_RESET_INKERNEL;
   if (!grouped || b->cm_dirty || memcmp(&b->cm_ctrl, &b->dm.ctrl, sizeof(DCtrl))) { if (join_groups(b)) return 1; }   // main-stream work ahead
   if (ensure_constants(b)) return 1;
   if ((flags & RF_OBS) && !b->dm.task.enabled) return fail("the task (observation / reward epilogue) was configured after the batch was created");
@@ -1265,7 +1274,7 @@ static int launch(rsim_batch* b, const float* actions, int n_sub, int flags) {
         if (wide_pass(b, actions, n_sub, flags, 2, b->d_wlist[1] + e0, cnt + 1, b->gstream[g])) return 1;
       }
       if (early && end_episodes_launch(b, e0, e1 - e0, nullptr, 0, (flags & (RF_APPLIED | RF_DEBUG)) ? 1 : 0, b->gstream[g])) return 1;
-      if (b->db.bank && (b->db.horizon > 0 || early)) {
+      if (!inkernel && b->db.bank && (b->db.horizon > 0 || early)) {
         db.order = nullptr; db.cost = nullptr;
         if (b->db.bank_P > 0 && b->db.cm_stride) {
           e = k_prepare_launch[b->cfg](&b->dm, &db, e1 - e0, 1, b->gstream[g]);
@@ -1330,13 +1339,13 @@ static int launch(rsim_batch* b, const float* actions, int n_sub, int flags) {
   if (sched1) b->nstep++;
   if (early && end_episodes_launch(b, 0, b->B, nullptr, 0, (flags & (RF_APPLIED | RF_DEBUG)) ? 1 : 0, b->stream)) return 1;
   if ((flags & RF_EPISODE) && b->db.bank && (b->db.horizon > 0 || early)) {
-    if (b->db.bank_P > 0 && b->db.cm_stride) {
+    if (!inkernel && b->db.bank_P > 0 && b->db.cm_stride) {
       // envs whose episode just ended were re-initialised from the reset bank, float-table patches included: rebuild their constant blocks
       e = k_prepare_launch[b->cfg](&b->dm, &b->db, b->B, 1, b->stream);
       if (e) return fail("constant-block kernel launch failed: %s", hipGetErrorString((hipError_t)e));
     }
     if (traced) tr_mark(b, 6);
-    if (b->dm.task.enabled) {
+    if (!inkernel && b->dm.task.enabled) {
       // ... and their observation record becomes the one MujocoEnv.reset() returns (base.py:298-347): sim.forward() + observables on the reset
       // state, no reward.  The terminal record of the finished episode was moved to RSIM_TERMINAL_OBS by the control step.
       DBatch db2 = b->db;
@@ -1728,6 +1737,16 @@ extern "C" int rsim_tier_snapshot(rsim_batch* b, int* host_tier) {
   if (join_groups(b)) return 1;
   HIPCHK(hipStreamSynchronize(b->stream));
   HIPCHK(hipMemcpy(host_tier, b->d_tier[b->tier_flip], (size_t)b->B * sizeof(int), hipMemcpyDeviceToHost));
+  return 0;
+}
+// needs_reset of every env, host int32 [B]: 1 = a launch restarted the env and the next rsim_control_step gives it fresh controller objects.  Diagnostics and tests
+// (whichever pass finishes a restart -- inside k_step or the two launches behind it -- leaves the flag to that next step).
+extern "C" int rsim_restart_flags(rsim_batch* b, int* host_flags) {
+  if (!host_flags) return fail("rsim_restart_flags: null destination");
+  HIPCHK(hipSetDevice(b->device));
+  if (join_groups(b)) return 1;
+  HIPCHK(hipStreamSynchronize(b->stream));
+  HIPCHK(hipMemcpy(host_flags, b->db.needs_reset, (size_t)b->B * sizeof(int), hipMemcpyDeviceToHost));
   return 0;
 }
 

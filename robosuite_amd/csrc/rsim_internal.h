@@ -269,4 +269,5 @@ enum {
   RF_RESET_ONLY = 256,  // only the envs whose needs_reset flag is set (the reset-observation pass after a control step)
   RF_NOSTORE = 512,     // debug form only: leave the state arrays (qpos .. time, warm start, controller state) as they are -- the refresh of the derived arrays on read
   RF_APPLIED = 1024,    // control step: add qfrc_applied + J^T xfrc_applied to the smooth forces, zero both at an on-device restart (the debug form: always)
+  RF_RESET_INKERNEL = 2048,   // fused-tier kernels (configurations 0-2): the workgroup that ended an env's episode rebuilds its constant block and takes its reset observation itself (no k_prepare / k_reset_obs launch behind the step)
 };

@@ -4468,19 +4468,25 @@ struct Sim {
 // What an env carries from the native body of a fused-tier kernel (RSIM_DIMS_W) into the wide body when a substep asks for more contacts / rows than the native
 // capacity: the substep to carry on with and the per-env values that live in registers.  The state arrays (qpos, qvel, qacc, qacc_warmstart, ctrl) stay where
 // they are -- both LDS layouts keep them at the same offsets -- and nothing else of a substep is persistent before its solver / integrator ran.
-struct Handover { int sub0; float time; bool fresh_ctrl, handed; int ndiverged, need_con, need_efc; float cstate; unsigned t_launch; };
+struct Handover { int sub0; float time; bool fresh_ctrl, handed; int ndiverged, need_con, need_efc; float cstate; unsigned t_launch;
+                  bool restarted; };   // the step ended the env's episode and re-initialised it from the ring (k_step: the reset pass follows in this workgroup)
 
 // FUSED: 0 = the kernel holds this body only; 1 = native body of a fused-tier kernel (returns true, with `ho` filled, when the env has to carry on in the wide
 // body); 2 = the wide body of such a kernel (ho->sub0 > 0: carries on from the native body's LDS state at that substep; 0: an env that was on the tier already)
 template <int NB, int NJ, int NV, int NG, int NS, int NCON, int NEFC, int NPAIR, bool DBG, int FUSED = 0>
 __device__ __forceinline__ bool step_body(const DModel& m, const DBatch& b, const float* __restrict__ actions, int n_sub, int flags, int slot, Handover* ho = nullptr) {
   typedef Smem<NB, NJ, NV, NG, NS, NCON, NEFC, NPAIR> SM;
-  const int lane = threadIdx.x;
+  // the bodies of a fused-tier kernel sit in k_step's reset-pass loop: with the plain lane id everything derived from it in the prologue and the epilogue is
+  // invariant in that loop, hoisted in front of it and kept alive across the whole body (cfg 0: 247 -> 256 registers and 160 B of private segment; opaque: 250, 0 B)
+  const int lane = FUSED ? opaque_lane((int)threadIdx.x) : (int)threadIdx.x;
   // Capacity tiers (DBatch.tier_pass >= 0, rsim_api.cpp launch()): pass 0 = this configuration steps the envs whose tier is 0 and hands an env that
   // runs out of contact / row capacity to the redo list WITHOUT committing anything of the step; passes 1 / 2 = a wider configuration steps the
   // envs of a list (1: the envs that were close to the native capacity last step, 2: the redo list), `slot` = index into that list.
   // Fused-tier kernels: the native body is pass 0 without a redo list (it hands over in place), the wide body behaves as pass 2 on the env of its own slot.
-  const int tpass = (!DBG && b.tier_cur) ? (FUSED == 2 ? 2 : FUSED == 1 ? 0 : b.tier_pass) : -1;
+  // Fused-tier kernels under RF_RESET_INKERNEL: k_step calls the native body a second time, with the flags of k_reset_obs, for an env whose episode the step
+  // just ended.  That pass is no tier pass and takes no part in the dispatch order, as the launch it stands for (rsim_api.cpp launch()).
+  const bool reentry = FUSED == 1 && (flags & RF_RESET_ONLY);
+  const int tpass = (!DBG && b.tier_cur && !reentry) ? (FUSED == 2 ? 2 : FUSED == 1 ? 0 : b.tier_pass) : -1;
   const bool resume = FUSED == 2 && ho->sub0 > 0;
   if ((tpass <= 0 || FUSED) && slot >= (b.nenv ? b.nenv : b.B)) return false;
   // workgroups are dispatched in index order: handing the envs that were slowest in the previous launch to the first workgroups
@@ -4488,9 +4494,9 @@ __device__ __forceinline__ bool step_body(const DModel& m, const DBatch& b, cons
   const int env = uni((tpass > 0 && !FUSED) ? b.wlist[slot] : (b.order ? b.order[slot] : slot) + b.env0);   // scalar: every per-env base address below then lives in SGPRs
   // RF_RESET_ONLY: the pass that follows a control step and produces the observation MujocoEnv.reset() returns (forward + epilogue, no reward)
   // for the envs that step re-initialised from the reset bank; every other workgroup leaves at once
-  if ((flags & RF_RESET_ONLY) && !b.needs_reset[env]) return false;
+  if (!reentry && (flags & RF_RESET_ONLY) && !b.needs_reset[env]) return false;
   if (!FUSED && tpass == 0 && b.tier_cur[env] != 0) return false;    // stepped by the wide configuration in this control step (fused kernels: k_step picks the body)
-  const unsigned t_launch = resume ? ho->t_launch : (b.cost ? (unsigned)uni((int)(clock64() >> 6)) : 0u);   // 64-tick units, scalar
+  const unsigned t_launch = resume ? ho->t_launch : ((b.cost && !reentry) ? (unsigned)uni((int)(clock64() >> 6)) : 0u);   // 64-tick units, scalar
   const float* fp = m.ft + (size_t)env * m.fstride;
   Sim<SM> sim(m, fp, lane, b.prof, b.cm, b.cm_stride ? (const char*)b.cm_env + (size_t)env * b.cm_stride : (const char*)b.cm);
   sim.pf.acc = b.prof_env == -1 || b.prof_env == env;   // -1: every env, -2: none (undistorted wave log)
@@ -4689,9 +4695,10 @@ __device__ __forceinline__ bool step_body(const DModel& m, const DBatch& b, cons
         for (int i = lane; i < m.nbody * 6; i += 64) b.xfrc_applied[(size_t)env * m.nbody * 6 + i] = 0.f;
       }
       if (lane == 0) { b.ep_index[env] = ep; b.needs_reset[env] = 1; }
+      if constexpr (FUSED != 0) ho->restarted = true;
       SYNC();
-      // the patched float-table entries change this env's constant block: the host follows this launch with k_prepare over the envs whose
-      // needs_reset flag is set (inlining prepare_constants() here makes the compiler keep a private copy of DModel)
+      // the patched float-table entries change this env's constant block: k_step rebuilds it behind this body (RF_RESET_INKERNEL), or the host follows
+      // this launch with k_prepare over the envs whose needs_reset flag is set
     }
     if (lane == 0) { b.done[env] = done ? 1 : 0; b.ep_step[env] = st; }
   }
@@ -4705,7 +4712,7 @@ __device__ __forceinline__ bool step_body(const DModel& m, const DBatch& b, cons
   }
   if (b.overflow && lane == 0 && sim.ovf) b.overflow[env] += sim.ovf;   // with capacity tiers: drops of the WIDE configuration only (pass 0 left above)
   if (b.cap_need && lane == 0) { int* cn = b.cap_need + 2 * (size_t)env; if (sim.need_con > cn[0]) cn[0] = sim.need_con; if (sim.need_efc > cn[1]) cn[1] = sim.need_efc; }
-  if (b.cost && lane == 0) {
+  if (b.cost && !reentry && lane == 0) {
     // dispatch-order key of the next step: this step's duration -- and half as much again for an env one of whose convex pairs ended within DModel.near_thresh of
     // touching: a contact that STARTS next step (full MPR runs, several times the Newton iterations) is what a duration cannot see coming, and such an env in the
     // last round of a launch is what ends it (profiles/r06_t_ab_peg_five_per_cu.txt).  Ordering only: no result depends on it.
@@ -4769,20 +4776,45 @@ __global__ RSIM_KSTEP_ATTR __launch_bounds__(64, RSIM_MINWAVES) void k_step(DMod
 #define b bk
   const int slot = (int)blockIdx.x;
   Handover ho;
-  ho.sub0 = 0; ho.time = 0.f; ho.fresh_ctrl = false; ho.handed = false; ho.ndiverged = 0; ho.need_con = 0; ho.need_efc = 0; ho.cstate = 0.f; ho.t_launch = 0u;
+  ho.sub0 = 0; ho.time = 0.f; ho.fresh_ctrl = false; ho.handed = false; ho.ndiverged = 0; ho.need_con = 0; ho.need_efc = 0; ho.cstate = 0.f; ho.t_launch = 0u; ho.restarted = false;
   bool wide = false;
   if (b.tier_cur) {
     if (slot >= (b.nenv ? b.nenv : b.B)) return;
     wide = b.tier_cur[uni((b.order ? b.order[slot] : slot) + b.env0)] != 0;
   }
-  if (!wide) {
-    const int over = uni(step_body<NB, NJ, NV, NG, NS, NCON, NEFC, NPAIR, false, 1>(m, b, actions, n_sub, flags, slot, &ho) ? 1 : 0);
-    if (!over) return;
-    // wave-uniform by construction; said so explicitly (the compiler sees them leave a branch on a vector condition)
-    ho.sub0 = uni(ho.sub0); ho.time = __builtin_bit_cast(float, uni(__builtin_bit_cast(int, ho.time))); ho.fresh_ctrl = uni(ho.fresh_ctrl ? 1 : 0) != 0; ho.handed = true;
-    ho.ndiverged = uni(ho.ndiverged); ho.need_con = uni(ho.need_con); ho.need_efc = uni(ho.need_efc); ho.t_launch = (unsigned)uni((int)ho.t_launch);
+  // RF_RESET_INKERNEL: an env whose episode this step ended (8 of 4096 in a lockstep step) gets what k_prepare(reset_only) and k_reset_obs would give it from
+  // its own workgroup, right behind the step: its constant block rebuilt from the patched float table, then the native body once more under the flags of
+  // k_reset_obs -- state and constants reloaded from global memory, so the pass computes what the separate launch computes.  The second round of the loop
+  // carries no RF_RESET_INKERNEL and ends it.  One call site per body: a second inlined copy of either would double the kernel.
+  const float* act = actions;
+  int nsub = n_sub, fl = flags;
+  for (;;) {
+    bool over = wide;
+    if (!wide) {
+      over = uni(step_body<NB, NJ, NV, NG, NS, NCON, NEFC, NPAIR, false, 1>(m, b, act, nsub, fl, slot, &ho) ? 1 : 0) != 0;
+      if (over) {
+        // wave-uniform by construction; said so explicitly (the compiler sees them leave a branch on a vector condition)
+        ho.sub0 = uni(ho.sub0); ho.time = __builtin_bit_cast(float, uni(__builtin_bit_cast(int, ho.time))); ho.fresh_ctrl = uni(ho.fresh_ctrl ? 1 : 0) != 0; ho.handed = true;
+        ho.ndiverged = uni(ho.ndiverged); ho.need_con = uni(ho.need_con); ho.need_efc = uni(ho.need_efc); ho.t_launch = (unsigned)uni((int)ho.t_launch);
+      }
+    }
+    if (over) step_body<RSIM_DIMS_W, false, 2>(m, b, act, nsub, fl, slot, &ho);
+    if (!(fl & RF_RESET_INKERNEL) || !uni(ho.restarted ? 1 : 0)) return;
+    // the step's stores (state, patched float-table entries, cleared warm-start words, needs_reset) before the loads of the rebuild and of the pass: the
+    // vector L1 is invalidated by the acquire, the scalar cache -- which the memory model leaves out -- by hand
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    __builtin_amdgcn_s_dcache_inv();
+    if (b.cm_stride != 0 && b.bank_P > 0) {
+      const int env = uni((b.order ? b.order[slot] : slot) + b.env0);
+      char* const cmb = (char*)b.cm_env + (size_t)env * b.cm_stride;
+      Sim<Smem<NB, NJ, NV, NG, NS, NCON, NEFC, NPAIR>> ps(m, m.ft + (size_t)env * m.fstride, opaque_lane((int)threadIdx.x), nullptr, cmb, cmb);
+      ps.prepare_constants((cmw_t)cmb);
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      __builtin_amdgcn_s_dcache_inv();
+    }
+    if (!m.task.enabled) return;   // no observation record to take (the host launches no k_reset_obs either)
+    act = nullptr; nsub = 1; fl = RF_POSVEL | RF_ACTSOLVE | RF_OBS | RF_RESET_ONLY; wide = false;
   }
-  step_body<RSIM_DIMS_W, false, 2>(m, b, actions, n_sub, flags, slot, &ho);
 #undef m
 #undef b
 #else
