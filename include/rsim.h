@@ -193,11 +193,18 @@ enum rsim_field {
   RSIM_TERMINAL_OBS,   /* [B,nobs]     observation record of the control step that ENDED an env's episode (valid where RSIM_DONE was reported); with a reset
                         *               bank installed RSIM_OBS of such an env already holds the observation MujocoEnv.reset() returns for its next
                         *               episode (gym auto-reset convention), the reward / success flags stay those of the terminal step */
-  RSIM_SENSORDATA,     /* [B,nsensordata] mjData.sensordata (binding_utils.py:935-938; Robot.get_sensor_measurement, robots/robot.py:739-751): the <force> and
-                        *               <torque> sensors at a site (the grippers' ft_frame) as mj_sensorAcc evaluates them -- the wrench the site body's
-                        *               parent transmits to it, from the solved accelerations and contact forces, in the site frame -- written by
-                        *               rsim_forward / rsim_step2 / rsim_step (the values of the last substep, before its integration).  Sensors of
-                        *               other types read zero.  rsim_model_int("nsensordata") gives the row length */
+  RSIM_SENSORDATA,     /* [B,nsensordata] mjData.sensordata (binding_utils.py:935-938; Robot.get_sensor_measurement, robots/robot.py:739-751), MuJoCo's semantics
+                        *               [3P, docs "XML reference: sensor"].  <force> / <torque> at a site (the grippers' ft_frame) as mj_sensorAcc evaluates them --
+                        *               the wrench the site body's parent transmits to it, from the solved accelerations and contact forces, in the site frame.
+                        *               Carried besides them: jointpos, jointvel (hinge / slide), tendonpos, tendonvel (fixed tendons), framepos, framequat,
+                        *               framelinvel, frameangvel (objtype site | xbody | body), velocimeter, gyro, accelerometer (at a site), touch (sphere,
+                        *               ellipsoid or box site) and actuatorfrc.  Written by rsim_forward / rsim_step2 / rsim_step / rsim_step2_last / rsim_observe:
+                        *               the values of the last substep, before its integration; rsim_step1 / rsim_run_controller write the position- and
+                        *               velocity-stage entries only and leave the acceleration-stage ones (force, torque, accelerometer, touch, actuatorfrc) as
+                        *               they are, as mj_step1 does.  A sensor that is not carried -- another type, reftype / refname, objtype geom | camera, a
+                        *               capsule or cylinder touch site, jointpos on a ball or free joint, a non-zero cutoff -- compiles and reads zero:
+                        *               rsim_model_int("nsensor_zero") counts them, rsim_sensor_slice names them.  noise is ignored, as MuJoCo's simulation
+                        *               ignores it.  rsim_model_int("nsensordata") gives the row length */
   RSIM_TASK_OBJECT,    /* [B] int32    PickPlace single-object mode 1: index of the object this env's current episode uses (see rsim_task_desc.single_object_mode) */
   RSIM_CAP_NEED,       /* [B,2] int32  largest number of contacts / constraint rows any substep of the env has asked for since the batch was created (what
                         *               RSIM_OVERFLOW's drops are measured against: a value above rsim_batch_limits means that substep was truncated);
@@ -241,8 +248,12 @@ int rsim_model_compile(const char* xml, size_t len, const char* asset_dir, rsim_
 int rsim_mjcf_to_blob(const char* xml, size_t len, const char* asset_dir, void** blob, size_t* blob_len);
 void rsim_blob_free(void* blob);
 void rsim_model_free(rsim_model* m);
-/* scalar / size query by blob field name ("nq", "nv", ...); returns -1 if unknown */
+/* scalar / size query by blob field name ("nq", "nv", ...); returns -1 if unknown.  Beyond the blob's fields: "nsensordata", and "nsensor_zero" = the
+ * number of sensors that read zero because their type, object or an option of theirs is not carried (RSIM_SENSORDATA) */
 int rsim_model_int(const rsim_model* m, const char* name);
+/* Where sensor `sensor_id` (rsim_name2id(m, "sensor", ..)) sits in a row of RSIM_SENSORDATA: first entry, number of entries, and whether it is computed
+ * (1) or reads zero (0).  Any of the three pointers may be NULL.  Non-zero return: bad id. */
+int rsim_sensor_slice(const rsim_model* m, int sensor_id, int* adr, int* dim, int* carried);
 /* Which compiled kernel configuration serves this model: 0 = 32 bodies x 16 dofs (Lift/Panda), 1 = 32 x 32 (Stack/Panda), 2 = 64 x 16 (Baxter);
  * 3 = 64 x 64 with tendon rows (PickPlace/IIWA+Robotiq140); -1 = none (rsim_batch_create would refuse it).  limits, if not NULL, receives 10 ints: {nbody, njnt, nv, ncgeom, nsite, ncon, nefc, npair, articulated trees} maxima
  * and a flag word: bit 0 = the configuration carries tendon / equality rows (the 32 x 16 one does not: such models go to the next larger one), bit 1 = two-arm

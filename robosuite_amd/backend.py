@@ -210,6 +210,8 @@ def lib():
             L.rsim_blob_free.restype = None
         L.rsim_model_free.argtypes = [vp]
         L.rsim_model_int.argtypes = [vp, C.c_char_p]
+        if hasattr(L, "rsim_sensor_slice"):        # (as above: absent from an earlier build named by RSIM_LIB)
+            L.rsim_sensor_slice.argtypes = [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.rsim_model_set_controller.argtypes = [vp, C.POINTER(CtrlDesc)]
         L.rsim_model_set_task.argtypes = [vp, C.POINTER(TaskDesc)]
         L.rsim_model_cgeom.argtypes = [vp, C.c_int]
@@ -360,6 +362,32 @@ class HipModel:
         r = self._L.rsim_id2name(self.ptr, kind.encode(), int(i))
         return None if r is None else r.decode()
 
+    def sensor_slice(self, name: str):
+        """(first entry, number of entries, carried) of the named sensor in a row of `sensordata` (include/rsim.h rsim_sensor_slice); carried = False: it reads zero."""
+        sid = self.name2id("sensor", name)
+        if sid < 0:
+            raise KeyError(f"no sensor named {name!r} in the model")
+        adr, dim, carried = C.c_int(), C.c_int(), C.c_int()
+        _chk(self._L.rsim_sensor_slice(self.ptr, sid, C.byref(adr), C.byref(dim), C.byref(carried)))
+        return adr.value, dim.value, bool(carried.value)
+
+    def sensor_status(self):
+        """[(name, type, carried, reason)] of every sensor: `type` the MJCF element ("other" for one outside mjcf.SENSOR_TYPES), `reason` why a sensor that is
+        not carried reads zero ("" for a carried one)."""
+        f = self.flat
+        n = self.int("nsensor")
+        types, reasons = (np.asarray(f.arrays["sensor_type"]).ravel() if n > 0 else []), f.arrays.get("sensor_reason")
+        names = f.names.get("sensor") or [None] * n      # (blobs written before names rode in them)
+        out = []
+        for i in range(max(n, 0)):
+            adr, dim, carried = C.c_int(), C.c_int(), C.c_int()
+            _chk(self._L.rsim_sensor_slice(self.ptr, i, C.byref(adr), C.byref(dim), C.byref(carried)))
+            t = int(types[i])
+            r = int(np.asarray(reasons).ravel()[i]) if reasons is not None else (0 if t in (0, 1) else 1)
+            reason = "" if carried.value else (mjcf.SENSOR_REASONS.get(r) or "not carried by this build")
+            out.append((names[i], mjcf.SENSOR_TYPE_NAMES.get(t, "other"), bool(carried.value), reason))
+        return out
+
     def kernel_config(self):
         """(config id, limits dict) of the compiled kernel configuration that serves this model; id -1 = unsupported size."""
         lim = (C.c_int * 10)()
@@ -472,6 +500,12 @@ class HipBatch:
         p = self._L.rsim_device_ptr(self.ptr, FIELD_ID[name], C.byref(cnt))
         typestr = "<i4" if name in INT_FIELDS else "<f4"
         return torch.as_tensor(_DevArray(p, self.shapes[name], typestr, self), device=f"cuda:{self.device}")
+
+    def sensor(self, name: str):
+        """Device tensor view [B, dim] of the named sensor's entries of `sensordata` (no copy).  Like `tensor("sensordata")`, a read after a fused control
+        step first brings the derived arrays up to the current state; the values are final once the batch's stream has run (`sync()`)."""
+        adr, dim, _ = self.model.sensor_slice(name)
+        return self.tensor("sensordata")[:, adr:adr + dim]
 
     # ---- simulation ------------------------------------------------------------------------
     def reset(self, mask=None):

@@ -62,6 +62,11 @@ class BatchState:
         pos = self.xpos[:, b] + torch.einsum("bij,j->bi", R, self._site_pos[site])
         return pos, torch.einsum("bij,jk->bik", R, self.quat2mat(self._site_quat[site]))
 
+    def sensor(self, name: str):
+        """sim.data.sensordata of the named sensor for every env: a device view [B, dim] (Robot.get_sensor_measurement, robots/robot.py:739-751).  Between
+        step1 and step2 the position- and velocity-stage sensors are those of the current substep, the acceleration-stage ones of the previous."""
+        return self.batch.sensor(name)
+
     def body_dofs(self, body: int):
         """bool [nv]: the dofs that move `body` (its own joints and those of its ancestors)."""
         import torch

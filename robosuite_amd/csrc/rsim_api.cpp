@@ -77,6 +77,7 @@ extern "C" int rsim_launch_order(const unsigned* cost, int* order, int B, hipStr
 extern "C" int rsim_launch_bank_scatter(float* bank, int* tag, const int* env, const int* episode, const float* rows, int n, int E, int W, hipStream_t stream);
 extern "C" int rsim_launch_randomize(const DModel* m, const DBatch* b, const DDr* d, unsigned long long seed, unsigned long long step, hipStream_t stream);
 #include "rsim_episode.h"
+#include "rsim_sensors.h"
 
 struct rsim_model;
 static int param_offset_impl(const rsim_model* m, const char* field, int elem);
@@ -117,6 +118,10 @@ struct rsim_model {
   std::vector<int> lanetab;   // [LT_COUNT][64]
   int kin_rounds, ndynroot, dynroot[RSIM_MAXDYNROOT], maxcondim, multijoint;
   int ntendon, neq, nsensor, nsensordata;
+  // sensors beyond force / torque (rsim_sensors.hip): per sensor its object kind, whether k_sensors computes it, the shape / size of a touch site; and their counts
+  std::vector<int> sens_objtype, sens_carried, sens_shape, sens_adr;
+  std::vector<float> sens_size;
+  int nsensor_extra, nsensor_zero;   // sensors k_sensors computes | sensors that read zero
   DCtrl ctrl;
   rsim_task_desc task;
   int has_task;
@@ -202,6 +207,9 @@ struct rsim_batch {
   int* d_end_reason;     // [B] RSIM_END_REASON
   int* d_seen_diverged;  // [B] RSIM_DIVERGED as of the last k_end_episodes launch (allocated when a rule is first armed)
   int* d_end_sel;        // [B] envs the last rsim_end_episodes restarted (allocated on first use)
+  // sensors beyond force / torque (rsim_sensors.hip): allocated only for a model that has one k_sensors computes
+  int* d_sens_i;         // [3][nsensor] object kind, carried flag, touch-site shape; then [ngeom] body of every geom
+  float* d_sens_f;       // [nsensor][3] touch-site sizes; then [B][nq + nv + nu]: qpos / qvel / ctrl as they were ahead of a debug launch that integrates
   int ended_outside;     // rsim_end_episodes left needs_reset flags for the next rsim_control_step (fresh controllers); rsim_step2_last, which runs no in-kernel controller, drops them first
   // stream groups: control steps of env block g run on gstream[g]; `forked` = the group streams hold work the main stream has not waited for
   int groups, ngroups, forked;   // streams created, groups in use (1 = everything on the main stream)
@@ -446,6 +454,37 @@ extern "C" int rsim_model_create(const void* blob, size_t len, rsim_model** out)
     }
     m->nsensordata = sa[m->nsensor];
     push(IO_sensor_type, st); push(IO_sensor_site, ss); push(IO_sensor_adr, sa);
+    // the further types (rsim_sensors.h): blobs compiled before they existed, and models with force / torque only, have no sensor_objtype / _reason / _shape
+    // entries -- every sensor of another type then reads zero, as it always did.  An object id the tables do not hold is not trusted to the kernel.
+    const int ns = m->nsensor, nt = m->I("ntendon") ? m->I("ntendon")[0] : 0;
+    m->sens_objtype.assign(ns, RS_OBJ_NONE); m->sens_carried.assign(ns, 0); m->sens_shape.assign(ns, -1); m->sens_size.assign((size_t)3 * ns + 3, 0.f); m->sens_adr = sa;
+    m->nsensor_extra = 0; m->nsensor_zero = 0;
+    const int *ot = m->I("sensor_objtype"), *rs = m->I("sensor_reason"), *sh = m->I("sensor_shape");
+    const bool have = ot && rs && sh && m->count("sensor_objtype") == (size_t)ns && m->count("sensor_reason") == (size_t)ns && m->count("sensor_shape") == (size_t)ns;
+    for (int i = 0; i < ns; i++) {
+      if (st[i] == 0 || st[i] == 1) continue;
+      bool ok = have && rs[i] == 0 && st[i] >= RS_JOINTPOS && st[i] < RS_TYPE_END;
+      if (ok) {
+        const int k = ot[i], o = ss[i], dim = sa[i + 1] - sa[i];
+        const int limit = k == RS_OBJ_JOINT ? nj : k == RS_OBJ_TENDON ? nt : k == RS_OBJ_SITE ? m->nsite : (k == RS_OBJ_XBODY || k == RS_OBJ_BODY) ? nb : k == RS_OBJ_ACTUATOR ? m->nu : 0;
+        const int want = (st[i] == RS_JOINTPOS || st[i] == RS_JOINTVEL) ? RS_OBJ_JOINT : (st[i] == RS_TENDONPOS || st[i] == RS_TENDONVEL) ? RS_OBJ_TENDON
+                         : st[i] == RS_ACTUATORFRC ? RS_OBJ_ACTUATOR : (st[i] == RS_FRAMEPOS || st[i] == RS_FRAMEQUAT || st[i] == RS_FRAMELINVEL || st[i] == RS_FRAMEANGVEL) ? -1 : RS_OBJ_SITE;
+        const int wdim = st[i] == RS_FRAMEQUAT ? 4 : (st[i] == RS_FRAMEPOS || (st[i] >= RS_VELOCIMETER && st[i] <= RS_ACCELEROMETER)) ? 3 : 1;
+        ok = o >= 0 && o < limit && dim == wdim && (want < 0 ? (k == RS_OBJ_SITE || k == RS_OBJ_XBODY || k == RS_OBJ_BODY) : k == want);
+        if (ok && k == RS_OBJ_JOINT) ok = jtype[o] == 2 || jtype[o] == 3;
+        if (ok && k == RS_OBJ_ACTUATOR) {   // the kernel reads one coordinate and one rate of the transmission joint: it must be a hinge or a slide
+          const int tj = m->I("actuator_trnid")[o];
+          ok = tj >= 0 && tj < nj && (jtype[tj] == 2 || jtype[tj] == 3);
+        }
+        if (ok && st[i] == RS_TOUCH) {
+          ok = (sh[i] == 2 || sh[i] == 4 || sh[i] == 6) && m->D("site_size") && m->count("site_size") >= (size_t)3 * m->nsite;
+          if (ok) for (int q = 0; q < 3; q++) m->sens_size[3 * i + q] = (float)m->D("site_size")[3 * o + q];
+        }
+        if (ok) { m->sens_objtype[i] = k; m->sens_shape[i] = sh[i]; }
+      }
+      m->sens_carried[i] = ok ? 1 : 0;
+      if (ok) m->nsensor_extra++; else m->nsensor_zero++;
+    }
   }
   // ---- float table
   auto& ft = m->ftab;
@@ -591,10 +630,20 @@ extern "C" int rsim_model_int(const rsim_model* m, const char* name) {
   if (!strcmp(name, "cstate_size")) return m->ctrl.enabled ? m->ctrl.cs_size : RSIM_CS_SIZE;
   if (!strcmp(name, "action_dim")) return m->ctrl.enabled ? m->ctrl.action_dim : 0;
   if (!strcmp(name, "nsensordata")) return m->nsensordata;
+  if (!strcmp(name, "nsensor_zero")) return m->nsensor_zero;                                      // sensors that read zero (a type, object or option that is not carried)
   if (!strcmp(name, "float_table_size")) return (int)m->ftab.size();                              // floats of one env's model float table
   if (!strcmp(name, "constant_block_bytes")) { const int c = pick_config(m, nullptr); return c < 0 ? -1 : k_cmem_bytes[c](); }   // one env's constant block
   const int* v = m->I(name);
   return v ? v[0] : -1;
+}
+
+extern "C" int rsim_sensor_slice(const rsim_model* m, int sensor_id, int* adr, int* dim, int* carried) {
+  if (!m || sensor_id < 0 || sensor_id >= m->nsensor) return fail("rsim_sensor_slice: sensor id %d out of range (%d sensors)", sensor_id, m ? m->nsensor : 0);
+  const int t = m->I("sensor_type")[sensor_id];
+  if (adr) *adr = m->sens_adr[sensor_id];
+  if (dim) *dim = m->sens_adr[sensor_id + 1] - m->sens_adr[sensor_id];
+  if (carried) *carried = (t == 0 || t == 1 || m->sens_carried[sensor_id]) ? 1 : 0;
+  return 0;
 }
 
 extern "C" int rsim_model_set_controller(rsim_model* m, const rsim_ctrl_desc* d) {
@@ -789,6 +838,7 @@ extern "C" int rsim_batch_create(rsim_model* m, int B, int device, int per_env, 
   b->gen = 1; b->cache_gen = 0; b->cache_env = -1;
   b->db.prof_env = -1;
   b->d_bank = nullptr; b->d_bank_tag = nullptr; b->d_patch = nullptr; b->d_ft_base = nullptr;
+  b->d_sens_i = nullptr; b->d_sens_f = nullptr;
   b->bstream = nullptr; b->bev = nullptr; b->h_epidx = nullptr; b->bank_poll_pending = 0; b->bstage_next = 0;
   memset(b->bstage, 0, sizeof(b->bstage));
   const int ncg = (int)m->cg.size();
@@ -972,6 +1022,16 @@ extern "C" int rsim_batch_create(rsim_model* m, int B, int device, int per_env, 
     if (dalloc((float**)fd.p, fd.n)) return 1;
     b->fptr[fd.id] = *fd.p; b->fcount[fd.id] = fd.n; b->fis_int[fd.id] = fd.is_int;
   }
+  if (m->nsensor_extra > 0) {
+    const int ns = m->nsensor, ng = m->ngeom;
+    std::vector<int> si;
+    si.insert(si.end(), m->sens_objtype.begin(), m->sens_objtype.end()); si.insert(si.end(), m->sens_carried.begin(), m->sens_carried.end());
+    si.insert(si.end(), m->sens_shape.begin(), m->sens_shape.end()); si.insert(si.end(), m->I("geom_bodyid"), m->I("geom_bodyid") + ng);
+    if (dalloc(&b->d_sens_i, si.size())) return 1;
+    HIPCHK(hipMemcpy(b->d_sens_i, si.data(), si.size() * sizeof(int), hipMemcpyHostToDevice));
+    if (dalloc(&b->d_sens_f, (size_t)3 * ns + (size_t)B * (nq + nv + nu))) return 1;
+    HIPCHK(hipMemcpy(b->d_sens_f, m->sens_size.data(), (size_t)3 * ns * sizeof(float), hipMemcpyHostToDevice));
+  }
   *out = b;
   return rsim_reset(b, nullptr);
 }
@@ -997,6 +1057,8 @@ extern "C" void rsim_batch_free(rsim_batch* b) {
   }
   if (b->d_seen_diverged) hipFree(b->d_seen_diverged);
   if (b->d_end_sel) hipFree(b->d_end_sel);
+  if (b->d_sens_i) hipFree(b->d_sens_i);
+  if (b->d_sens_f) hipFree(b->d_sens_f);
   if (b->db.mprc) hipFree(b->db.mprc);
   if (b->db.jg) hipFree(b->db.jg);
   if (b->db.bpl) hipFree(b->db.bpl);
@@ -1209,6 +1271,38 @@ static int wide_pass(rsim_batch* b, const float* actions, int n_sub, int flags, 
   return 0;
 }
 
+// The sensors beyond force / torque (rsim_sensors.hip), directly behind a debug launch of the step kernel, on the same stream: position and velocity
+// stage always (mj_step1 computes those), the acceleration stage where the launch solved for the accelerations.  Their values belong to the substep before
+// its integration, as force / torque do: `pre` = the launch integrates, and qpos / qvel / ctrl are read from the copies sensors_keep_state took ahead of it.
+static int sensors_keep_state(rsim_batch* b) {
+  const rsim_model* m = b->m;
+  float* keep = b->d_sens_f + (size_t)3 * m->nsensor;
+  const size_t B = (size_t)b->B;
+  HIPCHK(hipMemcpyAsync(keep, b->db.qpos, B * m->nq * sizeof(float), hipMemcpyDeviceToDevice, b->stream));
+  HIPCHK(hipMemcpyAsync(keep + B * m->nq, b->db.qvel, B * m->nv * sizeof(float), hipMemcpyDeviceToDevice, b->stream));
+  if (m->nu) HIPCHK(hipMemcpyAsync(keep + B * (m->nq + m->nv), b->db.ctrl, B * m->nu * sizeof(float), hipMemcpyDeviceToDevice, b->stream));
+  return 0;
+}
+static int sensors_launch(rsim_batch* b, int stages, bool pre) {
+  const rsim_model* m = b->m;
+  DSensors a;
+  memset(&a, 0, sizeof(a));
+  a.B = b->B; a.stages = stages;
+  a.nq = m->nq; a.nv = m->nv; a.nu = m->nu; a.nbody = m->nbody; a.nsensor = m->nsensor; a.nsensordata = m->nsensordata; a.ncon_max = b->lim[5]; a.fstride = b->dm.fstride;
+  memcpy(a.io, m->io, sizeof(a.io)); memcpy(a.fo, m->fo, sizeof(a.fo));
+  a.it = b->d_it; a.ft = b->d_ft;
+  a.objtype = b->d_sens_i; a.carried = b->d_sens_i + m->nsensor; a.shape = b->d_sens_i + 2 * m->nsensor; a.geom_body = b->d_sens_i + 3 * m->nsensor;
+  a.site_size = b->d_sens_f;
+  const float* keep = b->d_sens_f + (size_t)3 * m->nsensor;
+  const size_t B = (size_t)b->B;
+  a.qpos = pre ? keep : b->db.qpos; a.qvel = pre ? keep + B * m->nq : b->db.qvel; a.ctrl = pre ? keep + B * (m->nq + m->nv) : b->db.ctrl;
+  a.qacc = b->db.qacc; a.xpos = b->db.xpos; a.xquat = b->db.xquat; a.cdof = b->db.cdof; a.rootcom = b->db.rootcom; a.contact = b->db.contact; a.ncon = b->db.ncon;
+  a.sensordata = b->db.sensordata;
+  const int e = rsim_launch_sensors(&a, b->stream);
+  if (e) return fail("sensor kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+  return 0;
+}
+
 static int launch(rsim_batch* b, const float* actions, int n_sub, int flags) {
   const int WCN = 2 + 2 * RSIM_MAX_GROUPS;   // list lengths per step parity
   HIPCHK(hipSetDevice(b->device));
@@ -1325,8 +1419,12 @@ static int launch(rsim_batch* b, const float* actions, int n_sub, int flags) {
     b->db.wlist2 = b->d_wlist[1]; b->db.wcount2 = cnt + 1;
   }
   if (traced) tr_mark(b, 2);
+  const bool sensors = (flags & RF_DEBUG) && b->d_sens_i && b->db.sensordata;   // (a model without a sensor of the further types launches nothing extra)
+  const bool sens_pre = sensors && (flags & RF_INTEGRATE);
+  if (sens_pre && sensors_keep_state(b)) return 1;
   int e = k_step_launch[b->cfg](&b->dm, &b->db, actions, n_sub, flags, b->stream);
   if (e) return fail("kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+  if (sensors && sensors_launch(b, RS_STAGE_POS | RS_STAGE_VEL | ((flags & RF_ACTSOLVE) ? RS_STAGE_ACC : 0), sens_pre)) return 1;
   if (traced) tr_mark(b, 3);
   if (listed) {
     // after both: the envs the native pass had to hand over in mid-step (rare: most move up between steps), redone from their unchanged state

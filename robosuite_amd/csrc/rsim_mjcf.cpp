@@ -667,7 +667,7 @@ struct Joint { std::string name; bool named; int body, type; V3 pos, axis; bool 
                double solreflimit[2], solimplimit[5], solreffriction[2], solimpfriction[5]; int qposadr, dofadr; };
 struct Geom { std::string name; bool named; int body, type; std::string mesh; bool has_mesh; V3 size, pos; Q quat; int contype, conaffinity, condim, group, priority; double friction[3], solref[2], solimp[5],
               solmix, margin, gap, density, mass; bool has_mass; double rgba[4]; int dataid; };
-struct Site { std::string name; bool named; int body; V3 pos; Q quat; double size[3], rgba[4]; };
+struct Site { std::string name; bool named; int body; V3 pos; Q quat; double size[3], rgba[4]; int type; /* shape (geom numbering, -1 unknown): not in the blob, a touch sensor records it */ };
 struct Named { std::string name; bool named; int body; };
 struct MeshAsset { std::string name, file; bool has_file; double scale[3]; bool loaded; std::vector<V3> hull_vert; double volume; V3 com; M3 inertia; };
 
@@ -819,6 +819,11 @@ Flat compile(const char* xml, size_t len, const std::string& asset_dir) {
     Site s{};
     name_of(se, s.name, s.named);
     s.body = bid;
+    {
+      static const std::map<std::string, int> types = {{"plane", 0}, {"hfield", 1}, {"sphere", 2}, {"capsule", 3}, {"ellipsoid", 4}, {"cylinder", 5}, {"box", 6}, {"mesh", 7}};
+      auto ti = types.find(se.gets("type", "sphere"));
+      s.type = ti == types.end() ? -1 : ti->second;
+    }
     vecd size; bool has = floats(se.get("size"), -1, nullptr, size);
     for (int k = 0; k < 3; k++) s.size[k] = 0.005;
     if (has) for (size_t k = 0; k < std::min<size_t>(3, size.size()); k++) s.size[k] = size[k];
@@ -1176,24 +1181,67 @@ Flat compile(const char* xml, size_t len, const std::string& asset_dir) {
     m.seti("actuator_trnid", trn); m.setd("actuator_gear", gear); m.setd("actuator_gainprm", gain); m.setd("actuator_biasprm", bias); m.seti("actuator_biastype", bt);
     m.seti("actuator_ctrllimited", cl); m.setd("actuator_ctrlrange", cr); m.seti("actuator_forcelimited", fl); m.setd("actuator_forcerange", fr);
   }
-  // ---- sensors: names + dims; force / torque at a site carry their site
+  // ---- sensors: names, dims, types, objects.  force / torque at a site keep codes 0 / 1 and their site; the further types of the table below are computed by
+  // rsim_sensors.hip (MuJoCo semantics [3P, "XML reference: sensor"]); any other element compiles to -1.  A sensor that is not carried keeps compiling and
+  // reads zero: sensor_reason says why (mjcf.py SENSOR_REASONS).  The Python compiler's section of the same name is the checker of this one.
   std::vector<std::pair<std::string, bool>> sens_names;
   {
-    std::vector<int32_t> sdim, sobj, stype;
-    static const std::map<std::string, int> dims = {{"force", 3}, {"torque", 3}, {"touch", 1}, {"framepos", 3}, {"framequat", 4}, {"jointpos", 1}, {"jointvel", 1}};
+    std::vector<int32_t> sdim, sobj, stype, skind, sreason, sshape;
+    static const std::map<std::string, int> dims = {{"force", 3}, {"torque", 3}, {"touch", 1}, {"framepos", 3}, {"framequat", 4}, {"jointpos", 1}, {"jointvel", 1},
+                                                    {"velocimeter", 3}, {"gyro", 3}, {"accelerometer", 3}, {"framelinvel", 3}, {"frameangvel", 3}};
+    static const std::map<std::string, int> codes = {{"force", 0}, {"torque", 1}, {"jointpos", 2}, {"tendonpos", 3}, {"framepos", 4}, {"framequat", 5}, {"jointvel", 6}, {"tendonvel", 7},
+                                                     {"velocimeter", 8}, {"gyro", 9}, {"framelinvel", 10}, {"frameangvel", 11}, {"accelerometer", 12}, {"touch", 13}, {"actuatorfrc", 14}};
+    enum { OBJ_NONE, OBJ_JOINT, OBJ_TENDON, OBJ_SITE, OBJ_XBODY, OBJ_BODY, OBJ_ACTUATOR };
+    std::vector<std::pair<std::string, bool>> tnames;   // tendons are compiled further down: their names are all a sensor needs
+    if (const Xml* tend = root.find("tendon")) for (auto& t : tend->kids) { std::string nm; bool named; name_of(*t, nm, named); tnames.emplace_back(nm, named); }
+    // a named object, the last of that name (the Python compiler looks names up in a dict built in id order)
+    auto find_named = [&](int kind, const std::string* nm) {
+      int hit = -1;
+      if (!nm) return hit;
+      if (kind == OBJ_JOINT) { for (int i = 0; i < njnt; i++) if (joints[i].named && joints[i].name == *nm) hit = i; }
+      else if (kind == OBJ_TENDON) { for (size_t i = 0; i < tnames.size(); i++) if (tnames[i].second && tnames[i].first == *nm) hit = (int)i; }
+      else if (kind == OBJ_SITE) { for (int i = 0; i < nsite; i++) if (sites[i].named && sites[i].name == *nm) hit = i; }
+      else if (kind == OBJ_XBODY || kind == OBJ_BODY) { for (int i = 0; i < nbody; i++) if (bodies[i].named && bodies[i].name == *nm) hit = i; }
+      else if (kind == OBJ_ACTUATOR) { for (size_t i = 0; i < act_names.size(); i++) if (act_names[i].second && act_names[i].first == *nm) hit = (int)i; }
+      return hit;
+    };
+    bool extra = false;
     // the Python compiler maps sites by name through a dict built over ALL sites (an unnamed site is the key None; a later site of the same name wins)
     if (const Xml* se = root.find("sensor")) for (auto& s : se->kids) {
       std::string nm; bool named; name_of(*s, nm, named);
       sens_names.emplace_back(nm, named);
       auto di = dims.find(s->tag);
       sdim.push_back(di == dims.end() ? 1 : di->second);
-      const std::string* sn = s->get("site");
-      int sid = -1;
-      for (int i = 0; i < nsite; i++) if (sn ? (sites[i].named && sites[i].name == *sn) : !sites[i].named) sid = i;
-      sobj.push_back(sid);
-      stype.push_back(s->tag == "force" ? 0 : (s->tag == "torque" ? 1 : -1));
+      auto ci = codes.find(s->tag);
+      const int code = ci == codes.end() ? -1 : ci->second;
+      stype.push_back(code);
+      if (code < 2) {
+        const std::string* sn = s->get("site");
+        int sid = -1;
+        for (int i = 0; i < nsite; i++) if (sn ? (sites[i].named && sites[i].name == *sn) : !sites[i].named) sid = i;
+        sobj.push_back(sid); skind.push_back(code >= 0 ? OBJ_SITE : OBJ_NONE); sreason.push_back(code >= 0 ? 0 : 1); sshape.push_back(-1);
+        if (code < 0) extra = true;
+        continue;
+      }
+      extra = true;
+      int kind = OBJ_NONE; const char* attr = "objname";
+      const std::string& tg = s->tag;
+      if (tg == "jointpos" || tg == "jointvel") { kind = OBJ_JOINT; attr = "joint"; }
+      else if (tg == "tendonpos" || tg == "tendonvel") { kind = OBJ_TENDON; attr = "tendon"; }
+      else if (tg == "actuatorfrc") { kind = OBJ_ACTUATOR; attr = "actuator"; }
+      else if (tg == "velocimeter" || tg == "gyro" || tg == "accelerometer" || tg == "touch") { kind = OBJ_SITE; attr = "site"; }
+      else { const std::string ot = s->gets("objtype", ""); kind = ot == "site" ? OBJ_SITE : (ot == "xbody" ? OBJ_XBODY : (ot == "body" ? OBJ_BODY : OBJ_NONE)); }
+      int oid = -1, reason = 0, shape = -1;
+      if (kind == OBJ_NONE) reason = 3;
+      else { oid = find_named(kind, s->get(attr)); if (oid < 0) reason = 7; }
+      if (reason == 0 && kind == OBJ_JOINT && joints[oid].type != JNT_HINGE && joints[oid].type != JNT_SLIDE) reason = 5;
+      if (reason == 0 && tg == "touch") { shape = sites[oid].type; if (shape != GEOM_SPHERE && shape != GEOM_ELLIPSOID && shape != GEOM_BOX) reason = 4; }
+      if (reason == 0 && (s->get("reftype") || s->get("refname"))) reason = 2;
+      if (reason == 0 && to_double(s->gets("cutoff", "0")) != 0.0) reason = 6;
+      sobj.push_back(oid); skind.push_back(kind); sreason.push_back(reason); sshape.push_back(shape);
     }
     m.seti1("nsensor", (long)sdim.size()); m.seti("sensor_dim", sdim); m.seti("sensor_objid", sobj); m.seti("sensor_type", stype);
+    if (extra) { m.seti("sensor_objtype", skind); m.seti("sensor_reason", sreason); m.seti("sensor_shape", sshape); }   // a force / torque-only model keeps the blob it always had
   }
   // ---- fixed tendons, tendon equality constraints
   struct Tendon { std::string name; bool named; std::vector<std::pair<int, double>> wraps; double range[2], stiffness, damping, ls[2], margin, solref[2], solimp[5], frictionloss, solref_fri[2], solimp_fri[5]; int limited; };

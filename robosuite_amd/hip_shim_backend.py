@@ -38,6 +38,15 @@ class HipShimBackend:
         }
         self._ncon = 0
         self._contacts = []
+        # sensordata entries mj_step1 refreshes: the position- and velocity-stage sensors (mjcf.SENSOR_TYPES codes 2 .. 11)
+        sd = np.concatenate([[0], np.cumsum(np.asarray(m.arrays["sensor_dim"]).ravel())]).astype(int) if m.nsensor else np.zeros(1, dtype=int)
+        st = np.asarray(m.arrays["sensor_type"]).ravel() if m.nsensor else []
+        self._posvel = np.concatenate([np.arange(sd[i], sd[i + 1]) for i in range(len(st)) if 2 <= st[i] <= 11] + [np.zeros(0, dtype=int)]).astype(int)
+        zero = [(n, r) for n, _, carried, r in self.model.sensor_status() if not carried] if self.model.int("nsensor_zero") > 0 else []
+        if zero:
+            import warnings
+
+            warnings.warn("sensors that are not carried read zero: " + "; ".join(f"{n!r} ({r})" for n, r in zero), stacklevel=2)
 
     # ---- shim protocol -------------------------------------------------------------------------
     def model_array(self, name):
@@ -62,8 +71,10 @@ class HipShimBackend:
 
     def _pull(self, stepped, acc=True):
         b, d, m = self.batch, self.d, self.flat
-        if acc and len(d["sensordata"]):      # acceleration-stage sensors (mj_sensorAcc): force / torque at the gripper's ft_frame site
+        if acc and len(d["sensordata"]):      # every stage; acceleration-stage sensors (mj_sensorAcc): force / torque at the gripper's ft_frame site, accelerometer, touch, actuatorfrc
             d["sensordata"][:] = b.get("sensordata")[0]
+        elif len(self._posvel):               # mj_step1: the position- and velocity-stage entries only
+            d["sensordata"][self._posvel] = b.get("sensordata")[0][self._posvel]
         if stepped:
             for k in ("qpos", "qvel", "qacc_warmstart"):
                 d[k][:] = b.get(k)[0]

@@ -42,6 +42,22 @@ MINVAL = 1e-15
 
 GAIN_FIXED, BIAS_NONE, BIAS_AFFINE = 0, 0, 1
 
+# sensor_type codes of the blob (MuJoCo element names [3P, "XML reference: sensor"]); force / torque keep 0 / 1, any other element compiles to -1.
+# The same table is in csrc/rsim_mjcf.cpp and csrc/rsim_sensors.h.
+SENSOR_TYPES = {"force": 0, "torque": 1, "jointpos": 2, "tendonpos": 3, "framepos": 4, "framequat": 5, "jointvel": 6, "tendonvel": 7, "velocimeter": 8,
+                "gyro": 9, "framelinvel": 10, "frameangvel": 11, "accelerometer": 12, "touch": 13, "actuatorfrc": 14}
+SENSOR_TYPE_NAMES = {v: k for k, v in SENSOR_TYPES.items()}
+SENSOR_OBJ_NONE, SENSOR_OBJ_JOINT, SENSOR_OBJ_TENDON, SENSOR_OBJ_SITE, SENSOR_OBJ_XBODY, SENSOR_OBJ_BODY, SENSOR_OBJ_ACTUATOR = range(7)   # sensor_objtype
+# what a sensor's object is and the attribute that names it ("frame": objtype / objname)
+_SENSOR_OBJECT = {"jointpos": ("joint", "joint"), "jointvel": ("joint", "joint"), "tendonpos": ("tendon", "tendon"), "tendonvel": ("tendon", "tendon"),
+                  "framepos": ("frame", None), "framequat": ("frame", None), "framelinvel": ("frame", None), "frameangvel": ("frame", None),
+                  "velocimeter": ("site", "site"), "gyro": ("site", "site"), "accelerometer": ("site", "site"), "touch": ("site", "site"),
+                  "actuatorfrc": ("actuator", "actuator")}
+# sensor_reason: 0 = carried, otherwise why the sensor reads zero
+SENSOR_REASONS = {0: "", 1: "sensor type not carried", 2: "reftype / refname not carried", 3: "objtype not carried (site, xbody, body only)",
+                  4: "touch site shape not carried (sphere, ellipsoid, box only)", 5: "joint is not a hinge or slide", 6: "non-zero cutoff not carried",
+                  7: "object not found"}
+
 
 class MJCFError(ValueError):
     """Raised on malformed / unsupported MJCF (mirrors MuJoCo raising on compile errors)."""
@@ -550,6 +566,7 @@ def compile_mjcf(xml: str, asset_dir: str | None = None, max_hull_vert: int = 0)
                 pos=_floats(se.get("pos"), 3, [0, 0, 0]),
                 quat=_orientation(se, compiler),
                 size=s3,
+                type=_GEOM_TYPES.get(se.get("type", "sphere"), -1),      # not in the blob: touch sensors record the shape of their site (sensor_shape)
                 rgba=_floats(se.get("rgba"), 4, [0.5, 0.5, 0.5, 1]),
             )
         )
@@ -1004,18 +1021,61 @@ def compile_mjcf(xml: str, asset_dir: str | None = None, max_hull_vert: int = 0)
     m.set("actuator_forcelimited", np.array([a["forcelimited"] for a in acts], dtype=I32), I32)
     m.set("actuator_forcerange", np.array([a["forcerange"] for a in acts]).reshape(nu, 2), F64)
 
-    # ---- sensors / tendons / equality: names + dims only (force/torque sensors are §8(f)) ------
+    # ---- sensors: names, dims, types, objects (tendons / equality below) ------------------------------
+    # force / torque at a site are section 8(f); the thirteen further types of SENSOR_TYPES are computed by csrc/rsim_sensors.hip (host mirror: sensors.py).
+    # A sensor that is not carried keeps compiling and reads zero; sensor_reason says why (SENSOR_REASONS).
     sens = []
     se = root.find("sensor")
     if se is not None:
         for s in se:
-            sens.append(dict(name=s.get("name"), type=s.tag, site=s.get("site")))
-    _sdim = {"force": 3, "torque": 3, "touch": 1, "framepos": 3, "framequat": 4, "jointpos": 1, "jointvel": 1}
+            sens.append(dict(name=s.get("name"), type=s.tag, site=s.get("site"), elem=s))
+    _sdim = {"force": 3, "torque": 3, "touch": 1, "framepos": 3, "framequat": 4, "jointpos": 1, "jointvel": 1,
+             "velocimeter": 3, "gyro": 3, "accelerometer": 3, "framelinvel": 3, "frameangvel": 3}
     m.set("nsensor", len(sens), I32)
     m.set("sensor_dim", np.array([_sdim.get(s["type"], 1) for s in sens], dtype=I32), I32)
     sname2id = {s["name"]: i for i, s in enumerate(sites)}
-    m.set("sensor_objid", np.array([sname2id.get(s["site"], -1) for s in sens], dtype=I32), I32)
-    m.set("sensor_type", np.array([{"force": 0, "torque": 1}.get(s["type"], -1) for s in sens], dtype=I32), I32)
+    _named = lambda names: {n: i for i, n in enumerate(names) if n is not None}
+    tend_el = root.find("tendon")
+    _lookup = {"joint": _named([j["name"] for j in joints]), "tendon": _named([t.get("name") for t in tend_el] if tend_el is not None else []),
+               "site": _named([s["name"] for s in sites]), "body": _named([b["name"] for b in bodies]), "actuator": _named([a["name"] for a in acts])}
+    s_type, s_obj, s_kind, s_reason, s_shape = [], [], [], [], []
+    for s in sens:
+        code = SENSOR_TYPES.get(s["type"], -1)
+        e = s["elem"]
+        if code < 2:      # force / torque / a type outside the table: as before, the site (if any) is the object
+            s_type.append(code); s_obj.append(sname2id.get(s["site"], -1)); s_kind.append(SENSOR_OBJ_SITE if code >= 0 else SENSOR_OBJ_NONE)
+            s_reason.append(0 if code >= 0 else 1); s_shape.append(-1)
+            continue
+        kind, attr = _SENSOR_OBJECT[s["type"]]
+        if kind == "frame":
+            ot = e.get("objtype")
+            kind, attr = ({"site": "site", "xbody": "xbody", "body": "body"}.get(ot), "objname")
+        oid, reason, shape = -1, 0, -1
+        if kind is None:
+            reason = 3
+        else:
+            oid = _lookup["body" if kind in ("xbody", "body") else kind].get(e.get(attr), -1)
+            if oid < 0:
+                reason = 7
+        if reason == 0 and kind == "joint" and joints[oid]["type"] not in (JNT_HINGE, JNT_SLIDE):
+            reason = 5
+        if reason == 0 and s["type"] == "touch":
+            shape = sites[oid]["type"]
+            if shape not in (GEOM_SPHERE, GEOM_ELLIPSOID, GEOM_BOX):
+                reason = 4
+        if reason == 0 and (e.get("reftype") is not None or e.get("refname") is not None):
+            reason = 2
+        if reason == 0 and float(e.get("cutoff", "0")) != 0.0:
+            reason = 6
+        s_type.append(code); s_obj.append(oid); s_reason.append(reason); s_shape.append(shape)
+        s_kind.append({None: SENSOR_OBJ_NONE, "joint": SENSOR_OBJ_JOINT, "tendon": SENSOR_OBJ_TENDON, "site": SENSOR_OBJ_SITE, "xbody": SENSOR_OBJ_XBODY,
+                       "body": SENSOR_OBJ_BODY, "actuator": SENSOR_OBJ_ACTUATOR}[kind])
+    m.set("sensor_objid", np.array(s_obj, dtype=I32), I32)
+    m.set("sensor_type", np.array(s_type, dtype=I32), I32)
+    if any(t not in (0, 1) for t in s_type):      # a force / torque-only model keeps the blob it always had
+        m.set("sensor_objtype", np.array(s_kind, dtype=I32), I32)
+        m.set("sensor_reason", np.array(s_reason, dtype=I32), I32)
+        m.set("sensor_shape", np.array(s_shape, dtype=I32), I32)
     # ---- fixed tendons, tendon equality constraints (Robotiq grippers: models/assets/grippers/robotiq_gripper_140.xml:15-44) -------------
     # MuJoCo semantics [3P, docs "XML reference: tendon/fixed, equality/tendon"]: length = sum_i coef_i q_i; optional limit rows on the length;
     # an equality/tendon with one tendon constrains (length - length0) to polycoef[0] (default 0).

@@ -112,6 +112,13 @@ class VecEnv:
         self._ended_on_request = True
         return self.env.obs()
 
+    def sensor(self, name: str):
+        """sim.data.sensordata of the named sensor for every env, [n_envs, dim]: a device tensor aliasing the batch.  The fused `step` does not compute
+        sensors; the first read after it runs one forward pass on the current state (and waits for it), as robosuite's sim.forward() before such a read."""
+        s = self.env.batch.sensor(name)
+        self.env.batch.sync()
+        return s
+
     def enable_applied_forces(self, on: bool = True):
         """Honour `qfrc_applied` and `xfrc_applied` in `step` (off by default: the control step then reads neither).  An env that reports `done`
         has both rows zeroed for its next episode, in the same step, so a force written after seeing `done` acts on the new episode."""
