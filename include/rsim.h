@@ -398,6 +398,15 @@ const char* rsim_tuning_defaults(void);
 /* out2[0] = env-steps (env x control step) the wider capacity tier stepped since the batch was created, out2[1] = how many of them changed tier in mid-step
  * (carried on from the substep in which they outgrew the native capacity, or redone).  Synchronises the batch's stream.  bench.py reports both. */
 int rsim_tier_stats(rsim_batch* b, unsigned long long* out2);
+/* Configurations 0-2 compile the control step twice: a plain kernel, and a full one that also holds the profiler (rsim_profile), the MPR restart cone
+ * (RSIM_MPR_CONE) and the applied forces (rsim_set_applied_forces) behind their run-time switches; a launch takes the full one while any of the three is in
+ * use, or always when RSIM_FULL_STEP_KERNEL=1 was set when the batch was created.  Both compute the same bits.  out2[0] = launches of the plain kernel,
+ * out2[1] = of the full one, since the batch was created (0, 0 for the other configurations).  No synchronisation.  Diagnostics. */
+int rsim_step_kernel_launches(rsim_batch* b, unsigned long long* out2);
+/* The narrow phase's warm-start records as the last launch left them: HOST float32 [B][npair][12] (npair = rsim_model_int "npair"; per pair: a direction or
+ * depth, a flag -- 0 nothing known, 1 separating direction, 2 portal directions, 3 portal normal, 4 touched -- and two more portal directions).  An error
+ * for a batch that keeps none.  Synchronises the batch's stream.  No reference counterpart (diagnostics, bitwise comparisons of two builds). */
+int rsim_mpr_records(rsim_batch* b, float* host_out);
 /* per candidate pair p (model pair order): out[p] = narrow-phase visits, out[640 + p] = support-function calls (out: 1280 entries), summed over envs and launches since arming */
 int rsim_pairlog(rsim_batch* b, unsigned long long* out);
 

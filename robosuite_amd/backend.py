@@ -258,6 +258,9 @@ def lib():
         L.rsim_profile_env.argtypes = [vp, C.c_int]
         L.rsim_tier_snapshot.argtypes = [vp, vp]
         L.rsim_tier_stats.argtypes = [vp, vp]
+        if hasattr(L, "rsim_step_kernel_launches"):   # (as above: an earlier build named by RSIM_LIB)
+            L.rsim_step_kernel_launches.argtypes = [vp, vp]
+            L.rsim_mpr_records.argtypes = [vp, vp]
         if hasattr(L, "rsim_restart_flags"):       # (as above: an earlier build named by RSIM_LIB)
             L.rsim_restart_flags.argtypes = [vp, vp]
         L.rsim_tuning_defaults.restype = C.c_char_p
@@ -681,6 +684,18 @@ class HipBatch:
         out = np.zeros(2, dtype=np.uint64)
         _chk(self._L.rsim_tier_stats(self.ptr, out.ctypes.data))
         return int(out[0]), int(out[1])
+
+    def step_kernel_launches(self):
+        """(launches of the plain control-step kernel, launches of the full one) since the batch was created (include/rsim.h rsim_step_kernel_launches)."""
+        out = np.zeros(2, dtype=np.uint64)
+        _chk(self._L.rsim_step_kernel_launches(self.ptr, out.ctypes.data))
+        return int(out[0]), int(out[1])
+
+    def mpr_records(self):
+        """float32 [B, npair, 12]: the narrow phase's warm-start records as the last launch left them (include/rsim.h rsim_mpr_records); synchronises the stream."""
+        out = np.zeros((self.B, self._L.rsim_model_int(self.model.ptr, b"npair"), 12), dtype=np.float32)
+        _chk(self._L.rsim_mpr_records(self.ptr, out.ctypes.data))
+        return out
 
     def wavelog(self):
         """Per-env {hw_id, xcc_id, t_start, t_end} of the last launch (profiling must be armed)."""

@@ -50,6 +50,12 @@ typedef int (*step_fn)(const DModel*, const DBatch*, const float*, int, int, hip
 typedef int (*creset_fn)(const DModel*, const DBatch*, const unsigned char*, hipStream_t);
 typedef int (*limits_fn)(int*);
 static const step_fn k_step_launch[RSIM_NCFG] = {rsim_launch_step_cfg0, rsim_launch_step_cfg1, rsim_launch_step_cfg2, rsim_launch_step_cfg3, rsim_launch_step_cfg4};
+// configurations 0-2 hold the control step twice: k_step, the plain form a default launch runs, and k_full_step with the profiler, the MPR restart cone and the
+// applied forces behind their run-time switches (rsim_step.hip fused_step; step_launch() below picks per launch)
+extern "C" int rsim_launch_full_step_cfg0(const DModel* m, const DBatch* b, const float* actions, int n_sub, int flags, hipStream_t stream);
+extern "C" int rsim_launch_full_step_cfg1(const DModel* m, const DBatch* b, const float* actions, int n_sub, int flags, hipStream_t stream);
+extern "C" int rsim_launch_full_step_cfg2(const DModel* m, const DBatch* b, const float* actions, int n_sub, int flags, hipStream_t stream);
+static const step_fn k_full_step_launch[3] = {rsim_launch_full_step_cfg0, rsim_launch_full_step_cfg1, rsim_launch_full_step_cfg2};
 static const creset_fn k_creset_launch[RSIM_NCFG] = {rsim_launch_ctrl_reset_cfg0, rsim_launch_ctrl_reset_cfg1, rsim_launch_ctrl_reset_cfg2, rsim_launch_ctrl_reset_cfg3, rsim_launch_ctrl_reset_cfg4};
 extern "C" int rsim_launch_prepare_cfg0(const DModel* m, const DBatch* b, int nblocks, int reset_only, hipStream_t stream);
 extern "C" int rsim_cmem_bytes_cfg0(void);
@@ -182,6 +188,9 @@ struct rsim_batch {
   // block and takes its reset observation inside k_step (RF_RESET_INKERNEL) -- no k_prepare(reset_only) / k_reset_obs launch on the step's serial chain.
   // RSIM_SEPARATE_RESET_PASS=1 when the batch is created keeps the two launches (the reference of tests/test_reset_pass_fused.py and of A/B runs).
   int separate_reset;
+  // RSIM_FULL_STEP_KERNEL=1 when the batch is created: every control step runs k_full_step (the reference of tests/test_plain_step_kernel.py and of A/B runs)
+  int full_step;
+  unsigned long long n_plain, n_full;   // launches of k_step / k_full_step since the batch was created (rsim_step_kernel_launches; configurations 0-2)
   int tier_flip;
   // TIER_LIST only
   int share_cm;       // configuration 5 reads the NATIVE constant blocks: it differs from configuration 3 in contact / row capacity only, and the block layout
@@ -940,6 +949,7 @@ extern "C" int rsim_batch_create(rsim_model* m, int B, int device, int per_env, 
   // capacity tiers: only for controllers whose state lives in LDS for the whole launch (a step that is handed over must not have written anything);
   // RSIM_NO_TIERS: none, drops are then counted in RSIM_OVERFLOW (as before round 4)
   { const char* e = getenv("RSIM_SEPARATE_RESET_PASS"); b->separate_reset = (e && atoi(e) != 0) ? 1 : 0; }
+  { const char* e = getenv("RSIM_FULL_STEP_KERNEL"); b->full_step = (e && atoi(e) != 0) ? 1 : 0; }
   b->tier = TIER_NONE;
   if (b->cs <= RSIM_CS_LDS && !getenv("RSIM_NO_TIERS") && b->cfg <= 3) {
     int lw[10];
@@ -1303,6 +1313,17 @@ static int sensors_launch(rsim_batch* b, int stages, bool pre) {
   return 0;
 }
 
+// The one place a step kernel is launched.  Configurations 0-2: the plain k_step, unless this launch needs what only k_full_step compiles in -- the profiler
+// armed (rsim_profile), the MPR restart cone on (RSIM_MPR_CONE), applied forces enabled (RF_APPLIED) -- or the batch asked for the full form.  The debug form
+// (RF_DEBUG: k_step_dbg) and configurations 3-4 have one kernel.
+static int step_launch(rsim_batch* b, const DBatch* db, const float* actions, int n_sub, int flags, hipStream_t stream) {
+  if (b->cfg <= 2 && !(flags & RF_DEBUG)) {
+    if (b->db.prof || b->dm.mpr_cone > 0.f || (flags & RF_APPLIED) || b->full_step) { b->n_full++; return k_full_step_launch[b->cfg](&b->dm, db, actions, n_sub, flags, stream); }
+    b->n_plain++;
+  }
+  return k_step_launch[b->cfg](&b->dm, db, actions, n_sub, flags, stream);
+}
+
 static int launch(rsim_batch* b, const float* actions, int n_sub, int flags) {
   const int WCN = 2 + 2 * RSIM_MAX_GROUPS;   // list lengths per step parity
   HIPCHK(hipSetDevice(b->device));
@@ -1360,7 +1381,7 @@ static int launch(rsim_batch* b, const float* actions, int n_sub, int flags) {
         if (el) return fail("tier-list kernel launch failed: %s", hipGetErrorString((hipError_t)el));
         db.wlist2 = b->d_wlist[1] + e0; db.wcount2 = cnt + 1;
       }
-      int e = k_step_launch[b->cfg](&b->dm, &db, actions, n_sub, flags, b->gstream[g]);
+      int e = step_launch(b, &db, actions, n_sub, flags, b->gstream[g]);
       if (e) return fail("kernel launch failed: %s", hipGetErrorString((hipError_t)e));
       if (listed) {
         int* cnt = b->d_wcount + b->tier_flip * WCN + 2 + 2 * g;
@@ -1422,7 +1443,7 @@ static int launch(rsim_batch* b, const float* actions, int n_sub, int flags) {
   const bool sensors = (flags & RF_DEBUG) && b->d_sens_i && b->db.sensordata;   // (a model without a sensor of the further types launches nothing extra)
   const bool sens_pre = sensors && (flags & RF_INTEGRATE);
   if (sens_pre && sensors_keep_state(b)) return 1;
-  int e = k_step_launch[b->cfg](&b->dm, &b->db, actions, n_sub, flags, b->stream);
+  int e = step_launch(b, &b->db, actions, n_sub, flags, b->stream);
   if (e) return fail("kernel launch failed: %s", hipGetErrorString((hipError_t)e));
   if (sensors && sensors_launch(b, RS_STAGE_POS | RS_STAGE_VEL | ((flags & RF_ACTSOLVE) ? RS_STAGE_ACC : 0), sens_pre)) return 1;
   if (traced) tr_mark(b, 3);
@@ -1808,11 +1829,27 @@ extern "C" const char* rsim_tuning_defaults(void) {
   s = buf;
   static const char* const envs[] = {"RSIM_NEWTON_NS", "RSIM_NEWTON_NA", "RSIM_NEWTON_LS", "RSIM_NEWTON_NG", "RSIM_NEWTON_WIDE", "RSIM_NEWTON_EXACT", "RSIM_NEWTON_REFINE",
                                      "RSIM_POLISH_TOL", "RSIM_POLISH_GATE", "RSIM_BP_REACH", "RSIM_NEAR_THRESH", "RSIM_NEAR_GAIN", "RSIM_MPR_CONE", "RSIM_NO_MPR_WARMSTART", "RSIM_NO_MPR_PORTAL_WARMSTART",
-                                     "RSIM_TIER_UP_CON", "RSIM_TIER_UP_EFC", "RSIM_NO_TIERS", "RSIM_NO_SHARE_CM", "RSIM_EULER_FULL", "RSIM_FORCE_HANDOVER"};
+                                     "RSIM_TIER_UP_CON", "RSIM_TIER_UP_EFC", "RSIM_NO_TIERS", "RSIM_NO_SHARE_CM", "RSIM_EULER_FULL", "RSIM_FORCE_HANDOVER", "RSIM_FULL_STEP_KERNEL"};
   for (const char* e : envs) if (const char* v = getenv(e)) { s += ";env:"; s += e; s += "="; s += v; }
   // (early episode end, rsim_set_early_end, is not listed: it is a per-batch switch that is off unless a caller arms it -- not a default of the library, and nothing
   // bench.py measures runs with it; a measurement that arms it says so itself: tools/early_end_ab.py)
   return s.c_str();
+}
+// {launches of the plain k_step, launches of k_full_step} since the batch was created; both 0 for configurations 3-4, which have one kernel
+extern "C" int rsim_step_kernel_launches(rsim_batch* b, unsigned long long* out2) {
+  if (!out2) return fail("rsim_step_kernel_launches: null destination");
+  out2[0] = b->n_plain; out2[1] = b->n_full;
+  return 0;
+}
+// the narrow phase's warm-start records as the last launch left them, host float32 [B][npair][12] (rsim_step.hip Sim::MPRC); synchronises the batch's stream(s)
+extern "C" int rsim_mpr_records(rsim_batch* b, float* host_out) {
+  if (!host_out) return fail("rsim_mpr_records: null destination");
+  if (!b->db.mprc) return fail("rsim_mpr_records: the batch keeps no warm-start records (RSIM_NO_MPR_WARMSTART, or a model without geom pairs)");
+  HIPCHK(hipSetDevice(b->device));
+  if (join_groups(b)) return 1;
+  HIPCHK(hipStreamSynchronize(b->stream));
+  HIPCHK(hipMemcpy(host_out, b->db.mprc, (size_t)b->B * b->m->npair * 12 * sizeof(float), hipMemcpyDeviceToHost));
+  return 0;
 }
 // {env-steps the wider capacity tier stepped, env-steps of these that were handed over (TIER_FUSED) / redone (TIER_LIST) in mid-step} since the batch was created
 extern "C" int rsim_tier_stats(rsim_batch* b, unsigned long long* out2) {

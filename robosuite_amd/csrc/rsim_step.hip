@@ -224,7 +224,8 @@ __device__ __forceinline__ int uni(int x) { return __builtin_amdgcn_readfirstlan
 __device__ __forceinline__ u64 lanemask_lt(int lane) { return (1ull << lane) - 1ull; }
 
 // optional per-phase cycle accounting (DBatch.prof != null): lane 0 accumulates s_memtime deltas and event counters
-struct Prof {
+template <bool ON>
+struct ProfT {
   unsigned long long* p;
   unsigned long long* pairs = nullptr;   // per-pair {visits, supports} counters
   long long t0;
@@ -241,6 +242,16 @@ struct Prof {
       if (lane == 0 && acc) atomicAdd(p + id, (unsigned long long)v);
     }
   }
+};
+// the plain control-step kernel (Sim<SM, true>) carries no profiler: nothing to test at a mark, no counter live across the substep loop
+template <>
+struct ProfT<false> {
+  static constexpr unsigned long long* pairs = nullptr;
+  static constexpr int c_mpr = 0, c_support = 0, c_newton = 0, c_cand = 0;
+  static constexpr bool acc = false;
+  __device__ __forceinline__ void start() {}
+  __device__ __forceinline__ void mark(int) {}
+  __device__ __forceinline__ void count(int, int) {}
 };
 
 // ------------------------------------------------------------------------------------------------------------
@@ -1053,7 +1064,9 @@ struct LaneConst {
 // ------------------------------------------------------------------------------------------------------------
 // the simulator (all methods are wave-cooperative: every lane of the env's wavefront calls them)
 // ------------------------------------------------------------------------------------------------------------
-template <class SM>
+// PLAIN: the control step as a default launch runs it (k_step of the fused-tier builds): no profiler, no MPR restart cone, no applied forces.  The host
+// launches the full form (k_full_step) whenever one of the three is in use (rsim_api.cpp step_launch()).
+template <class SM, bool PLAIN = false>
 struct Sim {
   const DModel& m;
   const float* fp;
@@ -1107,7 +1120,7 @@ struct Sim {
   float __attribute__((address_space(1)))* mprc = nullptr;  // this env's narrow-phase warm-start record [npair][MPRC] in global memory (DBatch.mprc), or null
   bool mpr_portal = true;                                   // contacts leave their portal directions in the record (flag 2)
   float __attribute__((address_space(1)))* cst = nullptr;   // this env's controller-state record in global memory (slots >= RSIM_CS_LDS are used in place)
-  Prof pf;
+  ProfT<!PLAIN> pf;
   int ovf = 0;   // contacts / constraint rows this launch had to drop for lack of capacity (RSIM_OVERFLOW); MuJoCo's nconmax = 5000 never truncates
   float near_sep = 3.0e38f;   // smallest separation (m) along a separating direction any convex pair of the LAST substep's narrow phase ended on: how close the env is to a
                               // contact that does not exist yet (step_body: dispatch-order hint, DModel.near_thresh)
@@ -1134,13 +1147,13 @@ struct Sim {
   }
   static constexpr int NT = SM::NV_ / 16;       // 16-dof tiles per dimension of the dense nv x nv products
 
-  __device__ Sim(const DModel& m_, const float* fp_, int lane_, unsigned long long* prof, const void* cm_, const void* ce_) : m(m_), fp(fp_), lane(lane_), cm((cmr_t)cm_), ce((cmr_t)ce_), fenv(m_.fenv), ceoff((const char*)ce_ - (const char*)cm_) { pf.p = prof; pf.lane = lane_; pf.t0 = 0; }
+  __device__ Sim(const DModel& m_, const float* fp_, int lane_, unsigned long long* prof, const void* cm_, const void* ce_) : m(m_), fp(fp_), lane(lane_), cm((cmr_t)cm_), ce((cmr_t)ce_), fenv(m_.fenv), ceoff((const char*)ce_ - (const char*)cm_) { if constexpr (!PLAIN) { pf.p = prof; pf.lane = lane_; pf.t0 = 0; } }
   // Phase boundary for the register allocator: everything derived from the lane id (LDS addresses lane * stride, role predicates lane < n as
   // 64-bit masks) is loop invariant, so the compiler hoists all of it out of the substep loop and keeps it alive across every phase -- some
   // hundred registers at the pressure peaks.  A fresh (opaque) lane id per phase confines those values to the phase that uses them.
   __device__ __forceinline__ void phase() {
 #ifndef RSIM_NO_PHASE_LANE
-    lane = opaque_lane(lane); pf.lane = lane;
+    lane = opaque_lane(lane); if constexpr (!PLAIN) pf.lane = lane;
 #endif
     // the same for the field-override mask: with a loop-invariant `fenv` every `bit ? env table : shared table` select of FP() -- some seventy
     // 64-bit pointers -- is computed before the substep loop and parked in spilled SGPRs (v_writelane / v_readlane) for the whole kernel
@@ -2202,7 +2215,7 @@ struct Sim {
       warm = dot(v1, d1) > 0.f && dot(v2, d2) > 0.f && dot(v3_, d3) > 0.f && dot(cross(v1, v3_), v0) >= 0.f && dot(cross(v3_, v2), v0) >= 0.f && dot(cross(v2, v1), v0) >= 0.f;
       MPRSTAT(9, warm ? 1 : 0);
     }
-    if (wh == 3) {
+    if (!PLAIN && wh == 3) {
       // A contact in which one shape is SMOOTH (cylinder, capsule, sphere, ellipsoid) persists like any other -- a finger or a link resting against the mount's
       // cylinder -- and is the expensive kind: the refinement gains one bit of the tolerance per step on a curved surface (the portal has to shrink to
       // sqrt(2 R tol), ~0.6 mm on the mount), 13 - 20 support pairs per run, every substep; such runs are 60 % of the slowest env of a Lift launch
@@ -2380,7 +2393,7 @@ struct Sim {
       const int ta = uni(sg1.t), tb = uni(sg2.t);
       const bool smooth_a = ta == G_CYLINDER || ta == G_CAPSULE || ta == G_SPHERE || ta == G_ELLIPSOID, smooth_b = tb == G_CYLINDER || tb == G_CAPSULE || tb == G_SPHERE || tb == G_ELLIPSOID;
       if (((ta == G_BOX && tb == G_MESH) || (ta == G_MESH && tb == G_BOX)) && depth < 5e-3f) mpr_store_portal(wout, depth);
-      else if ((smooth_a || smooth_b) && m.mpr_cone > 0.f && norm(dir) > 0.5f) mpr_store(wout, dot(dir, v1) >= 0.f ? dir : -dir, 3.f);   // the final portal's outward normal (flag 3 above)
+      else if (!PLAIN && (smooth_a || smooth_b) && m.mpr_cone > 0.f && norm(dir) > 0.5f) mpr_store(wout, dot(dir, v1) >= 0.f ? dir : -dir, 3.f);   // the final portal's outward normal (flag 3 above)
       else mpr_store(wout, v3(depth, 0.f, 0.f), 4.f);   // touched, this deep: the next visit may start its cold run at once (see the pretest)
     }
     V3 w1 = p11 * bw.x + p21 * bw.y + p31 * bw.z, w2 = p12 * bw.x + p22 * bw.y + p32 * bw.z;
@@ -2586,7 +2599,7 @@ struct Sim {
         convex_convex(g1, g2, t1, t2, uni(__builtin_amdgcn_readlane(D.gm1, src)), uni(__builtin_amdgcn_readlane(D.gm2, src)), margin, cp, wd, wh, mprc ? mprc + MPRC * p : nullptr);
         pf.mark(RP_MPR); pf.count(RP_N_MPR, 1);
       }
-      if (pf.pairs && lane == 0 && pf.acc) { atomicAdd(pf.pairs + p, 1ull); atomicAdd(pf.pairs + RSIM_PAIR_MAX + p, (unsigned long long)(pf.c_support - sup0)); }
+      if constexpr (!PLAIN) { if (pf.pairs && lane == 0 && pf.acc) { atomicAdd(pf.pairs + p, 1ull); atomicAdd(pf.pairs + RSIM_PAIR_MAX + p, (unsigned long long)(pf.c_support - sup0)); } }
       SYNC();
     }
   }
@@ -4473,7 +4486,7 @@ struct Handover { int sub0; float time; bool fresh_ctrl, handed; int ndiverged, 
 
 // FUSED: 0 = the kernel holds this body only; 1 = native body of a fused-tier kernel (returns true, with `ho` filled, when the env has to carry on in the wide
 // body); 2 = the wide body of such a kernel (ho->sub0 > 0: carries on from the native body's LDS state at that substep; 0: an env that was on the tier already)
-template <int NB, int NJ, int NV, int NG, int NS, int NCON, int NEFC, int NPAIR, bool DBG, int FUSED = 0>
+template <int NB, int NJ, int NV, int NG, int NS, int NCON, int NEFC, int NPAIR, bool DBG, int FUSED = 0, bool PLAIN = false>
 __device__ __forceinline__ bool step_body(const DModel& m, const DBatch& b, const float* __restrict__ actions, int n_sub, int flags, int slot, Handover* ho = nullptr) {
   typedef Smem<NB, NJ, NV, NG, NS, NCON, NEFC, NPAIR> SM;
   // the bodies of a fused-tier kernel sit in k_step's reset-pass loop: with the plain lane id everything derived from it in the prologue and the epilogue is
@@ -4498,11 +4511,14 @@ __device__ __forceinline__ bool step_body(const DModel& m, const DBatch& b, cons
   if (!FUSED && tpass == 0 && b.tier_cur[env] != 0) return false;    // stepped by the wide configuration in this control step (fused kernels: k_step picks the body)
   const unsigned t_launch = resume ? ho->t_launch : ((b.cost && !reentry) ? (unsigned)uni((int)(clock64() >> 6)) : 0u);   // 64-tick units, scalar
   const float* fp = m.ft + (size_t)env * m.fstride;
-  Sim<SM> sim(m, fp, lane, b.prof, b.cm, b.cm_stride ? (const char*)b.cm_env + (size_t)env * b.cm_stride : (const char*)b.cm);
-  sim.pf.acc = b.prof_env == -1 || b.prof_env == env;   // -1: every env, -2: none (undistorted wave log)
-  if (b.prof) sim.pf.pairs = b.prof + RP_COUNT + 8 * (size_t)b.B;
+  typedef Sim<SM, PLAIN> SimT;   // PLAIN (k_step of a fused-tier build): no profiler, no restart cone, no applied forces -- the host launches k_full_step for those
+  SimT sim(m, fp, lane, PLAIN ? nullptr : b.prof, b.cm, b.cm_stride ? (const char*)b.cm_env + (size_t)env * b.cm_stride : (const char*)b.cm);
+  if constexpr (!PLAIN) {
+    sim.pf.acc = b.prof_env == -1 || b.prof_env == env;   // -1: every env, -2: none (undistorted wave log)
+    if (b.prof) sim.pf.pairs = b.prof + RP_COUNT + 8 * (size_t)b.B;
+  }
   sim.pf.start();
-  if (b.prof && lane == 0 && !resume) {
+  if (!PLAIN && b.prof && lane == 0 && !resume) {
     unsigned long long* wl = b.prof + RP_COUNT + 8 * (size_t)env;
     wl[0] = (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4);    // HW_REG_HW_ID
     wl[1] = (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 20);   // HW_REG_XCC_ID
@@ -4518,16 +4534,16 @@ __device__ __forceinline__ bool step_body(const DModel& m, const DBatch& b, cons
   const int cs = m.ctrl.cs_size, csl = cs < RSIM_CS_LDS ? cs : RSIM_CS_LDS;
   sim.cst = (gwf)(b.cstate + (size_t)env * cs);
   if (b.bpl) sim.bpl = (int __attribute__((address_space(1)))*)(b.bpl + (size_t)env * 320);
-  if (b.mprc) { sim.mprc = (gwf)(b.mprc + (size_t)env * Sim<SM>::MPRC * m.npair); sim.mpr_portal = b.mprc_portal != 0; }
-  if constexpr (Sim<SM>::JG) sim.Jg = (gwf)(b.jg + (size_t)env * b.jg_stride);   // one stride for every configuration that steps envs of this batch (the native and the wide pass run side by side)
-  if constexpr (Sim<SM>::MG) sim.Mg = sim.Jg + SM::NEFC_ * SM::JS_;
+  if (b.mprc) { sim.mprc = (gwf)(b.mprc + (size_t)env * SimT::MPRC * m.npair); sim.mpr_portal = b.mprc_portal != 0; }
+  if constexpr (SimT::JG) sim.Jg = (gwf)(b.jg + (size_t)env * b.jg_stride);   // one stride for every configuration that steps envs of this batch (the native and the wide pass run side by side)
+  if constexpr (SimT::MG) sim.Mg = sim.Jg + SM::NEFC_ * SM::JS_;
   if (lane < csl) sm.cstate[lane] = resume ? ho->cstate : sim.cst[lane];
   // external forces, mjData.qfrc_applied / xfrc_applied: read by the debug form always (the B = 1 shim entries: GripperTester's gravity compensation), by the
   // control step when the batch enabled them (rsim_set_applied_forces -> RF_APPLIED, a kernel argument).  One lane per body tests its wrench once per launch;
   // the ballot (an SGPR pair) is what the substeps loop over.  An env handed to the wide body in mid-step tests again there: the same rows, unchanged within a launch.
   gcf qfa = nullptr, xfa = nullptr;
   u64 xmask = 0;
-  if (DBG || (flags & RF_APPLIED)) {
+  if (!PLAIN && (DBG || (flags & RF_APPLIED))) {
     if (b.qfrc_applied) qfa = (gcf)(b.qfrc_applied + (size_t)env * m.nv);
     if (b.xfrc_applied) {
       xfa = (gcf)(b.xfrc_applied + (size_t)env * m.nbody * 6);
@@ -4596,7 +4612,7 @@ __device__ __forceinline__ bool step_body(const DModel& m, const DBatch& b, cons
     }
     if (flags & RF_ACTSOLVE) {
       sim.phase();
-      sim.actuation_acceleration(qfa, xfa, xmask);
+      if constexpr (PLAIN) sim.actuation_acceleration(); else sim.actuation_acceleration(qfa, xfa, xmask);
       sim.pf.mark(RP_ACT);
       sim.phase();
       sim.fwd_constraint();
@@ -4686,11 +4702,11 @@ __device__ __forceinline__ bool step_body(const DModel& m, const DBatch& b, cons
       }
       time = 0.f;
       st = 0;
-      if (sim.mprc) for (int p2 = lane; p2 < m.npair; p2 += 64) sim.mprc[Sim<SM>::MPRC * p2 + 3] = 0.f;   // the new episode's narrow phase starts cold, as after a host reset
+      if (sim.mprc) for (int p2 = lane; p2 < m.npair; p2 += 64) sim.mprc[SimT::MPRC * p2 + 3] = 0.f;   // the new episode's narrow phase starts cold, as after a host reset
       // mj_resetData: the new episode starts without external forces, wherever they are read -- the control step with the switch on, the debug form (the
       // host-controller path, rsim_step2_last) always; a wrench the caller writes after seeing `done` acts on it.  With the switch off the control step
       // neither reads nor writes them.
-      if (DBG || (flags & RF_APPLIED)) {
+      if (!PLAIN && (DBG || (flags & RF_APPLIED))) {
         for (int i = lane; i < m.nv; i += 64) b.qfrc_applied[(size_t)env * m.nv + i] = 0.f;
         for (int i = lane; i < m.nbody * 6; i += 64) b.xfrc_applied[(size_t)env * m.nbody * 6 + i] = 0.f;
       }
@@ -4720,7 +4736,7 @@ __device__ __forceinline__ bool step_body(const DModel& m, const DBatch& b, cons
     if (sim.near_sep < m.near_thresh) cst += (unsigned)((float)cst * m.near_gain);
     b.cost[env] = cst;
   }
-  if (b.prof && lane == 0) {
+  if (!PLAIN && b.prof && lane == 0) {
     unsigned long long* wl = b.prof + RP_COUNT + 8 * (size_t)env;
     wl[3] = wall_clock64(); wl[4] = sim.pf.c_mpr; wl[5] = sim.pf.c_support; wl[6] = sim.pf.c_newton; wl[7] = sim.pf.c_cand;
   }
@@ -4758,9 +4774,13 @@ __device__ __forceinline__ bool step_body(const DModel& m, const DBatch& b, cons
 #else
 #define RSIM_KSTEP_ATTR
 #endif
-template <int NB, int NJ, int NV, int NG, int NS, int NCON, int NEFC, int NPAIR>
-__global__ RSIM_KSTEP_ATTR __launch_bounds__(64, RSIM_MINWAVES) void k_step(DModel m, DBatch b, const float* __restrict__ actions, int n_sub, int flags) {
 #ifdef RSIM_DIMS_W
+// The control step of a fused-tier build, compiled twice: PLAIN for k_step -- what a default launch runs -- and in full for k_full_step, which the host launches
+// while the profiler is armed, the MPR restart cone is on or the batch enabled applied forces (rsim_api.cpp step_launch()).  The three are run-time switches of
+// the full form; compiled into the one kernel they cost every default launch their tests, branches and live state: cfg 0 -10 % instructions, -19 % branches,
+// 561 -> 444 spilled SGPRs (profiles/plain_step_kernel_ab.txt).  Same arithmetic, same control flow: the two forms agree bit for bit (tests/test_plain_step_kernel.py).
+template <int NB, int NJ, int NV, int NG, int NS, int NCON, int NEFC, int NPAIR, bool PLAIN>
+__device__ __forceinline__ void fused_step(const float* __restrict__ actions, int n_sub, int flags) {
   // fused-tier kernel: the workgroup steps its env with the native body; an env that is on the wide tier already (DBatch.tier_cur) or outgrows the native
   // capacity in mid-step (step_body returns true) is stepped / carried on by the wide body in this same workgroup.  No list, no second launch: the envs that
   // need the tier are the slowest of a control step, and a kernel of their own could not start before the native launch had drained.
@@ -4791,14 +4811,14 @@ __global__ RSIM_KSTEP_ATTR __launch_bounds__(64, RSIM_MINWAVES) void k_step(DMod
   for (;;) {
     bool over = wide;
     if (!wide) {
-      over = uni(step_body<NB, NJ, NV, NG, NS, NCON, NEFC, NPAIR, false, 1>(m, b, act, nsub, fl, slot, &ho) ? 1 : 0) != 0;
+      over = uni(step_body<NB, NJ, NV, NG, NS, NCON, NEFC, NPAIR, false, 1, PLAIN>(m, b, act, nsub, fl, slot, &ho) ? 1 : 0) != 0;
       if (over) {
         // wave-uniform by construction; said so explicitly (the compiler sees them leave a branch on a vector condition)
         ho.sub0 = uni(ho.sub0); ho.time = __builtin_bit_cast(float, uni(__builtin_bit_cast(int, ho.time))); ho.fresh_ctrl = uni(ho.fresh_ctrl ? 1 : 0) != 0; ho.handed = true;
         ho.ndiverged = uni(ho.ndiverged); ho.need_con = uni(ho.need_con); ho.need_efc = uni(ho.need_efc); ho.t_launch = (unsigned)uni((int)ho.t_launch);
       }
     }
-    if (over) step_body<RSIM_DIMS_W, false, 2>(m, b, act, nsub, fl, slot, &ho);
+    if (over) step_body<RSIM_DIMS_W, false, 2, PLAIN>(m, b, act, nsub, fl, slot, &ho);
     if (!(fl & RF_RESET_INKERNEL) || !uni(ho.restarted ? 1 : 0)) return;
     // the step's stores (state, patched float-table entries, cleared warm-start words, needs_reset) before the loads of the rebuild and of the pass: the
     // vector L1 is invalidated by the acquire, the scalar cache -- which the memory model leaves out -- by hand
@@ -4807,7 +4827,7 @@ __global__ RSIM_KSTEP_ATTR __launch_bounds__(64, RSIM_MINWAVES) void k_step(DMod
     if (b.cm_stride != 0 && b.bank_P > 0) {
       const int env = uni((b.order ? b.order[slot] : slot) + b.env0);
       char* const cmb = (char*)b.cm_env + (size_t)env * b.cm_stride;
-      Sim<Smem<NB, NJ, NV, NG, NS, NCON, NEFC, NPAIR>> ps(m, m.ft + (size_t)env * m.fstride, opaque_lane((int)threadIdx.x), nullptr, cmb, cmb);
+      Sim<Smem<NB, NJ, NV, NG, NS, NCON, NEFC, NPAIR>, PLAIN> ps(m, m.ft + (size_t)env * m.fstride, opaque_lane((int)threadIdx.x), nullptr, cmb, cmb);
       ps.prepare_constants((cmw_t)cmb);
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
       __builtin_amdgcn_s_dcache_inv();
@@ -4817,10 +4837,24 @@ __global__ RSIM_KSTEP_ATTR __launch_bounds__(64, RSIM_MINWAVES) void k_step(DMod
   }
 #undef m
 #undef b
+}
+#endif
+template <int NB, int NJ, int NV, int NG, int NS, int NCON, int NEFC, int NPAIR>
+__global__ RSIM_KSTEP_ATTR __launch_bounds__(64, RSIM_MINWAVES) void k_step(DModel m, DBatch b, const float* __restrict__ actions, int n_sub, int flags) {
+#ifdef RSIM_DIMS_W
+  fused_step<NB, NJ, NV, NG, NS, NCON, NEFC, NPAIR, true>(actions, n_sub, flags);
 #else
   step_body<NB, NJ, NV, NG, NS, NCON, NEFC, NPAIR, false>(m, b, actions, n_sub, flags, (int)blockIdx.x);
 #endif
 }
+#ifdef RSIM_DIMS_W
+// the same step with everything behind its run-time switches (profiler, restart cone, applied forces): today's reference of the plain form, and what the
+// profiling tools run on
+template <int NB, int NJ, int NV, int NG, int NS, int NCON, int NEFC, int NPAIR>
+__global__ RSIM_KSTEP_ATTR __launch_bounds__(64, RSIM_MINWAVES) void k_full_step(DModel m, DBatch b, const float* __restrict__ actions, int n_sub, int flags) {
+  fused_step<NB, NJ, NV, NG, NS, NCON, NEFC, NPAIR, false>(actions, n_sub, flags);
+}
+#endif
 // The same control step as the upper capacity tier of a batch whose model belongs to a narrower configuration: a fixed, small grid walks the list
 // of envs this pass steps (DBatch.wlist / wcount, filled on the device), so a control step in which no env needs the tier costs one empty launch.
 template <int NB, int NJ, int NV, int NG, int NS, int NCON, int NEFC, int NPAIR>
@@ -5026,6 +5060,13 @@ extern "C" int RSIM_SYM(rsim_limits_w)(int* lim) {
 // explicit instantiations + launchers (one set per configuration build) ----------------------------------------------------------
 template __global__ void k_step<RSIM_DIMS>(DModel, DBatch, const float*, int, int);
 template __global__ void k_step_dbg<RSIM_DIMS>(DModel, DBatch, const float*, int, int);
+#ifdef RSIM_DIMS_W
+template __global__ void k_full_step<RSIM_DIMS>(DModel, DBatch, const float*, int, int);
+extern "C" int RSIM_SYM(rsim_launch_full_step)(const DModel* m, const DBatch* b, const float* actions, int n_sub, int flags, hipStream_t stream) {
+  hipLaunchKernelGGL((k_full_step<RSIM_DIMS>), dim3(b->nenv ? b->nenv : b->B), dim3(64), 0, stream, *m, *b, actions, n_sub, flags);
+  return (int)hipGetLastError();
+}
+#endif
 #if RSIM_CFG == 5   // the list-walking form of the tier above configuration 3 (rsim_api.cpp launch(): TIER_LIST)
 template __global__ void k_step_list<RSIM_DIMS>(DModel, DBatch, const float*, int, int);
 extern "C" int RSIM_SYM(rsim_launch_step_list)(const DModel* m, const DBatch* b, const float* actions, int n_sub, int flags, int grid, hipStream_t stream) {
