@@ -334,11 +334,11 @@ extern "C" int rsim_model_create(const void* blob, size_t len, rsim_model** out)
     for (int b = 0; b < nb && b < 64; b++) {
       int p0 = parent[b];
       auto jump = [&](int x, int times) { for (int t = 0; t < times; t++) x = parent[x]; return x; };
-      int pr[5];
-      for (int r = 0; r < 5; r++) pr[r] = jump(b, 1 << r);
+      int pr[6];
+      for (int r = 0; r < 6; r++) pr[r] = jump(b, 1 << r);
       (void)p0;
       LT(LT_part, b) = pr[0] | (pr[1] << 8) | (pr[2] << 16) | (pr[3] << 24);
-      LT(LT_part4, b) = pr[4];
+      LT(LT_part4, b) = pr[4] | (pr[5] << 8);   // pr[5] != 0 only in trees deeper than 32: the 32-body builds read the word whole
       int jt = 15, qa = 0, da = 0;
       if (jnum[b] >= 1) { jt = jtype[jadr[b]]; qa = m->I("jnt_qposadr")[jadr[b]]; da = jdof[jadr[b]]; }
       if (jnum[b] > 1) m->multijoint = 1;
@@ -804,6 +804,9 @@ static int dalloc(T** p, size_t n) {
 static bool config_holds(const rsim_model* m, const int* lim) {
   const int ncg = (int)m->cg.size();
   const bool tendons = m->ntendon > 0 || m->neq > 0;
+  bool ball = false;   // ball joints: only the builds that compile them in (limits bit 6)
+  for (int j = 0; j < m->njnt; j++) ball |= m->I("jnt_type")[j] == 1;
+  if (ball && !(lim[9] & 64)) return false;
   return !(m->nbody > lim[0] || m->njnt > lim[1] || m->nv > lim[2] || m->nq > lim[2] + 8 || m->nu > 16 || ncg > lim[3] || m->nsite > lim[4] || m->npair > lim[7] ||
            m->ndynroot > lim[8] || (tendons && !(lim[9] & 1)) || (m->ctrl.enabled && m->ctrl.narm == 2 && !(lim[9] & 2)));
 }
@@ -854,6 +857,17 @@ extern "C" int rsim_batch_create(rsim_model* m, int B, int device, int per_env, 
   b->cfg = pick_config(m, b->lim);
   if (b->cfg < 0) {
     int lim[10];
+    bool ball = false;
+    for (int j = 0; j < m->njnt; j++) ball |= m->I("jnt_type")[j] == 1;
+    for (int c = 0; ball && c < RSIM_NCFG; c++) {   // a model with ball joints: say what the builds that carry them hold
+      k_limits[c](lim);
+      if (!(lim[9] & 64)) continue;
+      int r = fail("rsim_batch_create: model with ball joints (nbody %d njnt %d nv %d nq %d nu %d ncgeom %d nsite %d npair %d, %d articulated trees) exceeds the kernel configuration that carries "
+                   "ball joints (nbody %d njnt %d nv %d nq %d nu 16 ncgeom %d nsite %d npair %d, %d trees%s)", m->nbody, m->njnt, m->nv, m->nq, m->nu, ncg, m->nsite, m->npair, m->ndynroot,
+                   lim[0], lim[1], lim[2], lim[2] + 8, lim[3], lim[4], lim[7], lim[8], (lim[9] & 2) ? "" : ", one arm part");
+      delete b;
+      return r;
+    }
     k_limits[RSIM_NCFG - 1](lim);
     int r = fail("rsim_batch_create: model (nbody %d njnt %d nv %d ncgeom %d nsite %d npair %d, %d articulated trees) exceeds the largest compiled kernel configuration "
                  "(%d %d %d %d %d .. %d, %d trees)", m->nbody, m->njnt, m->nv, ncg, m->nsite, m->npair, m->ndynroot, lim[0], lim[1], lim[2], lim[3], lim[4], lim[7], lim[8]);
@@ -934,7 +948,7 @@ extern "C" int rsim_batch_create(rsim_model* m, int B, int device, int per_env, 
   }
 
   if (m->maxcondim > 4) { int r = fail("rsim_batch_create: condim %d contacts are not supported by the compiled kernel configuration (max 4)", m->maxcondim); delete b; return r; }
-  for (int j = 0; j < m->njnt; j++) if (m->I("jnt_type")[j] == 1) { int r = fail("rsim_batch_create: ball joints are not supported by the fused kernel"); delete b; return r; }
+  for (int j = 0; j < m->njnt; j++) if (m->I("jnt_type")[j] == 1 && m->I("jnt_limited")[j]) { int r = fail("rsim_batch_create: joint %d: limited ball joints are not supported (no limit rows for them in the fused kernel)", j); delete b; return r; }
   if (dalloc(&b->d_lt, m->lanetab.size())) return 1;
   HIPCHK(hipMemcpy(b->d_lt, m->lanetab.data(), m->lanetab.size() * sizeof(int), hipMemcpyHostToDevice));
   dm.lt = b->d_lt; dm.kin_rounds = m->kin_rounds; dm.ndynroot = m->ndynroot; dm.maxcondim = m->maxcondim;

@@ -38,7 +38,7 @@ enum {
 // ---- per-lane packed int constants ("lane table", 64 ints per row): what lane l needs in each of its roles --------------
 enum {
   LT_part,   /* body b = lane: pointer-jump partners of kinematics rounds 0..3 (8 bits each) */
-  LT_part4,  /* round-4 partner (trees deeper than 16) */
+  LT_part4,  /* round-4 partner (trees deeper than 16), bits 8-15: round-5 partner (deeper than 32; 64-body builds) */
   LT_binfo,  /* body: jtype(4b, 15 = no joint) | qposadr<<4 | dofadr<<12 | rootid<<20 | moving<<28 */
   LT_bdofs,  /* body: bit k set if dof k moves the body */
   LT_dinfo,  /* dof i = lane: body | zerodot<<8 | limited<<9 | qposadr<<10 | jntid<<18 | jtype<<26 */

@@ -137,6 +137,12 @@ typedef unsigned long long u64;
 #define PI_F 3.14159265358979f
 
 enum { JNT_FREE = 0, JNT_BALL = 1, JNT_SLIDE = 2, JNT_HINGE = 3 };
+// ball joints (frames, motion axes, quaternion integration; no limit rows): compiled into the builds made with -DRSIM_BALL (limits bit 6), refused by the others
+#ifdef RSIM_BALL
+#define RSIM_BALL_ENABLED 1
+#else
+#define RSIM_BALL_ENABLED 0
+#endif
 enum { G_PLANE = 0, G_HFIELD, G_SPHERE, G_CAPSULE, G_ELLIPSOID, G_CYLINDER, G_BOX, G_MESH };
 enum { C_FRICTION_DOF = 0, C_LIMIT_JOINT = 1, C_CONTACT_FRICTIONLESS = 2, C_CONTACT_ELLIPTIC = 3,
        C_EQUALITY = 4 /* equality/tendon: bilateral, always quadratic */, C_LIMIT_TENDON = 5 /* limit on a fixed tendon's length */,
@@ -1403,12 +1409,20 @@ struct Sim {
     } else if (jt == JNT_SLIDE) {
       lp = K.bpos + qrot(K.bquat, K.jaxis) * (sm.qpos[qa] - K.q0);
     }
+#if RSIM_BALL_ENABLED
+    else if (jt == JNT_BALL) {
+      lq = qmul(K.bquat, qnorm(ldq(sm.qpos + qa)));
+      lp = K.bpos + qrot(K.bquat, K.jpos) - qrot(lq, K.jpos);
+    }
+#endif
     if (b == 0) { lp = v3(0, 0, 0); lq.w = 1.f; lq.x = lq.y = lq.z = 0.f; }
     SUBMARK_U(RP_X4);
     for (int r = 0; r < m.kin_rounds; r++) {
       if (b < SM_NB) { st3(sm.xpos + 3 * b, lp); stq(sm.xquat + 4 * b, lq); }
       SYNC();
-      const int p = r < 4 ? (K.part >> (8 * r)) & 255 : K.part4;
+      int p;
+      if constexpr (SM_NB > 32) p = r < 4 ? (K.part >> (8 * r)) & 255 : (K.part4 >> (8 * (r - 4))) & 255;   // 64 bodies: trees deeper than 32, a sixth round
+      else p = r < 4 ? (K.part >> (8 * r)) & 255 : K.part4;
       const V3 pp = ld3(sm.xpos + 3 * p);
       const Q4 pq = ldq(sm.xquat + 4 * p);
       SYNC();
@@ -1495,7 +1509,14 @@ struct Sim {
           const V3 ax = col(R, k);
           st3(cd + CS6 * (3 + k), ax); st3(cd + CS6 * (3 + k) + 3, cross(ax, off));
         }
-      } else {
+      }
+#if RSIM_BALL_ENABLED
+      else if (jt == JNT_BALL) {   // the body's own axes about the anchor
+        const V3 off = com - (xp + mv(R, K.jpos));
+        for (int k = 0; k < 3; k++) { const V3 ax = col(R, k); st3(cd + CS6 * k, ax); st3(cd + CS6 * k + 3, cross(ax, off)); }
+      }
+#endif
+      else {
         const V3 ax = mv(R, K.jaxis);
         if (jt == JNT_SLIDE) { st3(cd, v3(0, 0, 0)); st3(cd + 3, ax); }
         else { const V3 off = com - (xp + mv(R, K.jpos)); st3(cd, ax); st3(cd + 3, cross(ax, off)); }
@@ -3092,7 +3113,21 @@ struct Sim {
           const Q4 dq = {cs, w.x * k, w.y * k, w.z * k};
           stq(sm.qpos + pa + 3, qnorm(qmul(ldq(sm.qpos + pa + 3), dq)));
         }
-      } else sm.qpos[pa] += h * sm.qvel[da];
+      }
+#if RSIM_BALL_ENABLED
+      else if (jt == JNT_BALL) {
+        const V3 w = ld3(sm.qvel + da);
+        const float wn = norm(w), ang = wn * h;
+        if (ang > 1e-15f) {
+          float sn, cs;
+          sincos_f(0.5f * ang, sn, cs);
+          const float k = sn / wn;
+          const Q4 dq = {cs, w.x * k, w.y * k, w.z * k};
+          stq(sm.qpos + pa, qnorm(qmul(ldq(sm.qpos + pa), dq)));
+        }
+      }
+#endif
+      else sm.qpos[pa] += h * sm.qvel[da];
     }
     SYNC();
   }
@@ -5052,7 +5087,7 @@ extern "C" int rsim_launch_order(const unsigned* cost, int* order, int B, hipStr
 extern "C" int RSIM_SYM(rsim_limits_w)(int* lim) {
   const int dims[8] = {RSIM_DIMS_W};
   for (int i = 0; i < 8; i++) lim[i] = dims[i];
-  lim[8] = SmemW::NROOT_; lim[9] = (SmemW::TENDONS_ ? 1 : 0) | (SmemW::NB_ > 32 ? 2 : 0) | (SmemW::JG_ ? 4 : 0) | (SmemW::MG_ ? 8 : 0) | (SmemW::CG_ ? 16 : 0) | 32;
+  lim[8] = SmemW::NROOT_; lim[9] = (SmemW::TENDONS_ ? 1 : 0) | (SmemW::NB_ > 32 ? 2 : 0) | (SmemW::JG_ ? 4 : 0) | (SmemW::MG_ ? 8 : 0) | (SmemW::CG_ ? 16 : 0) | 32 | (RSIM_BALL_ENABLED ? 64 : 0);
   static_assert(sizeof(Cmem<RSIM_DIMS_W>) == sizeof(Cmem0), "the wide body reads the native configuration's constant blocks");
   return 1;
 }
@@ -5100,6 +5135,6 @@ extern "C" int RSIM_SYM(rsim_cmem_bytes)(void) { return (int)((sizeof(Cmem0) + 2
 extern "C" int RSIM_SYM(rsim_limits)(int* lim) {
   const int dims[8] = {RSIM_DIMS};
   for (int i = 0; i < 8; i++) lim[i] = dims[i];
-  lim[8] = Smem0::NROOT_; lim[9] = (Smem0::TENDONS_ ? 1 : 0) | (Smem0::NB_ > 32 ? 2 : 0) | (Smem0::JG_ ? 4 : 0) | (Smem0::MG_ ? 8 : 0) | (Smem0::CG_ ? 16 : 0) | (RSIM_FUSED_ENABLED ? 32 : 0);   // bit 5: the capacity tier above this configuration is compiled into its control-step kernel (rsim_limits_w)   // bit 2: the constraint Jacobian lives in DBatch.jg (NEFC * (NV + 1) floats per env)   // bit 1: two OSC arm parts
+  lim[8] = Smem0::NROOT_; lim[9] = (Smem0::TENDONS_ ? 1 : 0) | (Smem0::NB_ > 32 ? 2 : 0) | (Smem0::JG_ ? 4 : 0) | (Smem0::MG_ ? 8 : 0) | (Smem0::CG_ ? 16 : 0) | (RSIM_FUSED_ENABLED ? 32 : 0) | (RSIM_BALL_ENABLED ? 64 : 0);   // bit 5: the capacity tier above this configuration is compiled into its control-step kernel (rsim_limits_w)   // bit 2: the constraint Jacobian lives in DBatch.jg (NEFC * (NV + 1) floats per env)   // bit 1: two OSC arm parts
   return 0;
 }
