@@ -198,7 +198,8 @@ enum rsim_field {
                         *               the wrench the site body's parent transmits to it, from the solved accelerations and contact forces, in the site frame.
                         *               Carried besides them: jointpos, jointvel (hinge / slide), tendonpos, tendonvel (fixed tendons), framepos, framequat,
                         *               framelinvel, frameangvel (objtype site | xbody | body), velocimeter, gyro, accelerometer (at a site), touch (sphere,
-                        *               ellipsoid or box site) and actuatorfrc.  Written by rsim_forward / rsim_step2 / rsim_step / rsim_step2_last / rsim_observe:
+                        *               ellipsoid or box site), actuatorfrc, and rangefinder (position stage: rsim_ray from the site along its +Z, the site's body
+                        *               excluded, all groups, static geoms included; -1 when nothing is hit).  Written by rsim_forward / rsim_step2 / rsim_step / rsim_step2_last / rsim_observe:
                         *               the values of the last substep, before its integration; rsim_step1 / rsim_run_controller write the position- and
                         *               velocity-stage entries only and leave the acceleration-stage ones (force, torque, accelerometer, touch, actuatorfrc) as
                         *               they are, as mj_step1 does.  A sensor that is not carried -- another type, reftype / refname, objtype geom | camera, a
@@ -434,6 +435,24 @@ typedef struct rsim_contact {
   int32_t geom1, geom2, dim, efc_address;
 } rsim_contact;
 int rsim_contacts(rsim_batch* b, int env, int max_out, rsim_contact* out);
+
+/* Ray casting against the scene for the whole batch, on the device (csrc/rsim_ray.hip): MuJoCo's mj_ray semantics [3P, docs "API reference: ray collisions"].
+ * The result is the nearest surface point at t >= 0 along origin + t dir (dir need not be unit length; t is in units of |dir|); a ray that starts inside a
+ * solid reports where it leaves it; a plane is hit only from its +Z side, and a non-zero size[0] / size[1] bounds the hit.  ALL geoms of the model take
+ * part, visual ones included; A MESH GEOM IS ITS CONVEX HULL, the geometry this simulator collides with.  A geom is skipped when its rgba alpha is 0, when
+ * geomgroup is non-zero and bit `group` of it is clear, when it sits on the world body and flg_static == 0, or when its body is bodyexclude (-1: none).  Ties
+ * between geoms go to the lower geom id.  Heightfields are not carried.  The body poses are those of RSIM_XPOS / RSIM_XQUAT (after a fused control step they
+ * are brought up to the current state first, like every derived quantity); geom sizes / offsets an env of a per_env_params batch has overridden are honoured.
+ * Both calls are asynchronous on the batch's stream, take DEVICE pointers in and out, and allocate nothing after the first of them on a batch (which builds
+ * the scene table; a batch that never casts a ray holds none). */
+typedef struct { uint32_t geomgroup; int flg_static; int bodyexclude; } rsim_ray_opts;
+typedef struct { int body; float pos[3], quat[4]; float fovy_deg; } rsim_camera;   /* pose in the body frame; looks along -Z, +Y up */
+/* n_per_env rays per env: origin_dev / dir_dev [B][N][3] -> dist_dev [B][N] (t, -1 = nothing hit), geomid_dev [B][N] (model geom id, -1; may be NULL) */
+int rsim_ray(rsim_batch* b, const float* origin_dev, const float* dir_dev, int n_per_env, const rsim_ray_opts* opts, float* dist_dev, int32_t* geomid_dev);
+/* One ray per pixel of a pinhole camera, made in the kernel: row r counts from the TOP, the direction of pixel (r, c) in the camera frame is
+ * (a tan(fovy / 2) (2 (c + 1/2) / W - 1), tan(fovy / 2) (1 - 2 (r + 1/2) / H), -1) with a = W / H, so depth_dev [B][H][W] is the metric depth along the optical
+ * axis (what robosuite's get_real_depth_map yields), +inf where nothing is hit; geomid_dev [B][H][W] (may be NULL) is the `element` segmentation, -1 = none. */
+int rsim_render_depth(rsim_batch* b, const rsim_camera* cam, int height, int width, const rsim_ray_opts* opts, float* depth_dev, int32_t* geomid_dev);
 
 /* DynamicsModder / per-episode model edits (utils/mjmod.py:1705-1964, lift.py:311-318): overwrite a float model array
  * (blob field name, e.g. "geom_size", "body_mass", "dof_damping") for envs [env0, env0+nenv). `values` is HOST float64

@@ -268,6 +268,9 @@ def lib():
         L.rsim_id2name.argtypes = [vp, C.c_char_p, C.c_int]; L.rsim_id2name.restype = C.c_char_p
         L.rsim_full_M.argtypes = [vp, C.c_int, vp]
         L.rsim_contacts.argtypes = [vp, C.c_int, C.c_int, vp]
+        if hasattr(L, "rsim_ray"):        # (as above: absent from an earlier build named by RSIM_LIB)
+            L.rsim_ray.argtypes = [vp, vp, vp, C.c_int, C.POINTER(RayOpts), vp, vp]
+            L.rsim_render_depth.argtypes = [vp, C.POINTER(CameraDesc), C.c_int, C.c_int, C.POINTER(RayOpts), vp, vp]
         L.rsim_comm_unique_id.argtypes = [vp, C.c_size_t]
         L.rsim_comm_create.argtypes = [vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
         L.rsim_allreduce_stats.argtypes = [vp, vp, C.c_int, C.c_int]
@@ -450,6 +453,14 @@ class HipModel:
                 self._L.rsim_model_free(self.ptr)
         except Exception:
             pass
+
+
+class RayOpts(C.Structure):      # include/rsim.h rsim_ray_opts
+    _fields_ = [("geomgroup", C.c_uint32), ("flg_static", C.c_int), ("bodyexclude", C.c_int)]
+
+
+class CameraDesc(C.Structure):   # include/rsim.h rsim_camera
+    _fields_ = [("body", C.c_int), ("pos", C.c_float * 3), ("quat", C.c_float * 4), ("fovy_deg", C.c_float)]
 
 
 class _DevArray:
@@ -736,6 +747,64 @@ class HipBatch:
         if getattr(self, "_main_ext", None) is None:
             self._main_ext = torch.cuda.ExternalStream(self.stream(), device=f"cuda:{self.device}")
         return self._main_ext
+
+    # ---- ray casting (include/rsim.h rsim_ray / rsim_render_depth, csrc/rsim_ray.hip) ----------
+    def _ray_opts(self, geomgroup, static, bodyexclude):
+        return RayOpts(int(geomgroup), int(bool(static)), int(bodyexclude))
+
+    def _ray_fence_in(self, *tensors):
+        """inputs are usually produced on torch's current stream and are read on the batch's: the batch's stream waits for the producer"""
+        import torch
+
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(f"cuda:{self.device}"))
+        self._mask_stream().wait_event(ev)
+
+    def _ray_fence_out(self):
+        """... and torch's current stream waits for the kernel before it reads (or frees) what the call wrote or read: nothing blocks the host"""
+        import torch
+
+        ev = torch.cuda.Event()
+        ev.record(self._mask_stream())
+        torch.cuda.current_stream(f"cuda:{self.device}").wait_event(ev)
+
+    def raycast(self, origins, dirs, geomgroup=0, static=True, bodyexclude=-1):
+        """Cast N rays per env against the env's scene: origins / dirs CUDA float32 tensors [B, N, 3] (origin + t dir, dir need not be unit length) ->
+        (dist float32 [B, N] in units of |dir|, -1 = nothing hit; geomid int32 [B, N], -1).  geomgroup: bit mask of the geom groups that take part (0 = all);
+        static: geoms of the world body take part; bodyexclude: a body whose geoms do not.  MuJoCo's mj_ray semantics; a mesh geom is its convex hull."""
+        import torch
+
+        if not (isinstance(origins, torch.Tensor) and isinstance(dirs, torch.Tensor) and origins.is_cuda and dirs.is_cuda):
+            raise RsimError("raycast: origins and dirs must be CUDA tensors")
+        if origins.dim() != 3 or tuple(origins.shape) != tuple(dirs.shape) or origins.shape[0] != self.B or origins.shape[2] != 3 or origins.shape[1] < 1:
+            raise RsimError(f"raycast: origins and dirs must both have shape ({self.B}, N, 3) with N >= 1, got {tuple(origins.shape)} and {tuple(dirs.shape)}")
+        o, d = origins.contiguous().float(), dirs.contiguous().float()
+        n = int(o.shape[1])
+        dist = torch.empty((self.B, n), dtype=torch.float32, device=o.device)
+        gid = torch.empty((self.B, n), dtype=torch.int32, device=o.device)
+        opts = self._ray_opts(geomgroup, static, bodyexclude)
+        self._ray_fence_in()
+        _chk(self._L.rsim_ray(self.ptr, C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr()), n, C.byref(opts), C.c_void_p(dist.data_ptr()), C.c_void_p(gid.data_ptr())))
+        self._ray_fence_out()
+        return dist, gid
+
+    def render_depth(self, camera, height, width, segmentation=False, geomgroup=0, static=True, bodyexclude=-1):
+        """Depth image of every env from a raycast.Camera: float32 [B, H, W], metric depth along the optical axis, row 0 at the top, +inf where nothing is
+        hit; with segmentation=True also the `element` segmentation, int32 [B, H, W] geom ids (-1 = nothing).  The rays are made in the kernel."""
+        import torch
+
+        cam = CameraDesc(int(camera.body), (C.c_float * 3)(*[float(x) for x in camera.pos]), (C.c_float * 4)(*[float(x) for x in camera.quat]), float(camera.fovy))
+        dev = f"cuda:{self.device}"
+        h, w = int(height), int(width)
+        if h < 1 or w < 1:
+            raise RsimError(f"render_depth: image size {h} x {w}")
+        depth = torch.empty((self.B, h, w), dtype=torch.float32, device=dev)
+        seg = torch.empty((self.B, h, w), dtype=torch.int32, device=dev) if segmentation else None
+        opts = self._ray_opts(geomgroup, static, bodyexclude)
+        self._ray_fence_in()
+        _chk(self._L.rsim_render_depth(self.ptr, C.byref(cam), h, w, C.byref(opts), C.c_void_p(depth.data_ptr()), C.c_void_p(seg.data_ptr()) if segmentation else None))
+        self._ray_fence_out()
+        return (depth, seg) if segmentation else depth
 
     def set_schedule(self, longest_first=True):
         """Dispatch order of control_step: slowest envs of the previous step first (default) or identity."""

@@ -67,6 +67,14 @@ class BatchState:
         step1 and step2 the position- and velocity-stage sensors are those of the current substep, the acceleration-stage ones of the previous."""
         return self.batch.sensor(name)
 
+    def raycast(self, origins, dirs, **opts):
+        """mj_ray for every env on the body poses as they stand: valid between step1 and step2, like the other views (HipBatch.raycast)."""
+        return self.batch.raycast(origins, dirs, **opts)
+
+    def render_depth(self, camera, height, width, segmentation=False, **opts):
+        """Depth (and `element` segmentation) image of every env on the body poses as they stand (HipBatch.render_depth)."""
+        return self.batch.render_depth(camera, height, width, segmentation=segmentation, **opts)
+
     def body_dofs(self, body: int):
         """bool [nv]: the dofs that move `body` (its own joints and those of its ancestors)."""
         import torch

@@ -84,6 +84,8 @@ extern "C" int rsim_launch_bank_scatter(float* bank, int* tag, const int* env, c
 extern "C" int rsim_launch_randomize(const DModel* m, const DBatch* b, const DDr* d, unsigned long long seed, unsigned long long step, hipStream_t stream);
 #include "rsim_episode.h"
 #include "rsim_sensors.h"
+#include "rsim_ray.h"
+#include "rsim_hull.h"
 
 struct rsim_model;
 static int param_offset_impl(const rsim_model* m, const char* field, int elem);
@@ -128,6 +130,7 @@ struct rsim_model {
   std::vector<int> sens_objtype, sens_carried, sens_shape, sens_adr;
   std::vector<float> sens_size;
   int nsensor_extra, nsensor_zero;   // sensors k_sensors computes | sensors that read zero
+  int nsensor_ray;                   // rangefinders (computed by the ray kernel, rsim_ray.hip)
   DCtrl ctrl;
   rsim_task_desc task;
   int has_task;
@@ -218,6 +221,10 @@ struct rsim_batch {
   int* d_end_sel;        // [B] envs the last rsim_end_episodes restarted (allocated on first use)
   // sensors beyond force / torque (rsim_sensors.hip): allocated only for a model that has one k_sensors computes
   int* d_sens_i;         // [3][nsensor] object kind, carried flag, touch-site shape; then [ngeom] body of every geom
+  // ray casting (rsim_ray.hip): the scene table, built and uploaded by the first call that casts a ray (ray_scene) -- never for a batch that casts none
+  DRayGeom* d_ray_geom;  // [ngeom]
+  float* d_ray_planes;   // [nplane][4] face planes of the mesh geoms' hulls
+  int* d_ray_rf;         // [3][nsensor] rangefinders: site (-1: the sensor is none), its body, its first entry of a sensordata row
   float* d_sens_f;       // [nsensor][3] touch-site sizes; then [B][nq + nv + nu]: qpos / qvel / ctrl as they were ahead of a debug launch that integrates
   int ended_outside;     // rsim_end_episodes left needs_reset flags for the next rsim_control_step (fresh controllers); rsim_step2_last, which runs no in-kernel controller, drops them first
   // stream groups: control steps of env block g run on gstream[g]; `forked` = the group streams hold work the main stream has not waited for
@@ -467,11 +474,18 @@ extern "C" int rsim_model_create(const void* blob, size_t len, rsim_model** out)
     // entries -- every sensor of another type then reads zero, as it always did.  An object id the tables do not hold is not trusted to the kernel.
     const int ns = m->nsensor, nt = m->I("ntendon") ? m->I("ntendon")[0] : 0;
     m->sens_objtype.assign(ns, RS_OBJ_NONE); m->sens_carried.assign(ns, 0); m->sens_shape.assign(ns, -1); m->sens_size.assign((size_t)3 * ns + 3, 0.f); m->sens_adr = sa;
-    m->nsensor_extra = 0; m->nsensor_zero = 0;
+    m->nsensor_extra = 0; m->nsensor_zero = 0; m->nsensor_ray = 0;
     const int *ot = m->I("sensor_objtype"), *rs = m->I("sensor_reason"), *sh = m->I("sensor_shape");
     const bool have = ot && rs && sh && m->count("sensor_objtype") == (size_t)ns && m->count("sensor_reason") == (size_t)ns && m->count("sensor_shape") == (size_t)ns;
     for (int i = 0; i < ns; i++) {
       if (st[i] == 0 || st[i] == 1) continue;
+      if (st[i] == RSIM_RANGEFINDER) {   // a ray from a site along its +Z: the ray kernel's, not k_sensors'
+        const bool ok = have && rs[i] == 0 && ot[i] == RS_OBJ_SITE && ss[i] >= 0 && ss[i] < m->nsite && sa[i + 1] - sa[i] == 1;
+        if (ok) m->sens_objtype[i] = RS_OBJ_SITE;
+        m->sens_carried[i] = ok ? 1 : 0;
+        if (ok) m->nsensor_ray++; else m->nsensor_zero++;
+        continue;
+      }
       bool ok = have && rs[i] == 0 && st[i] >= RS_JOINTPOS && st[i] < RS_TYPE_END;
       if (ok) {
         const int k = ot[i], o = ss[i], dim = sa[i + 1] - sa[i];
@@ -851,6 +865,7 @@ extern "C" int rsim_batch_create(rsim_model* m, int B, int device, int per_env, 
   b->db.prof_env = -1;
   b->d_bank = nullptr; b->d_bank_tag = nullptr; b->d_patch = nullptr; b->d_ft_base = nullptr;
   b->d_sens_i = nullptr; b->d_sens_f = nullptr;
+  b->d_ray_geom = nullptr; b->d_ray_planes = nullptr; b->d_ray_rf = nullptr;
   b->bstream = nullptr; b->bev = nullptr; b->h_epidx = nullptr; b->bank_poll_pending = 0; b->bstage_next = 0;
   memset(b->bstage, 0, sizeof(b->bstage));
   const int ncg = (int)m->cg.size();
@@ -1083,6 +1098,9 @@ extern "C" void rsim_batch_free(rsim_batch* b) {
   if (b->d_end_sel) hipFree(b->d_end_sel);
   if (b->d_sens_i) hipFree(b->d_sens_i);
   if (b->d_sens_f) hipFree(b->d_sens_f);
+  if (b->d_ray_geom) hipFree(b->d_ray_geom);
+  if (b->d_ray_planes) hipFree(b->d_ray_planes);
+  if (b->d_ray_rf) hipFree(b->d_ray_rf);
   if (b->db.mprc) hipFree(b->db.mprc);
   if (b->db.jg) hipFree(b->db.jg);
   if (b->db.bpl) hipFree(b->db.bpl);
@@ -1327,6 +1345,95 @@ static int sensors_launch(rsim_batch* b, int stages, bool pre) {
   return 0;
 }
 
+// ---- ray casting (rsim_ray.hip) ---------------------------------------------------------------------------------------------------------------
+// The scene table: one record per geom of the model (visual geoms included) and, per mesh geom, the face planes of its convex hull -- the geometry this
+// simulator collides with -- from the blob's hull vertices through the MJCF compiler's quickhull (rsim_hull.h).  Built and uploaded by the first call
+// that needs it; the model blob is not touched.
+static int ray_scene(rsim_batch* b) {
+  if (b->d_ray_geom) return 0;
+  const rsim_model* m = b->m;
+  const int ng = m->ngeom;
+  const int *gt = m->I("geom_type"), *gb = m->I("geom_bodyid"), *gg = m->I("geom_group"), *gd = m->I("geom_dataid");
+  const double *gs = m->D("geom_size"), *gp = m->D("geom_pos"), *gq = m->D("geom_quat"), *rgba = m->D("geom_rgba"), *rb = m->D("geom_rbound"), *rc = m->D("geom_rcenter");
+  if (ng < 1 || !gt || !gb || !gs || !gp || !gq) return fail("ray casting: the model has no geoms");
+  std::vector<DRayGeom> G((size_t)ng);
+  std::vector<float> planes;
+  std::map<int, std::pair<int, int>> mesh_planes;   // mesh id -> (first row, rows): geoms of one mesh share its planes
+  for (int g = 0; g < ng; g++) {
+    DRayGeom& r = G[g];
+    memset(&r, 0, sizeof(r));
+    r.type = gt[g]; r.body = gb[g]; r.cg = m->geom2cg[g];
+    const int group = gg ? gg[g] : 0;
+    r.flags = ((!rgba || rgba[4 * g + 3] != 0.0) ? RAY_VISIBLE : 0) | ((group < 0 ? 0 : group > 30 ? 30 : group) << 8);
+    for (int k = 0; k < 3; k++) { r.size[k] = (float)gs[3 * g + k]; r.pos[k] = (float)gp[3 * g + k]; r.rcenter[k] = rc ? (float)rc[3 * g + k] : 0.f; }
+    for (int k = 0; k < 4; k++) r.quat[k] = (float)gq[4 * g + k];
+    r.rbound = rb ? (float)rb[g] : 0.f;
+    if (r.body < 0 || r.body >= m->nbody) return fail("ray casting: geom %d names body %d", g, r.body);
+    if (r.type == 7) {
+      const int did = gd ? gd[g] : -1;
+      const int nmesh = (int)m->count("mesh_vertadr");
+      if (did < 0) continue;   // a mesh geom whose mesh is not in the blob (the compilers keep the hulls of colliding geoms only): nothing to hit, the kernel skips it
+      if (did >= nmesh || !m->D("mesh_vert")) return fail("ray casting: mesh geom %d names mesh %d of %d", g, did, nmesh);
+      auto it = mesh_planes.find(did);
+      if (it == mesh_planes.end()) {
+        const int adr = m->I("mesh_vertadr")[did], num = m->I("mesh_vertnum")[did];
+        if (adr < 0 || num < 4 || (size_t)(adr + num) * 3 > m->count("mesh_vert")) return fail("ray casting: hull of mesh %d out of range", did);
+        const double* V = m->D("mesh_vert") + 3 * (size_t)adr;
+        int np = rsim_hull_planes(V, num, nullptr, 0);
+        if (np < 0) return 1;
+        std::vector<double> P((size_t)4 * np);
+        if (rsim_hull_planes(V, num, P.data(), np) != np) return fail("ray casting: hull of mesh %d changed between two runs", did);
+        it = mesh_planes.emplace(did, std::make_pair((int)(planes.size() / 4), np)).first;
+        for (double v : P) planes.push_back((float)v);
+        if (!rb) {   // a blob without bounding spheres: about the origin of the geom frame
+          double far = 0;
+          for (int v = 0; v < num; v++) far = std::max(far, std::sqrt(V[3 * v] * V[3 * v] + V[3 * v + 1] * V[3 * v + 1] + V[3 * v + 2] * V[3 * v + 2]));
+          r.rbound = (float)far;
+        }
+      }
+      r.plane_adr = it->second.first; r.plane_num = it->second.second;
+    }
+  }
+  std::vector<int> rf((size_t)3 * (m->nsensor > 0 ? m->nsensor : 1), -1);
+  for (int i = 0; i < m->nsensor; i++) {
+    if (m->I("sensor_type")[i] != RSIM_RANGEFINDER || !m->sens_carried[i]) continue;
+    const int site = m->I("sensor_objid")[i];
+    rf[i] = site; rf[m->nsensor + i] = m->I("site_bodyid")[site]; rf[2 * m->nsensor + i] = m->sens_adr[i];
+  }
+  HIPCHK(hipSetDevice(b->device));
+  if (dalloc(&b->d_ray_rf, rf.size())) return 1;
+  HIPCHK(hipMemcpy(b->d_ray_rf, rf.data(), rf.size() * sizeof(int), hipMemcpyHostToDevice));
+  if (dalloc(&b->d_ray_planes, planes.size() + 4)) return 1;
+  if (!planes.empty()) HIPCHK(hipMemcpy(b->d_ray_planes, planes.data(), planes.size() * sizeof(float), hipMemcpyHostToDevice));
+  if (dalloc((char**)&b->d_ray_geom, G.size() * sizeof(DRayGeom))) return 1;
+  HIPCHK(hipMemcpy(b->d_ray_geom, G.data(), G.size() * sizeof(DRayGeom), hipMemcpyHostToDevice));
+  return 0;
+}
+static void ray_args(rsim_batch* b, DRay* a, int mode, int n) {
+  const rsim_model* m = b->m;
+  memset(a, 0, sizeof(*a));
+  a->B = b->B; a->mode = mode; a->n = n; a->ngeom = m->ngeom; a->nbody = m->nbody; a->fstride = b->dm.fstride;
+  a->fo_size = m->fo[FO_cg_size]; a->fo_pos = m->fo[FO_cg_pos]; a->fo_quat = m->fo[FO_cg_quat]; a->fo_rcenter = m->fo[FO_cg_rcenter]; a->fo_rbound = m->fo[FO_cg_rbound];
+  a->fo_site_pos = m->fo[FO_site_pos]; a->fo_site_quat = m->fo[FO_site_quat];
+  a->geom = b->d_ray_geom; a->planes = b->d_ray_planes; a->ft = b->d_ft; a->xpos = b->db.xpos; a->xquat = b->db.xquat;
+  a->flg_static = 1; a->bodyexclude = -1; a->miss = -1.f;
+}
+static int ray_launch(rsim_batch* b, const DRay* a, const char* who) {
+  if (b->B > 65535) return fail("%s: more than 65535 envs in one batch", who);
+  const int e = rsim_launch_ray(a, b->stream);
+  if (e) return fail("%s: ray kernel launch failed: %s", who, hipGetErrorString((hipError_t)e));
+  return 0;
+}
+// the rangefinders of RSIM_SENSORDATA: position stage, behind a debug launch of the step kernel (which has just written RSIM_XPOS / RSIM_XQUAT and zeroed
+// the entries), on the same stream, one wavefront per env
+static int rangefinder_launch(rsim_batch* b) {
+  if (ray_scene(b)) return 1;
+  DRay a;
+  ray_args(b, &a, RAY_RANGEFINDER, b->m->nsensor);
+  a.rf = b->d_ray_rf; a.nsensordata = b->m->nsensordata; a.dist = b->db.sensordata;
+  return ray_launch(b, &a, "rangefinder");
+}
+
 // The one place a step kernel is launched.  Configurations 0-2: the plain k_step, unless this launch needs what only k_full_step compiles in -- the profiler
 // armed (rsim_profile), the MPR restart cone on (RSIM_MPR_CONE), applied forces enabled (RF_APPLIED) -- or the batch asked for the full form.  The debug form
 // (RF_DEBUG: k_step_dbg) and configurations 3-4 have one kernel.
@@ -1460,6 +1567,7 @@ static int launch(rsim_batch* b, const float* actions, int n_sub, int flags) {
   int e = step_launch(b, &b->db, actions, n_sub, flags, b->stream);
   if (e) return fail("kernel launch failed: %s", hipGetErrorString((hipError_t)e));
   if (sensors && sensors_launch(b, RS_STAGE_POS | RS_STAGE_VEL | ((flags & RF_ACTSOLVE) ? RS_STAGE_ACC : 0), sens_pre)) return 1;
+  if ((flags & RF_DEBUG) && b->m->nsensor_ray > 0 && b->db.sensordata && rangefinder_launch(b)) return 1;   // (a model without a rangefinder launches nothing extra)
   if (traced) tr_mark(b, 3);
   if (listed) {
     // after both: the envs the native pass had to hand over in mid-step (rare: most move up between steps), redone from their unchanged state
@@ -1932,6 +2040,55 @@ extern "C" int rsim_set_array(rsim_batch* b, int field, const void* src, size_t 
   if (field == RSIM_QPOS && b->db.mprc) HIPCHK(hipMemset(b->db.mprc, 0, (size_t)b->B * b->m->npair * 12 * sizeof(float)));
   b->gen++;
   return 0;
+}
+
+// ---- ray queries and depth images (include/rsim.h) ---------------------------------------------------------------------------------------------
+static int ray_opts(const char* who, rsim_batch* b, const rsim_ray_opts* o, DRay* a) {
+  if (o->bodyexclude < -1 || o->bodyexclude >= b->m->nbody) return fail("%s: bodyexclude %d out of range (%d bodies, -1 = none)", who, o->bodyexclude, b->m->nbody);
+  a->geomgroup = o->geomgroup; a->flg_static = o->flg_static ? 1 : 0; a->bodyexclude = o->bodyexclude;
+  return 0;
+}
+extern "C" int rsim_ray(rsim_batch* b, const float* origin_dev, const float* dir_dev, int n_per_env, const rsim_ray_opts* opts, float* dist_dev, int32_t* geomid_dev) {
+  if (!b) return fail("rsim_ray: batch is NULL");
+  if (!origin_dev || !dir_dev) return fail("rsim_ray: origin_dev / dir_dev is NULL");
+  if (!opts) return fail("rsim_ray: opts is NULL");
+  if (!dist_dev) return fail("rsim_ray: dist_dev is NULL");
+  if (n_per_env <= 0) return fail("rsim_ray: n_per_env %d <= 0", n_per_env);
+  if ((long long)n_per_env * b->B > 0x7fffffffLL / 3) return fail("rsim_ray: %d rays per env x %d envs is more than one call carries", n_per_env, b->B);
+  if (join_groups(b)) return 1;
+  HIPCHK(hipSetDevice(b->device));
+  if (refresh_derived(b, RSIM_XPOS) || ray_scene(b)) return 1;
+  DRay a;
+  ray_args(b, &a, RAY_ARRAYS, n_per_env);
+  if (ray_opts("rsim_ray", b, opts, &a)) return 1;
+  a.origin = origin_dev; a.dir = dir_dev; a.dist = dist_dev; a.geomid = geomid_dev;
+  return ray_launch(b, &a, "rsim_ray");
+}
+extern "C" int rsim_render_depth(rsim_batch* b, const rsim_camera* cam, int height, int width, const rsim_ray_opts* opts, float* depth_dev, int32_t* geomid_dev) {
+  if (!b) return fail("rsim_render_depth: batch is NULL");
+  if (!cam) return fail("rsim_render_depth: camera is NULL");
+  if (!opts) return fail("rsim_render_depth: opts is NULL");
+  if (!depth_dev) return fail("rsim_render_depth: depth_dev is NULL");
+  if (height <= 0 || width <= 0) return fail("rsim_render_depth: image size %d x %d", height, width);
+  if ((long long)height * width > (1 << 24)) return fail("rsim_render_depth: image of %d x %d pixels is more than one call carries", height, width);
+  if (cam->body < 0 || cam->body >= b->m->nbody) return fail("rsim_render_depth: camera body %d out of range (%d bodies)", cam->body, b->m->nbody);
+  if (!(cam->fovy_deg > 0.f && cam->fovy_deg < 180.f)) return fail("rsim_render_depth: fovy %g outside (0, 180) degrees", (double)cam->fovy_deg);
+  double qn = 0;
+  for (int k = 0; k < 4; k++) qn += (double)cam->quat[k] * cam->quat[k];
+  if (!(qn > 1e-12)) return fail("rsim_render_depth: camera quaternion is zero");
+  if (join_groups(b)) return 1;
+  HIPCHK(hipSetDevice(b->device));
+  if (refresh_derived(b, RSIM_XPOS) || ray_scene(b)) return 1;
+  DRay a;
+  ray_args(b, &a, RAY_CAMERA, height * width);
+  if (ray_opts("rsim_render_depth", b, opts, &a)) return 1;
+  a.cam_body = cam->body; a.H = height; a.W = width;
+  for (int k = 0; k < 3; k++) a.cam_pos[k] = cam->pos[k];
+  for (int k = 0; k < 4; k++) a.cam_quat[k] = cam->quat[k];
+  a.tanhalf = (float)tan(0.5 * (double)cam->fovy_deg * 3.14159265358979323846 / 180.0);
+  a.miss = INFINITY;
+  a.dist = depth_dev; a.geomid = geomid_dev;
+  return ray_launch(b, &a, "rsim_render_depth");
 }
 
 // mj_fullM (controllers/parts/controller.py:226-227: `mujoco.mj_fullM(model, mass_matrix, data.qM)`): the dense joint-space inertia of one env

@@ -1190,7 +1190,8 @@ Flat compile(const char* xml, size_t len, const std::string& asset_dir) {
     static const std::map<std::string, int> dims = {{"force", 3}, {"torque", 3}, {"touch", 1}, {"framepos", 3}, {"framequat", 4}, {"jointpos", 1}, {"jointvel", 1},
                                                     {"velocimeter", 3}, {"gyro", 3}, {"accelerometer", 3}, {"framelinvel", 3}, {"frameangvel", 3}};
     static const std::map<std::string, int> codes = {{"force", 0}, {"torque", 1}, {"jointpos", 2}, {"tendonpos", 3}, {"framepos", 4}, {"framequat", 5}, {"jointvel", 6}, {"tendonvel", 7},
-                                                     {"velocimeter", 8}, {"gyro", 9}, {"framelinvel", 10}, {"frameangvel", 11}, {"accelerometer", 12}, {"touch", 13}, {"actuatorfrc", 14}};
+                                                     {"velocimeter", 8}, {"gyro", 9}, {"framelinvel", 10}, {"frameangvel", 11}, {"accelerometer", 12}, {"touch", 13}, {"actuatorfrc", 14},
+                                                     {"rangefinder", 15} /* computed by rsim_ray.hip */};
     enum { OBJ_NONE, OBJ_JOINT, OBJ_TENDON, OBJ_SITE, OBJ_XBODY, OBJ_BODY, OBJ_ACTUATOR };
     std::vector<std::pair<std::string, bool>> tnames;   // tendons are compiled further down: their names are all a sensor needs
     if (const Xml* tend = root.find("tendon")) for (auto& t : tend->kids) { std::string nm; bool named; name_of(*t, nm, named); tnames.emplace_back(nm, named); }
@@ -1229,7 +1230,7 @@ Flat compile(const char* xml, size_t len, const std::string& asset_dir) {
       if (tg == "jointpos" || tg == "jointvel") { kind = OBJ_JOINT; attr = "joint"; }
       else if (tg == "tendonpos" || tg == "tendonvel") { kind = OBJ_TENDON; attr = "tendon"; }
       else if (tg == "actuatorfrc") { kind = OBJ_ACTUATOR; attr = "actuator"; }
-      else if (tg == "velocimeter" || tg == "gyro" || tg == "accelerometer" || tg == "touch") { kind = OBJ_SITE; attr = "site"; }
+      else if (tg == "velocimeter" || tg == "gyro" || tg == "accelerometer" || tg == "touch" || tg == "rangefinder") { kind = OBJ_SITE; attr = "site"; }
       else { const std::string ot = s->gets("objtype", ""); kind = ot == "site" ? OBJ_SITE : (ot == "xbody" ? OBJ_XBODY : (ot == "body" ? OBJ_BODY : OBJ_NONE)); }
       int oid = -1, reason = 0, shape = -1;
       if (kind == OBJ_NONE) reason = 3;
@@ -1494,4 +1495,41 @@ extern "C" int rsim_model_compile(const char* xml, size_t len, const char* asset
   const int r = rsim_model_create(blob, n, out);
   free(blob);
   return r;
+}
+
+// ------------------------------------------------------------------------------------------------------------------ internal (rsim_hull.h)
+// Face planes of a hull for the ray kernel (rsim_ray.hip).  Triangles of one flat facet come out of quickhull with normals that differ by rounding: a
+// triangle whose three corners lie within 1e-9 of the hull's extent of an earlier facet's plane, and whose normal points the same way, joins that facet.
+#include "rsim_hull.h"
+extern "C" int rsim_hull_planes(const double* vert, int nvert, double* planes, int cap) {
+  if (!vert || nvert < 4 || (cap > 0 && !planes)) { fail_msg("rsim_hull_planes: NULL argument or fewer than 4 points"); return -1; }
+  try {
+    std::vector<V3> P((size_t)nvert);
+    double scale = 1e-300;
+    for (int i = 0; i < nvert; i++) { P[i] = {vert[3 * i], vert[3 * i + 1], vert[3 * i + 2]}; for (int k = 0; k < 3; k++) scale = std::max(scale, std::fabs(vert[3 * i + k])); }
+    const Hull h = quickhull(P);
+    const double tol = 1e-9 * scale;
+    std::vector<std::array<double, 4>> out;
+    std::vector<double> area;   // the facet keeps the plane of its largest triangle
+    for (auto& t : h.tri) {
+      const V3 nn = cross(P[t[1]] - P[t[0]], P[t[2]] - P[t[0]]);
+      const double l = norm(nn);
+      if (!(l > 0)) continue;
+      const V3 n = nn * (1.0 / l);
+      const double d = dot(n, P[t[0]]);
+      bool merged = false;
+      for (size_t r = 0; r < out.size() && !merged; r++) {
+        const V3 rn = {out[r][0], out[r][1], out[r][2]};
+        if (dot(rn, n) < 0.5) continue;
+        double far = 0;
+        for (int k = 0; k < 3; k++) far = std::max(far, std::fabs(dot(rn, P[t[k]]) - out[r][3]));
+        if (far > tol) continue;
+        merged = true;
+        if (l > area[r]) { out[r] = {n.x, n.y, n.z, d}; area[r] = l; }
+      }
+      if (!merged) { out.push_back({n.x, n.y, n.z, d}); area.push_back(l); }
+    }
+    for (size_t r = 0; r < out.size() && (int)r < cap; r++) for (int k = 0; k < 4; k++) planes[4 * r + k] = out[r][k];
+    return (int)out.size();
+  } catch (const std::exception& e) { fail_msg(std::string("rsim_hull_planes: ") + e.what()); return -1; }
 }

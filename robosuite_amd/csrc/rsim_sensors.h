@@ -3,7 +3,8 @@
 #include "rsim_internal.h"
 
 // sensor_type codes of the model blob (rsim_mjcf.cpp / robosuite_amd/mjcf.py SENSOR_TYPES).  0 / 1 (force, torque) are computed inside the step kernel
-// (rsim_step.hip sensor_acc), which writes zero to every other entry; k_sensors runs behind it and fills the entries of the codes below.
+// (rsim_step.hip sensor_acc), which writes zero to every other entry; k_sensors runs behind it and fills the entries of the codes below.  Code 15, the
+// rangefinder, is past RS_TYPE_END on purpose: k_sensors leaves it alone, the ray kernel behind it fills it (rsim_ray.h RSIM_RANGEFINDER).
 enum {
   RS_JOINTPOS = 2, RS_TENDONPOS, RS_FRAMEPOS, RS_FRAMEQUAT,                                   // position stage (mj_sensorPos)
   RS_JOINTVEL, RS_TENDONVEL, RS_VELOCIMETER, RS_GYRO, RS_FRAMELINVEL, RS_FRAMEANGVEL,         // velocity stage (mj_sensorVel)

@@ -38,10 +38,10 @@ class HipShimBackend:
         }
         self._ncon = 0
         self._contacts = []
-        # sensordata entries mj_step1 refreshes: the position- and velocity-stage sensors (mjcf.SENSOR_TYPES codes 2 .. 11)
+        # sensordata entries mj_step1 refreshes: the position- and velocity-stage sensors (mjcf.SENSOR_TYPES codes 2 .. 11, and the rangefinder, code 15)
         sd = np.concatenate([[0], np.cumsum(np.asarray(m.arrays["sensor_dim"]).ravel())]).astype(int) if m.nsensor else np.zeros(1, dtype=int)
         st = np.asarray(m.arrays["sensor_type"]).ravel() if m.nsensor else []
-        self._posvel = np.concatenate([np.arange(sd[i], sd[i + 1]) for i in range(len(st)) if 2 <= st[i] <= 11] + [np.zeros(0, dtype=int)]).astype(int)
+        self._posvel = np.concatenate([np.arange(sd[i], sd[i + 1]) for i in range(len(st)) if 2 <= st[i] <= 11 or st[i] == 15] + [np.zeros(0, dtype=int)]).astype(int)
         zero = [(n, r) for n, _, carried, r in self.model.sensor_status() if not carried] if self.model.int("nsensor_zero") > 0 else []
         if zero:
             import warnings

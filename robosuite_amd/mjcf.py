@@ -46,13 +46,15 @@ GAIN_FIXED, BIAS_NONE, BIAS_AFFINE = 0, 0, 1
 # The same table is in csrc/rsim_mjcf.cpp and csrc/rsim_sensors.h.
 SENSOR_TYPES = {"force": 0, "torque": 1, "jointpos": 2, "tendonpos": 3, "framepos": 4, "framequat": 5, "jointvel": 6, "tendonvel": 7, "velocimeter": 8,
                 "gyro": 9, "framelinvel": 10, "frameangvel": 11, "accelerometer": 12, "touch": 13, "actuatorfrc": 14}
-SENSOR_TYPE_NAMES = {v: k for k, v in SENSOR_TYPES.items()}
+# the sensor the ray kernel computes (csrc/rsim_ray.hip, host mirror: raycast.py); a table of its own: SENSOR_TYPES is the set csrc/rsim_sensors.hip covers
+RAY_SENSOR_TYPES = {"rangefinder": 15}
+SENSOR_TYPE_NAMES = {v: k for k, v in {**SENSOR_TYPES, **RAY_SENSOR_TYPES}.items()}
 SENSOR_OBJ_NONE, SENSOR_OBJ_JOINT, SENSOR_OBJ_TENDON, SENSOR_OBJ_SITE, SENSOR_OBJ_XBODY, SENSOR_OBJ_BODY, SENSOR_OBJ_ACTUATOR = range(7)   # sensor_objtype
 # what a sensor's object is and the attribute that names it ("frame": objtype / objname)
 _SENSOR_OBJECT = {"jointpos": ("joint", "joint"), "jointvel": ("joint", "joint"), "tendonpos": ("tendon", "tendon"), "tendonvel": ("tendon", "tendon"),
                   "framepos": ("frame", None), "framequat": ("frame", None), "framelinvel": ("frame", None), "frameangvel": ("frame", None),
                   "velocimeter": ("site", "site"), "gyro": ("site", "site"), "accelerometer": ("site", "site"), "touch": ("site", "site"),
-                  "actuatorfrc": ("actuator", "actuator")}
+                  "actuatorfrc": ("actuator", "actuator"), "rangefinder": ("site", "site")}
 # sensor_reason: 0 = carried, otherwise why the sensor reads zero
 SENSOR_REASONS = {0: "", 1: "sensor type not carried", 2: "reftype / refname not carried", 3: "objtype not carried (site, xbody, body only)",
                   4: "touch site shape not carried (sphere, ellipsoid, box only)", 5: "joint is not a hinge or slide", 6: "non-zero cutoff not carried",
@@ -1040,7 +1042,7 @@ def compile_mjcf(xml: str, asset_dir: str | None = None, max_hull_vert: int = 0)
                "site": _named([s["name"] for s in sites]), "body": _named([b["name"] for b in bodies]), "actuator": _named([a["name"] for a in acts])}
     s_type, s_obj, s_kind, s_reason, s_shape = [], [], [], [], []
     for s in sens:
-        code = SENSOR_TYPES.get(s["type"], -1)
+        code = SENSOR_TYPES.get(s["type"], RAY_SENSOR_TYPES.get(s["type"], -1))
         e = s["elem"]
         if code < 2:      # force / torque / a type outside the table: as before, the site (if any) is the object
             s_type.append(code); s_obj.append(sname2id.get(s["site"], -1)); s_kind.append(SENSOR_OBJ_SITE if code >= 0 else SENSOR_OBJ_NONE)

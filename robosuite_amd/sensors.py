@@ -15,7 +15,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import mjcf
+from . import mjcf, raycast
 from .mjcf import (SENSOR_OBJ_BODY, SENSOR_OBJ_SITE, SENSOR_OBJ_XBODY, SENSOR_TYPES)
 
 
@@ -149,6 +149,10 @@ def sensor_values(m, qpos, qvel, qacc, ctrl, contacts=()):
             if I("actuator_forcelimited")[o]:
                 f = min(max(f, A("actuator_forcerange", 2)[o, 0]), A("actuator_forcerange", 2)[o, 1])
             out[sl] = f
+        elif t == raycast.RANGEFINDER:            # the ray kernel's sensor (csrc/rsim_ray.hip): its mirror is raycast.py
+            if frames is None:
+                frames = body_frames(m, qpos, qvel, qacc)
+            out[sl] = raycast.rangefinder_values(m, [f.p for f in frames], [f.q for f in frames])[i]
         else:
             if frames is None:
                 frames = body_frames(m, qpos, qvel, qacc)

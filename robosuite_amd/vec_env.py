@@ -119,6 +119,40 @@ class VecEnv:
         self.env.batch.sync()
         return s
 
+    # ---- geometric queries (include/rsim.h rsim_ray / rsim_render_depth): explicit calls, never part of `step`
+    def cameras(self, xml: str | None = None):
+        """{name: raycast.Camera} of the fixed cameras of the env's MJCF: of `xml`, or of the XML the model was compiled from when it is at hand (the shipped
+        assets carry none: hand `render_depth` a raycast.Camera then)."""
+        from . import raycast
+
+        flat = self.env.model.flat
+        xml = xml if xml is not None else getattr(flat, "xml", None)
+        if xml is None:
+            raise ValueError("cameras: this model carries no MJCF; pass the XML, or build a raycast.Camera(body, pos, quat, fovy) yourself")
+        return raycast.cameras_from_xml(xml, flat)
+
+    def raycast(self, origins, dirs, geomgroup=0, static=True, bodyexclude=-1):
+        """mj_ray for every env: origins / dirs [n_envs, N, 3] device tensors -> (dist [n_envs, N], -1 = nothing hit; geomid [n_envs, N]).  The first query after
+        a fused `step` runs one forward pass on the current state, as robosuite's sim.forward() before such a read."""
+        return self.env.batch.raycast(origins, dirs, geomgroup=geomgroup, static=static, bodyexclude=bodyexclude)
+
+    def render_depth(self, camera, height, width, segmentation=False, convention="opengl", **opts):
+        """Metric depth image of every env, [n_envs, H, W] (what robosuite's get_real_depth_map makes of a depth observation; +inf where nothing is hit), and
+        with segmentation=True the `element` segmentation (geom ids, -1 = nothing; robosuite's camera_segmentations="element").  camera: a raycast.Camera,
+        or the name of a fixed camera when the model's MJCF is at hand.  convention: "opengl" hands the BOTTOM row first, as robosuite's default image
+        convention does; "opencv" the top row first.  Colour, `instance` / `class` segmentation, tracking cameras and heightfields are not carried."""
+        if convention not in ("opengl", "opencv"):
+            raise ValueError(f"convention must be 'opengl' or 'opencv', got {convention!r}")
+        if isinstance(camera, str):
+            cams = self.cameras()
+            if camera not in cams:
+                raise KeyError(f"no fixed camera named {camera!r} (have {sorted(cams)})")
+            camera = cams[camera]
+        out = self.env.batch.render_depth(camera, height, width, segmentation=segmentation, **opts)
+        if convention == "opencv":
+            return out
+        return tuple(o.flip(1) for o in out) if segmentation else out.flip(1)
+
     def enable_applied_forces(self, on: bool = True):
         """Honour `qfrc_applied` and `xfrc_applied` in `step` (off by default: the control step then reads neither).  An env that reports `done`
         has both rows zeroed for its next episode, in the same step, so a force written after seeing `done` acts on the new episode."""
