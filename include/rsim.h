@@ -503,6 +503,30 @@ int rsim_comm_create(const void* id, size_t bytes, int rank, int world, int devi
 int rsim_allreduce_stats(rsim_comm* c, double* inout, int n, int op);
 void rsim_comm_free(rsim_comm* c);
 
+/* Inverse kinematics of a site for the whole batch, on the device (csrc/rsim_ik.hip): k damped least-squares solves per env, one wavefront each.  Which joint
+ * positions of the `ndof` controlled dofs (dof ids, each a hinge or slide joint on the path from the world to the site's body; 1 .. RSIM_JNT_MAX of them)
+ * put `site` at the target position and, with target_quat_dev, orientation?  Per iteration: p, R, J = FK(q) (site pose and its Jacobian over the controlled
+ * dofs, world frame); err = [p* - p ; w], w the rotation vector of q* (x) conj(q_site), angle in (-pi, pi]; converged when |err_pos| < pos_tol and (with an
+ * orientation target) |w| < rot_tol, given up after max_iters updates; A = J J^T + damping I, dq = J^T A^-1 err; with posture_gain > 0 also
+ * v = posture_gain (q_rest - q), dq += v - J^T A^-1 (J v), q_rest the start vector; dq scaled so that max |dq| <= max_dq; q += dq, clamped to jnt_range
+ * where the joint is limited (clamp_range; the start vector is clamped the same way).  FK is the position stage's (qpos0 offsets, hinge anchors, several
+ * joints per body) on the env's OWN model parameters (per_env_params overrides, domain-randomisation draws); a joint on the path that is not controlled is
+ * held at the env's current qpos.  A ball joint, a free joint or a mocap body on the path, and a controlled dof that is not on it, fail by name.
+ * A PURE QUERY: it reads qpos and the model parameters and writes only its three outputs; state, derived arrays and their stale marks stay as they are.
+ * Asynchronous on the batch's stream, DEVICE pointers in and out; the chain table of a (site, dofs) key is built and uploaded by the first call that
+ * names it and kept in the batch (a batch that never solves holds none).  q_out of a problem that did not converge is the last iterate: finite and, with
+ * clamp_range, inside the ranges.  robosuite_amd/ik.py is the fp64 host mirror. */
+typedef struct rsim_ik_opts { float damping, max_dq, pos_tol, rot_tol, posture_gain; int32_t max_iters, clamp_range; } rsim_ik_opts;
+/* defaults (opts == NULL): damping 1e-4, max_dq 0.5, pos_tol 1e-4 m, rot_tol 1e-3 rad, posture_gain 0, max_iters 50, clamp_range 1 */
+int rsim_ik_site(rsim_batch* b, int site, int ndof, const int32_t* dof_ids, int k,
+                 const float* target_pos_dev   /* [B][k][3] */,
+                 const float* target_quat_dev  /* [B][k][4] wxyz, or NULL: position only */,
+                 const float* q_init_dev       /* [B][k][ndof], or NULL: the env's current qpos */,
+                 const rsim_ik_opts* opts      /* NULL: defaults */,
+                 float* q_out_dev              /* [B][k][ndof] */,
+                 float* err_dev                /* [B][k][2]: |err_pos|, |omega| at q_out (0 without an orientation target) */,
+                 int32_t* iters_dev            /* [B][k]: updates made; bit 30 set = converged */);
+
 
 #ifdef __cplusplus
 }

@@ -271,6 +271,8 @@ def lib():
         if hasattr(L, "rsim_ray"):        # (as above: absent from an earlier build named by RSIM_LIB)
             L.rsim_ray.argtypes = [vp, vp, vp, C.c_int, C.POINTER(RayOpts), vp, vp]
             L.rsim_render_depth.argtypes = [vp, C.POINTER(CameraDesc), C.c_int, C.c_int, C.POINTER(RayOpts), vp, vp]
+        if hasattr(L, "rsim_ik_site"):
+            L.rsim_ik_site.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, vp, vp, vp, C.POINTER(IkOpts), vp, vp, vp]
         L.rsim_comm_unique_id.argtypes = [vp, C.c_size_t]
         L.rsim_comm_create.argtypes = [vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
         L.rsim_allreduce_stats.argtypes = [vp, vp, C.c_int, C.c_int]
@@ -461,6 +463,11 @@ class RayOpts(C.Structure):      # include/rsim.h rsim_ray_opts
 
 class CameraDesc(C.Structure):   # include/rsim.h rsim_camera
     _fields_ = [("body", C.c_int), ("pos", C.c_float * 3), ("quat", C.c_float * 4), ("fovy_deg", C.c_float)]
+
+
+class IkOpts(C.Structure):       # include/rsim.h rsim_ik_opts
+    _fields_ = [("damping", C.c_float), ("max_dq", C.c_float), ("pos_tol", C.c_float), ("rot_tol", C.c_float), ("posture_gain", C.c_float),
+                ("max_iters", C.c_int32), ("clamp_range", C.c_int32)]
 
 
 class _DevArray:
@@ -805,6 +812,53 @@ class HipBatch:
         _chk(self._L.rsim_render_depth(self.ptr, C.byref(cam), h, w, C.byref(opts), C.c_void_p(depth.data_ptr()), C.c_void_p(seg.data_ptr()) if segmentation else None))
         self._ray_fence_out()
         return (depth, seg) if segmentation else depth
+
+    # ---- inverse kinematics (include/rsim.h rsim_ik_site, csrc/rsim_ik.hip) --------------------------
+    def solve_ik(self, site, dofs, pos, quat=None, q_init=None, **opts):
+        """Which joint positions of `dofs` (dof ids: hinge / slide joints on the path to the site) put `site` at the target pose?  K damped least-squares
+        solves per env on the device, away from the simulation state (nothing of it is written).  pos: CUDA float32 [B, K, 3]; quat: [B, K, 4] wxyz, or None
+        for a position-only target; q_init: [B, K, n] start vectors, or None for the env's current joint positions.  2-D inputs mean K = 1 and give 2-D
+        results.  opts: damping, max_dq, max_iters, pos_tol, rot_tol, posture_gain, clamp_range (robosuite_amd.ik.DEFAULTS).
+        -> (q [B, K, n], err [B, K, 2] = |err_pos|, |omega| at q, iters int32 [B, K], converged bool [B, K]); q of a problem that did not converge is the
+        last iterate.  robosuite_amd/ik.py is the fp64 host mirror of the algorithm."""
+        import torch
+
+        from . import ik as _ik
+
+        try:
+            o = _ik.options(**opts)
+        except (TypeError, ValueError) as e:
+            raise RsimError(f"solve_ik: {e}") from None
+        dofs = [int(d) for d in np.asarray(dofs).ravel()]
+        n = len(dofs)
+        given = [("pos", pos, 3)] + ([("quat", quat, 4)] if quat is not None else []) + ([("q_init", q_init, n)] if q_init is not None else [])
+        for name, t, w in given:
+            if not (isinstance(t, torch.Tensor) and t.is_cuda):
+                raise RsimError(f"solve_ik: {name} must be a CUDA tensor")
+            if t.device.index != self.device:      # (the kernel is handed raw pointers: memory of another GPU is not its to read)
+                raise RsimError(f"solve_ik: {name} lives on {t.device}, the batch on cuda:{self.device}")
+        flat2 = pos.dim() == 2
+        K = 1 if flat2 else (int(pos.shape[1]) if pos.dim() == 3 else 0)
+        for name, t, w in given:
+            want = (self.B, w) if flat2 else (self.B, K, w)
+            if K < 1 or tuple(t.shape) != want:
+                raise RsimError(f"solve_ik: {name} must have shape ({self.B}, K, {w}) (or ({self.B}, {w}) for K = 1), got {tuple(t.shape)}")
+        f = lambda t: None if t is None else t.contiguous().float()      # noqa: E731
+        p, qt, qi = f(pos), f(quat), f(q_init)
+        dev = p.device
+        q = torch.empty((self.B, K, n), dtype=torch.float32, device=dev)
+        err = torch.empty((self.B, K, 2), dtype=torch.float32, device=dev)
+        it = torch.empty((self.B, K), dtype=torch.int32, device=dev)
+        co = IkOpts(o["damping"], o["max_dq"], o["pos_tol"], o["rot_tol"], o["posture_gain"], int(o["max_iters"]), int(bool(o["clamp_range"])))
+        P = lambda t: None if t is None else C.c_void_p(t.data_ptr())      # noqa: E731
+        self._ray_fence_in()
+        _chk(self._L.rsim_ik_site(self.ptr, int(site), n, (C.c_int32 * max(n, 1))(*dofs), K, P(p), P(qt), P(qi), C.byref(co), P(q), P(err), P(it)))
+        self._ray_fence_out()
+        conv = (it & (1 << 30)) != 0
+        it = it & ((1 << 30) - 1)
+        if flat2:
+            return q[:, 0], err[:, 0], it[:, 0], conv[:, 0]
+        return q, err, it, conv
 
     def set_schedule(self, longest_first=True):
         """Dispatch order of control_step: slowest envs of the previous step first (default) or identity."""

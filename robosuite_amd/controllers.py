@@ -75,6 +75,10 @@ class BatchState:
         """Depth (and `element` segmentation) image of every env on the body poses as they stand (HipBatch.render_depth)."""
         return self.batch.render_depth(camera, height, width, segmentation=segmentation, **opts)
 
+    def solve_ik(self, site, dofs, pos, quat=None, q_init=None, **opts):
+        """Inverse kinematics of `site` over `dofs` for every env, away from the state (HipBatch.solve_ik): -> (q, err, iters, converged)."""
+        return self.batch.solve_ik(site, dofs, pos, quat=quat, q_init=q_init, **opts)
+
     def body_dofs(self, body: int):
         """bool [nv]: the dofs that move `body` (its own joints and those of its ancestors)."""
         import torch
@@ -238,6 +242,74 @@ class TorchJointPositionController(BatchedController):
         if not self.use_torque_compensation:
             return want
         return torch.einsum("bij,bj->bi", self.mass_matrix, want) + self.torque_compensation
+
+
+class TorchIKPoseController(TorchJointPositionController):
+    """An inverse-kinematics action space on the plugin protocol: the action is a pose delta of the end effector, the device IK solver
+    (BatchState.solve_ik, csrc/rsim_ik.hip) turns it into joint targets, and the joint-position law of TorchJointPositionController tracks them.
+
+    THIS PROJECT'S DEFINITION of an IK action space, not a transcription of the reference's IK_POSE part controller (whose source was not at hand):
+      set_goal        the 6-vector (3 with control_ori=False) is scaled exactly as TorchOSCController.set_goal scales it -- a delta in the robot-base
+                      frame applied to the achieved pose (position delta added, axis-angle delta composed onto the current orientation) -- turned into a
+                      world-frame target, and solved with K = 1 from the current joint positions (`ik_opts`: the solver's options).  The solution becomes
+                      goal_qpos; in an env whose solve did not converge the goal stays what it was, and `ik_failures` counts these.
+      run_controller  inherited: M_part (kp (goal - q) - kd qd) + torque compensation.
+    eef_site / base_site: as for TorchOSCController."""
+
+    name = "IK_POSE"
+
+    def __init__(self, state, joint_indexes, actuator_range, eef_site, base_site, input_max=1, input_min=-1, output_max=(0.05, 0.05, 0.05, 0.5, 0.5, 0.5),
+                 output_min=(-0.05, -0.05, -0.05, -0.5, -0.5, -0.5), kp=50.0, damping_ratio=1.0, control_ori=True, ik_opts=None, **kw):
+        super().__init__(state, joint_indexes, actuator_range, kp=kp, damping_ratio=damping_ratio, **kw)
+        self.eef_site, self.base_site, self.use_ori = int(eef_site), int(base_site), bool(control_ori)
+        self.control_dim = 6 if self.use_ori else 3
+        self.input_max, self.input_min = np.broadcast_to(np.asarray(input_max, dtype=np.float32), (self.control_dim,)), np.broadcast_to(np.asarray(input_min, dtype=np.float32), (self.control_dim,))
+        self.output_max, self.output_min = np.asarray(output_max, dtype=np.float32)[:self.control_dim], np.asarray(output_min, dtype=np.float32)[:self.control_dim]
+        self.dofs = [int(d) for d in np.asarray(joint_indexes["qvel"]).ravel()]
+        self.ik_opts = dict(ik_opts or {})
+        self.ik_failures = 0
+        self.target_pos = self.target_quat = None
+
+    def target(self, action):
+        """the world-frame target the action asks for: (pos [B, 3], wxyz quat [B, 4] or None)"""
+        import torch
+
+        d = self.scale_action(action)
+        ep, eR = self.state.site_pose(self.eef_site)
+        op, oR = self.state.site_pose(self.base_site)
+        pos = ep + torch.einsum("bij,bj->bi", oR, d[:, :3])                                      # base-frame delta on the achieved position
+        if not self.use_ori:
+            return pos, None
+        ang = torch.linalg.norm(d[:, 3:6], dim=1, keepdim=True)
+        ax = d[:, 3:6] / torch.where(ang > 0, ang, torch.ones_like(ang))
+        w = torch.where(ang > 0, torch.cos(0.5 * ang), torch.ones_like(ang))
+        dq = torch.cat([w, ax * torch.sin(0.5 * ang)], dim=1)                                   # the delta rotation, base frame
+        Rw = torch.einsum("bij,bjk,blk,blm->bim", oR, BatchState.quat2mat(dq), oR, eR)          # oR dR oR^T eR
+        return pos, self.mat2quat(Rw)
+
+    @staticmethod
+    def mat2quat(R):
+        """rotation matrices [B, 3, 3] -> wxyz unit quaternions [B, 4] (the branch with the largest pivot, per env)"""
+        import torch
+
+        m = lambda i, j: R[:, i, j]      # noqa: E731
+        t = torch.stack([1 + m(0, 0) + m(1, 1) + m(2, 2), 1 + m(0, 0) - m(1, 1) - m(2, 2), 1 - m(0, 0) + m(1, 1) - m(2, 2), 1 - m(0, 0) - m(1, 1) + m(2, 2)], dim=1)
+        cand = torch.stack([torch.stack([t[:, 0], m(2, 1) - m(1, 2), m(0, 2) - m(2, 0), m(1, 0) - m(0, 1)], dim=1),
+                            torch.stack([m(2, 1) - m(1, 2), t[:, 1], m(0, 1) + m(1, 0), m(0, 2) + m(2, 0)], dim=1),
+                            torch.stack([m(0, 2) - m(2, 0), m(0, 1) + m(1, 0), t[:, 2], m(1, 2) + m(2, 1)], dim=1),
+                            torch.stack([m(1, 0) - m(0, 1), m(0, 2) + m(2, 0), m(1, 2) + m(2, 1), t[:, 3]], dim=1)], dim=1)      # [B, 4 branches, 4]
+        q = cand[torch.arange(R.shape[0], device=R.device), t.argmax(dim=1)]
+        return q / torch.linalg.norm(q, dim=1, keepdim=True)
+
+    def set_goal(self, action):
+        import torch
+
+        self.target_pos, self.target_quat = self.target(action)
+        q, err, iters, conv = self.state.solve_ik(self.eef_site, self.dofs, self.target_pos, self.target_quat, self.joint_pos.contiguous(), **self.ik_opts)
+        if self.limits is not None:
+            q = torch.minimum(torch.maximum(q, self.limits[0]), self.limits[1])
+        self.goal_qpos = torch.where(conv[:, None], q, self.goal_qpos)
+        self.ik_failures += int((~conv).sum())
 
 
 class TorchOSCController(BatchedController):

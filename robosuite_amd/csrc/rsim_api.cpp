@@ -85,6 +85,7 @@ extern "C" int rsim_launch_randomize(const DModel* m, const DBatch* b, const DDr
 #include "rsim_episode.h"
 #include "rsim_sensors.h"
 #include "rsim_ray.h"
+#include "rsim_ik.h"
 #include "rsim_hull.h"
 
 struct rsim_model;
@@ -225,6 +226,8 @@ struct rsim_batch {
   DRayGeom* d_ray_geom;  // [ngeom]
   float* d_ray_planes;   // [nplane][4] face planes of the mesh geoms' hulls
   int* d_ray_rf;         // [3][nsensor] rangefinders: site (-1: the sensor is none), its body, its first entry of a sensordata row
+  // inverse kinematics (rsim_ik.hip): the chain table of every (site, dofs) key solved so far, on the device (ik_chain) -- none for a batch that never solves
+  std::map<std::vector<int>, std::pair<int*, int>> ik_chains;   // (site, dof ids) -> (table, chain elements)
   float* d_sens_f;       // [nsensor][3] touch-site sizes; then [B][nq + nv + nu]: qpos / qvel / ctrl as they were ahead of a debug launch that integrates
   int ended_outside;     // rsim_end_episodes left needs_reset flags for the next rsim_control_step (fresh controllers); rsim_step2_last, which runs no in-kernel controller, drops them first
   // stream groups: control steps of env block g run on gstream[g]; `forked` = the group streams hold work the main stream has not waited for
@@ -1101,6 +1104,7 @@ extern "C" void rsim_batch_free(rsim_batch* b) {
   if (b->d_ray_geom) hipFree(b->d_ray_geom);
   if (b->d_ray_planes) hipFree(b->d_ray_planes);
   if (b->d_ray_rf) hipFree(b->d_ray_rf);
+  for (auto& kv : b->ik_chains) hipFree(kv.second.first);
   if (b->db.mprc) hipFree(b->db.mprc);
   if (b->db.jg) hipFree(b->db.jg);
   if (b->db.bpl) hipFree(b->db.bpl);
@@ -2089,6 +2093,104 @@ extern "C" int rsim_render_depth(rsim_batch* b, const rsim_camera* cam, int heig
   a.miss = INFINITY;
   a.dist = depth_dev; a.geomid = geomid_dev;
   return ray_launch(b, &a, "rsim_render_depth");
+}
+
+// ---- inverse kinematics (rsim_ik.hip, include/rsim.h rsim_ik_site) -------------------------------------------------------------------------------
+// The chain table of one (site, dofs) key (rsim_ik.h): the bodies from the world to the site's body in order, each followed by its joints, then the site.
+// Plain host code on the model's int tables; what the solver does not carry is refused here, by name.
+static std::string ik_joint_name(const rsim_model* m, int j) {
+  auto it = m->names.find("joint");
+  char buf[160];
+  if (it != m->names.end() && j < (int)it->second.size() && !it->second[j].empty()) snprintf(buf, sizeof(buf), "joint %d (%s)", j, it->second[j].c_str());
+  else snprintf(buf, sizeof(buf), "joint %d", j);
+  return buf;
+}
+static int ik_chain_build(const rsim_model* m, int site, int ndof, const int32_t* dofs, std::vector<int>* out, int* nel) {
+  const int *parent = m->I("body_parentid"), *jadr = m->I("body_jntadr"), *jnum = m->I("body_jntnum"), *jtype = m->I("jnt_type"), *qadr = m->I("jnt_qposadr"),
+            *dadr = m->I("jnt_dofadr"), *lim = m->I("jnt_limited"), *sb = m->I("site_bodyid"), *mocap = m->I("body_mocapid");
+  if (!parent || !jadr || !jnum || !jtype || !qadr || !dadr || !lim || !sb) return fail("rsim_ik_site: the model lacks a joint / body table");
+  for (int c = 0; c < ndof; c++) {
+    if (dofs[c] < 0 || dofs[c] >= m->nv) return fail("rsim_ik_site: controlled dof %d out of range (%d dofs)", dofs[c], m->nv);
+    for (int d = 0; d < c; d++) if (dofs[d] == dofs[c]) return fail("rsim_ik_site: dof %d is listed twice", dofs[c]);
+  }
+  std::vector<int> path;
+  for (int b = sb[site]; b > 0; b = parent[b]) {
+    if (b >= m->nbody || (int)path.size() >= m->nbody) return fail("rsim_ik_site: the body tree above site %d is malformed", site);
+    path.push_back(b);
+  }
+  if (path.size() > 64) return fail("rsim_ik_site: the chain to site %d passes %d bodies, more than 64", site, (int)path.size());
+  out->assign(RSIM_IK_HEAD, 0);
+  std::vector<int> found((size_t)ndof, -1);
+  auto push = [&](int kind, int o1, int o2, int qa, int col, int o3) { const int r[RSIM_IK_REC] = {kind, o1, o2, qa, col, o3, 0, 0}; out->insert(out->end(), r, r + RSIM_IK_REC); };
+  for (size_t k = path.size(); k-- > 0;) {
+    const int b = path[k];
+    if (mocap && mocap[b] >= 0) return fail("rsim_ik_site: body %d on the path to site %d is a mocap body", b, site);
+    push(IK_BODY, m->fo[FO_body_pos] + 3 * b, m->fo[FO_body_quat] + 4 * b, 0, -1, 0);
+    for (int j = jadr[b]; j < jadr[b] + jnum[b]; j++) {
+      if (j < 0 || j >= m->njnt) return fail("rsim_ik_site: body %d names joint %d of %d", b, j, m->njnt);
+      if (jtype[j] != IK_HINGE && jtype[j] != IK_SLIDE)
+        return fail("rsim_ik_site: %s on the path to site %d is a %s joint", ik_joint_name(m, j).c_str(), site, jtype[j] == 0 ? "free" : "ball");
+      int col = -1;
+      for (int c = 0; c < ndof; c++) if (dofs[c] == dadr[j]) col = c;
+      if (col >= 0) {
+        found[col] = j;
+        int* h = out->data() + 4 * col;
+        h[0] = m->fo[FO_jnt_range] + 2 * j; h[1] = lim[j] ? 1 : 0; h[2] = qadr[j]; h[3] = jtype[j];
+      }
+      push(jtype[j], m->fo[FO_jnt_pos] + 3 * j, m->fo[FO_jnt_axis] + 3 * j, qadr[j], col, m->fo[FO_qpos0] + qadr[j]);
+    }
+  }
+  push(IK_SITE, m->fo[FO_site_pos] + 3 * site, m->fo[FO_site_quat] + 4 * site, 0, -1, 0);
+  for (int c = 0; c < ndof; c++)
+    if (found[c] < 0) return fail("rsim_ik_site: controlled dof %d is not a hinge or slide joint on the path to site %d", dofs[c], site);
+  *nel = (int)((out->size() - RSIM_IK_HEAD) / RSIM_IK_REC);
+  return 0;
+}
+static int ik_chain(rsim_batch* b, int site, int ndof, const int32_t* dofs, const int** d_chain, int* nel) {
+  std::vector<int> key(1, site);
+  key.insert(key.end(), dofs, dofs + ndof);
+  auto it = b->ik_chains.find(key);
+  if (it == b->ik_chains.end()) {
+    std::vector<int> tab;
+    int n = 0;
+    if (ik_chain_build(b->m, site, ndof, dofs, &tab, &n)) return 1;
+    int* d = nullptr;
+    if (dalloc(&d, tab.size())) return 1;
+    HIPCHK(hipMemcpy(d, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
+    it = b->ik_chains.emplace(key, std::make_pair(d, n)).first;
+  }
+  *d_chain = it->second.first; *nel = it->second.second;
+  return 0;
+}
+extern "C" int rsim_ik_site(rsim_batch* b, int site, int ndof, const int32_t* dof_ids, int k, const float* target_pos_dev, const float* target_quat_dev,
+                            const float* q_init_dev, const rsim_ik_opts* opts, float* q_out_dev, float* err_dev, int32_t* iters_dev) {
+  if (!b) return fail("rsim_ik_site: batch is NULL");
+  if (ndof < 1 || ndof > RSIM_JNT_MAX) return fail("rsim_ik_site: ndof %d outside 1..%d", ndof, RSIM_JNT_MAX);
+  if (!dof_ids) return fail("rsim_ik_site: dof_ids is NULL");
+  if (k < 1) return fail("rsim_ik_site: k %d < 1", k);
+  if (!target_pos_dev) return fail("rsim_ik_site: target_pos_dev is NULL");
+  if (!q_out_dev || !err_dev || !iters_dev) return fail("rsim_ik_site: %s is NULL", !q_out_dev ? "q_out_dev" : !err_dev ? "err_dev" : "iters_dev");
+  if (site < 0 || site >= b->m->nsite) return fail("rsim_ik_site: site %d out of range (%d sites)", site, b->m->nsite);
+  if ((long long)k * b->B > 0x7fffffffLL / (4 * RSIM_JNT_MAX)) return fail("rsim_ik_site: %d problems per env x %d envs is more than one call carries", k, b->B);
+  const rsim_ik_opts def = {1e-4f, 0.5f, 1e-4f, 1e-3f, 0.f, 50, 1};
+  const rsim_ik_opts o = opts ? *opts : def;
+  if (!(o.damping >= 0.f) || !(o.max_dq > 0.f) || !(o.pos_tol >= 0.f) || !(o.rot_tol >= 0.f) || !(o.posture_gain >= 0.f) || o.max_iters < 0 || o.max_iters >= (1 << 30))
+    return fail("rsim_ik_site: option out of range (damping %g, max_dq %g, pos_tol %g, rot_tol %g, posture_gain %g, max_iters %d)", (double)o.damping, (double)o.max_dq,
+                (double)o.pos_tol, (double)o.rot_tol, (double)o.posture_gain, o.max_iters);
+  if (join_groups(b)) return 1;
+  HIPCHK(hipSetDevice(b->device));
+  DIk a;
+  memset(&a, 0, sizeof(a));
+  if (ik_chain(b, site, ndof, dof_ids, &a.chain, &a.nel)) return 1;
+  a.B = b->B; a.K = k; a.n = ndof; a.rows = target_quat_dev ? 6 : 3; a.nq = b->m->nq; a.fstride = b->dm.fstride;
+  a.ft = b->d_ft; a.qpos = b->db.qpos;
+  a.tpos = target_pos_dev; a.tquat = target_quat_dev; a.q_init = q_init_dev;
+  a.damping = o.damping; a.max_dq = o.max_dq; a.pos_tol = o.pos_tol; a.rot_tol = o.rot_tol; a.posture_gain = o.posture_gain;
+  a.max_iters = o.max_iters; a.clamp_range = o.clamp_range ? 1 : 0;
+  a.q_out = q_out_dev; a.err = err_dev; a.iters = iters_dev;
+  const int e = rsim_launch_ik(&a, b->stream);
+  if (e) return fail("rsim_ik_site: kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+  return 0;
 }
 
 // mj_fullM (controllers/parts/controller.py:226-227: `mujoco.mj_fullM(model, mass_matrix, data.qM)`): the dense joint-space inertia of one env

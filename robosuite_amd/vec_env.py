@@ -153,6 +153,22 @@ class VecEnv:
             return out
         return tuple(o.flip(1) for o in out) if segmentation else out.flip(1)
 
+    def solve_ik(self, pos, quat=None, arm=0, q_init=None, **opts):
+        """Which arm joint positions put the gripper site at this pose?  pos [n_envs, K, 3] / quat [n_envs, K, 4] (wxyz; None: position only) device tensors,
+        2-D for K = 1; q_init [n_envs, K, n] start vectors (None: the current joint positions) -> (q, err, iters, converged) (HipBatch.solve_ik).  Site and
+        dofs are those of the env's controller description: `eef_site` and the arm's `dof_idx`; arm=1: the second arm of a two-arm OSC description.  A query:
+        the simulation state is not touched -- hand `q` to a JOINT_POSITION action, or write it yourself."""
+        from .backend import ctrl_desc
+
+        d = ctrl_desc(self.env.cfg)
+        if arm == 0:
+            site, dofs = int(d.eef_site), [int(d.dof_idx[i]) for i in range(d.ndof) if d.part_of[i] == 0]
+        elif arm == 1 and d.narm == 2:
+            site, dofs = int(d.eef_site2), [int(d.dof_idx[8 + i]) for i in range(d.ndof2)]
+        else:
+            raise ValueError(f"solve_ik: the controller description has no arm {arm}")
+        return self.env.batch.solve_ik(site, dofs, pos, quat=quat, q_init=q_init, **opts)
+
     def enable_applied_forces(self, on: bool = True):
         """Honour `qfrc_applied` and `xfrc_applied` in `step` (off by default: the control step then reads neither).  An env that reports `done`
         has both rows zeroed for its next episode, in the same step, so a force written after seeing `done` acts on the new episode."""
