@@ -528,6 +528,48 @@ int rsim_ik_site(rsim_batch* b, int site, int ndof, const int32_t* dof_ids, int 
                  int32_t* iters_dev            /* [B][k]: updates made; bit 30 set = converged */);
 
 
+/* Signed distance and nearest points of geom pairs for the whole batch, on the device (csrc/rsim_dist.hip): MuJoCo's mj_geomDistance [3P, docs "API reference:
+ * mj_geomDistance"] for every env and every listed pair.  `pairs` is a HOST array [npair][2] of MODEL geom ids (any geom of the model, visual ones included).
+ *   dist     the Euclidean distance of the two solids when they are disjoint and closer than distmax.  A MESH GEOM IS ITS CONVEX HULL; a plane is the infinite
+ *            half-space below its +Z face, as in collision.
+ *   fromto   the nearest point on geom1, then the nearest point on geom2, world coordinates -- always oriented geom1 to geom2.
+ *   status   RSIM_DIST_OK (0): the pair is disjoint and closer than distmax, OR it overlaps and its signed distance is exact: one member is a plane (a plane
+ *            against any convex shape, in either slot of the pair), or both members are spheres or capsules.  dist is then minus the penetration depth and
+ *            fromto holds the deepest points.
+ *            RSIM_DIST_FAR (1): beyond distmax: dist = distmax and fromto is zero (MuJoCo's convention).
+ *            RSIM_DIST_OVERLAP (2): any other overlapping pair (box, cylinder, ellipsoid and mesh combinations, and a sphere or capsule against one of them):
+ *            dist = 0 and fromto is one common point, twice.  THE PENETRATION DEPTH OF GENERAL CONVEX SOLIDS IS NOT COMPUTED HERE; rsim_contacts reports the
+ *            depth the simulator itself uses.
+ *            RSIM_DIST_CAP (bit 8, or-ed in): the iteration stopped at max_iters before its bounds were within tol; dist and fromto are the best iterate,
+ *            still a valid upper bound of the distance.
+ * Algorithm: GJK on the Minkowski difference of the two cores (a sphere is a point, a capsule a segment; the radii come off at the end); each iteration has an
+ * upper and a lower bound on the distance and stops when their gap is <= tol (or fp32 resolves no further progress, which ends it as converged); a plane pair
+ * takes no iteration.  Every loop is bounded by max_iters (1 .. RSIM_DIST_MAX_ITERS) or a vertex count.
+ * Refused by name (rsim_last_error): a geom id out of range, a geom against itself, plane against plane, a mesh geom whose hull vertices the model does not
+ * hold (visual-only meshes: the limit ray casting has), a heightfield, npair < 1.
+ * Like rsim_ray: the body poses are those of RSIM_XPOS / RSIM_XQUAT, brought up to the current state first; geom sizes / offsets an env of a per_env_params
+ * batch has overridden are honoured; the call is asynchronous on the batch's stream and takes DEVICE pointers for its outputs; it is a pure query of the state.
+ * The pair table is uploaded by the first call that names that list and kept in the batch: a repeat call with the same list allocates nothing, and a batch that
+ * never asks holds and launches nothing.  robosuite_amd/distance.py is the fp64 host mirror.
+ * Not carried: MuJoCo's distance / normal / fromto SENSORS in sensordata, heightfields, a distance term inside IK or the fused step. */
+#define RSIM_DIST_OK 0
+#define RSIM_DIST_FAR 1
+#define RSIM_DIST_OVERLAP 2
+#define RSIM_DIST_CAP 256
+#define RSIM_DIST_MAX_ITERS 1024
+typedef struct rsim_dist_opts { float tol; int32_t max_iters; } rsim_dist_opts;
+/* defaults (opts == NULL): tol 1e-6 m on the gap between the iteration's upper and lower bound, max_iters 64.
+ * NOTE on tol: status 0 without bit 8 does NOT prove that the two bounds came within tol.  The iteration also ends, as converged, when the support point is one
+ * the simplex already holds or the upper bound no longer shrinks in fp32; the lower bound may then still be up to some 1e-4 m below (pairs a few 1e-4 m apart,
+ * curved shapes), while dist itself stays within about 1e-6 m of the fp64 value (profiles/distance_parity.txt).  Bit 8 reports the iteration cap only.
+ * NOTE on the pair table cache: one device table per distinct pair list is kept until rsim_batch_free, never evicted (as the IK chain tables are); a caller that
+ * builds a different list every step should ask for a superset list once instead. */
+int rsim_geom_distance(rsim_batch* b, int npair, const int32_t* pairs /* HOST [npair][2] */, float distmax,
+                       const rsim_dist_opts* opts /* NULL: defaults */,
+                       float* dist_dev            /* [B][npair] */,
+                       float* fromto_dev          /* [B][npair][6], or NULL */,
+                       int32_t* status_dev        /* [B][npair], or NULL */);
+
 #ifdef __cplusplus
 }
 #endif

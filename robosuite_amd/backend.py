@@ -273,6 +273,8 @@ def lib():
             L.rsim_render_depth.argtypes = [vp, C.POINTER(CameraDesc), C.c_int, C.c_int, C.POINTER(RayOpts), vp, vp]
         if hasattr(L, "rsim_ik_site"):
             L.rsim_ik_site.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, vp, vp, vp, C.POINTER(IkOpts), vp, vp, vp]
+        if hasattr(L, "rsim_geom_distance"):
+            L.rsim_geom_distance.argtypes = [vp, C.c_int, C.POINTER(C.c_int32), C.c_float, C.POINTER(DistOpts), vp, vp, vp]
         L.rsim_comm_unique_id.argtypes = [vp, C.c_size_t]
         L.rsim_comm_create.argtypes = [vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
         L.rsim_allreduce_stats.argtypes = [vp, vp, C.c_int, C.c_int]
@@ -468,6 +470,10 @@ class CameraDesc(C.Structure):   # include/rsim.h rsim_camera
 class IkOpts(C.Structure):       # include/rsim.h rsim_ik_opts
     _fields_ = [("damping", C.c_float), ("max_dq", C.c_float), ("pos_tol", C.c_float), ("rot_tol", C.c_float), ("posture_gain", C.c_float),
                 ("max_iters", C.c_int32), ("clamp_range", C.c_int32)]
+
+
+class DistOpts(C.Structure):     # include/rsim.h rsim_dist_opts
+    _fields_ = [("tol", C.c_float), ("max_iters", C.c_int32)]
 
 
 class _DevArray:
@@ -859,6 +865,38 @@ class HipBatch:
         if flat2:
             return q[:, 0], err[:, 0], it[:, 0], conv[:, 0]
         return q, err, it, conv
+
+    # ---- geom distance (include/rsim.h rsim_geom_distance, csrc/rsim_dist.hip) ------------------------
+    def geom_distance(self, pairs, distmax=1.0, fromto=True, tol=None, max_iters=None):
+        """mj_geomDistance for every env and every listed pair: pairs is an int array [P, 2] of MODEL geom ids (host).  -> (dist float32 [B, P], fromto
+        float32 [B, P, 6] -- the nearest point on geom1, then on geom2, world frame -- or None with fromto=False, status int32 [B, P]).  status 0: disjoint
+        and closer than distmax, or an overlap whose signed distance is exact (a plane pair; spheres / capsules among themselves): dist < 0 is then minus the
+        penetration depth; 1: beyond distmax (dist = distmax, fromto zero); 2: any other overlapping pair (dist = 0, fromto one common point twice: the depth
+        of general convex overlaps is not computed -- `contacts` reports the one the simulator uses); bit 8 (256): the iteration stopped at max_iters.  A mesh
+        geom is its convex hull.  tol (1e-6 m): the gap between the iteration's bounds at which it stops; max_iters (64).  A pure query of the state, on the
+        batch's stream; robosuite_amd/distance.py is the fp64 host mirror (and names the status codes)."""
+        import torch
+
+        from . import distance as _dist
+
+        try:
+            o = _dist.options(**{k: v for k, v in (("tol", tol), ("max_iters", max_iters)) if v is not None})
+        except (TypeError, ValueError) as e:
+            raise RsimError(str(e)) from None
+        p = np.ascontiguousarray(np.asarray(pairs), dtype=np.int32)
+        if p.ndim != 2 or p.shape[1] != 2 or p.shape[0] < 1:
+            raise RsimError(f"geom_distance: npair < 1 or pairs not of shape [P, 2] (got shape {tuple(p.shape)})")
+        n = int(p.shape[0])
+        dev = f"cuda:{self.device}"
+        dist = torch.empty((self.B, n), dtype=torch.float32, device=dev)
+        ft = torch.empty((self.B, n, 6), dtype=torch.float32, device=dev) if fromto else None
+        st = torch.empty((self.B, n), dtype=torch.int32, device=dev)
+        co = DistOpts(o["tol"], o["max_iters"])
+        self._ray_fence_in()
+        _chk(self._L.rsim_geom_distance(self.ptr, n, p.ctypes.data_as(C.POINTER(C.c_int32)), float(distmax), C.byref(co), C.c_void_p(dist.data_ptr()),
+                                        C.c_void_p(ft.data_ptr()) if fromto else None, C.c_void_p(st.data_ptr())))
+        self._ray_fence_out()
+        return dist, ft, st
 
     def set_schedule(self, longest_first=True):
         """Dispatch order of control_step: slowest envs of the previous step first (default) or identity."""

@@ -85,6 +85,7 @@ extern "C" int rsim_launch_randomize(const DModel* m, const DBatch* b, const DDr
 #include "rsim_episode.h"
 #include "rsim_sensors.h"
 #include "rsim_ray.h"
+#include "rsim_dist.h"
 #include "rsim_ik.h"
 #include "rsim_hull.h"
 
@@ -228,6 +229,8 @@ struct rsim_batch {
   int* d_ray_rf;         // [3][nsensor] rangefinders: site (-1: the sensor is none), its body, its first entry of a sensordata row
   // inverse kinematics (rsim_ik.hip): the chain table of every (site, dofs) key solved so far, on the device (ik_chain) -- none for a batch that never solves
   std::map<std::vector<int>, std::pair<int*, int>> ik_chains;   // (site, dof ids) -> (table, chain elements)
+  // geom distance (rsim_dist.hip): pair tables, one per pair list a call has named (dist_pairs) -- none for a batch that never asks
+  std::map<std::vector<int>, int*> dist_tables;   // (geom1, geom2, ...) -> [npair][RSIM_DIST_REC] on the device
   float* d_sens_f;       // [nsensor][3] touch-site sizes; then [B][nq + nv + nu]: qpos / qvel / ctrl as they were ahead of a debug launch that integrates
   int ended_outside;     // rsim_end_episodes left needs_reset flags for the next rsim_control_step (fresh controllers); rsim_step2_last, which runs no in-kernel controller, drops them first
   // stream groups: control steps of env block g run on gstream[g]; `forked` = the group streams hold work the main stream has not waited for
@@ -1105,6 +1108,7 @@ extern "C" void rsim_batch_free(rsim_batch* b) {
   if (b->d_ray_planes) hipFree(b->d_ray_planes);
   if (b->d_ray_rf) hipFree(b->d_ray_rf);
   for (auto& kv : b->ik_chains) hipFree(kv.second.first);
+  for (auto& kv : b->dist_tables) hipFree(kv.second);
   if (b->db.mprc) hipFree(b->db.mprc);
   if (b->db.jg) hipFree(b->db.jg);
   if (b->db.bpl) hipFree(b->db.bpl);
@@ -2190,6 +2194,77 @@ extern "C" int rsim_ik_site(rsim_batch* b, int site, int ndof, const int32_t* do
   a.q_out = q_out_dev; a.err = err_dev; a.iters = iters_dev;
   const int e = rsim_launch_ik(&a, b->stream);
   if (e) return fail("rsim_ik_site: kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+  return 0;
+}
+
+// ---- geom distance (rsim_dist.hip, include/rsim.h rsim_geom_distance) ----------------------------------------------------------------------------------
+// The pair table of one pair list: per pair the two geom ids and, for a mesh geom, where its hull vertices sit in DModel.mesh_vert.  What the query does not
+// carry is refused here, by name.  The geom records themselves are the ray kernel's scene table (ray_scene).
+static int dist_pairs(rsim_batch* b, int npair, const int32_t* pairs, const int** d_tab) {
+  std::vector<int> key(pairs, pairs + 2 * (size_t)npair);
+  auto it = b->dist_tables.find(key);
+  if (it == b->dist_tables.end()) {
+    const rsim_model* m = b->m;
+    const int *gt = m->I("geom_type"), *gd = m->I("geom_dataid");
+    if (!gt) return fail("rsim_geom_distance: the model has no geoms");
+    const int nmesh = (int)m->count("mesh_vertadr");
+    std::vector<int> tab((size_t)npair * RSIM_DIST_REC, 0);
+    for (int p = 0; p < npair; p++) {
+      const int g[2] = {pairs[2 * p], pairs[2 * p + 1]};
+      for (int k = 0; k < 2; k++)
+        if (g[k] < 0 || g[k] >= m->ngeom) return fail("rsim_geom_distance: pair %d: geom id %d out of range (%d geoms)", p, g[k], m->ngeom);
+      if (g[0] == g[1]) return fail("rsim_geom_distance: pair %d: geom %d against itself", p, g[0]);
+      if (gt[g[0]] == 0 && gt[g[1]] == 0) return fail("rsim_geom_distance: pair %d: plane against plane (%d, %d)", p, g[0], g[1]);
+      for (int k = 0; k < 2; k++) {
+        const int t = gt[g[k]];
+        tab[(size_t)p * RSIM_DIST_REC + k] = g[k];
+        if (t == 7) {
+          const int did = gd ? gd[g[k]] : -1;
+          if (did < 0 || did >= nmesh || !m->D("mesh_vert"))
+            return fail("rsim_geom_distance: pair %d: the model holds no hull vertices of mesh geom %d (a visual-only mesh)", p, g[k]);
+          const int adr = m->I("mesh_vertadr")[did], num = m->I("mesh_vertnum")[did];
+          if (adr < 0 || num < 1 || (size_t)(adr + num) * 3 > m->count("mesh_vert") || (size_t)(adr + num) * 3 > m->mesh_vert.size())
+            return fail("rsim_geom_distance: pair %d: hull of mesh %d out of range", p, did);
+          tab[(size_t)p * RSIM_DIST_REC + 2 + 2 * k] = adr; tab[(size_t)p * RSIM_DIST_REC + 3 + 2 * k] = num;
+        } else if (t != 0 && (t < 2 || t > 6))
+          return fail("rsim_geom_distance: pair %d: geom %d has type %d, which is not carried (heightfields are out of scope)", p, g[k], t);
+      }
+    }
+    int* d = nullptr;
+    if (dalloc(&d, tab.size())) return 1;
+    HIPCHK(hipMemcpy(d, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
+    it = b->dist_tables.emplace(key, d).first;
+  }
+  *d_tab = it->second;
+  return 0;
+}
+extern "C" int rsim_geom_distance(rsim_batch* b, int npair, const int32_t* pairs, float distmax, const rsim_dist_opts* opts, float* dist_dev, float* fromto_dev,
+                                  int32_t* status_dev) {
+  if (!b) return fail("rsim_geom_distance: batch is NULL");
+  if (npair < 1) return fail("rsim_geom_distance: npair %d < 1", npair);
+  if (!pairs) return fail("rsim_geom_distance: pairs is NULL");
+  if (!dist_dev) return fail("rsim_geom_distance: dist_dev is NULL");
+  if (!(distmax >= 0.f)) return fail("rsim_geom_distance: distmax %g is not >= 0", (double)distmax);
+  if ((long long)npair * b->B > 0x7fffffffLL / 6) return fail("rsim_geom_distance: %d pairs x %d envs is more than one call carries", npair, b->B);
+  if (((long long)b->B + RSIM_DIST_LANES - 1) / RSIM_DIST_LANES > 65535) return fail("rsim_geom_distance: more than %d envs in one batch", 65535 * RSIM_DIST_LANES);
+  const rsim_dist_opts def = {1e-6f, 64};
+  const rsim_dist_opts o = opts ? *opts : def;
+  if (!(o.tol >= 0.f) || o.max_iters < 1 || o.max_iters > RSIM_DIST_MAX_ITERS)
+    return fail("rsim_geom_distance: option out of range (tol %g, max_iters %d: 1..%d)", (double)o.tol, o.max_iters, RSIM_DIST_MAX_ITERS);
+  if (join_groups(b)) return 1;
+  HIPCHK(hipSetDevice(b->device));
+  DDist a;
+  memset(&a, 0, sizeof(a));
+  if (dist_pairs(b, npair, pairs, &a.pairs)) return 1;   // (refusals come before anything is launched)
+  if (refresh_derived(b, RSIM_XPOS) || ray_scene(b)) return 1;
+  const rsim_model* m = b->m;
+  a.B = b->B; a.npair = npair; a.nbody = m->nbody; a.fstride = b->dm.fstride;
+  a.fo_size = m->fo[FO_cg_size]; a.fo_pos = m->fo[FO_cg_pos]; a.fo_quat = m->fo[FO_cg_quat];
+  a.geom = b->d_ray_geom; a.mesh_vert = b->d_mesh; a.ft = b->d_ft; a.xpos = b->db.xpos; a.xquat = b->db.xquat;
+  a.distmax = distmax; a.tol = o.tol; a.max_iters = o.max_iters;
+  a.dist = dist_dev; a.fromto = fromto_dev; a.status = status_dev;
+  const int e = rsim_launch_dist(&a, b->stream);
+  if (e) return fail("rsim_geom_distance: kernel launch failed: %s", hipGetErrorString((hipError_t)e));
   return 0;
 }
 

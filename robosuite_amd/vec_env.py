@@ -153,6 +153,52 @@ class VecEnv:
             return out
         return tuple(o.flip(1) for o in out) if segmentation else out.flip(1)
 
+    def _geom_ids(self, pairs):
+        names = self.env.model.flat.names["geom"]
+        out = []
+        for pr in pairs:
+            if len(pr) != 2:
+                raise ValueError(f"geom_distance: a pair is two geoms, got {pr!r}")
+            ids = []
+            for g in pr:
+                if isinstance(g, str):
+                    if g not in names:
+                        raise KeyError(f"no geom named {g!r}")
+                    g = names.index(g)
+                ids.append(int(g))
+            out.append(ids)
+        return np.asarray(out, dtype=np.int32).reshape(-1, 2)
+
+    def geom_distance(self, pairs, distmax=1.0, fromto=True, **opts):
+        """mj_geomDistance for every env: pairs is a list of (geom, geom), each a geom name or a model geom id -> (dist [n_envs, P], fromto [n_envs, P, 6] or
+        None, status [n_envs, P]) device tensors (HipBatch.geom_distance: status codes, the convex-hull and overlap rules).  The first query after a fused
+        `step` runs one forward pass on the current state, as `raycast` does."""
+        return self.env.batch.geom_distance(self._geom_ids(pairs), distmax=distmax, fromto=fromto, **opts)
+
+    def body_distance(self, bodies_a, bodies_b, distmax=1.0, **opts):
+        """The smallest distance between two sets of bodies (names or ids) per env: all geom pairs (a geom of A, a geom of B) are queried and reduced with
+        torch.min.  -> (min dist [n_envs], its fromto [n_envs, 6], its pair index [n_envs], the pair list int32 [P, 2]).  GEOMS THE QUERY REFUSES ARE
+        SKIPPED: mesh geoms whose hull vertices the model does not hold (visual-only meshes), heightfields, a geom against itself, plane against plane
+        (distance.body_pairs).  With every pair beyond distmax the result is (distmax, zeros, 0)."""
+        import torch
+
+        from . import distance as _dist
+
+        flat = self.env.model.flat
+        bn = flat.names["body"]
+
+        def ids(bodies):
+            bodies = [bodies] if isinstance(bodies, (str, int, np.integer)) else list(bodies)
+            for b in bodies:
+                if isinstance(b, str) and b not in bn:
+                    raise KeyError(f"no body named {b!r}")
+            return [bn.index(b) if isinstance(b, str) else int(b) for b in bodies]
+
+        pairs = _dist.body_pairs(flat, ids(bodies_a), ids(bodies_b))
+        dist, ft, _ = self.env.batch.geom_distance(pairs, distmax=distmax, fromto=True, **opts)
+        d, k = torch.min(dist, dim=1)
+        return d, ft[torch.arange(ft.shape[0], device=ft.device), k], k, pairs
+
     def solve_ik(self, pos, quat=None, arm=0, q_init=None, **opts):
         """Which arm joint positions put the gripper site at this pose?  pos [n_envs, K, 3] / quat [n_envs, K, 4] (wxyz; None: position only) device tensors,
         2-D for K = 1; q_init [n_envs, K, n] start vectors (None: the current joint positions) -> (q, err, iters, converged) (HipBatch.solve_ik).  Site and
