@@ -570,6 +570,47 @@ int rsim_geom_distance(rsim_batch* b, int npair, const int32_t* pairs /* HOST [n
                        float* fromto_dev          /* [B][npair][6], or NULL */,
                        int32_t* status_dev        /* [B][npair], or NULL */);
 
+/* Configuration clearance for the whole batch, on the device (csrc/rsim_clear.hip): "is this joint configuration free, and by how much?" for k candidate joint
+ * vectors per env -- the body poses at each candidate (rsim_config_fk) and the smallest distance between what the candidate moves and everything it can hit
+ * (rsim_config_clearance), without writing the candidate into the state.  What rsim_ik_site returns goes straight in.
+ *   candidate   q[env][k][0..ndof): positions of the ndof controlled dofs (dof ids as for rsim_ik_site, 1 .. RSIM_JNT_MAX of them, each of a hinge or slide joint;
+ *               they need not lie on one chain: both arms of a two-arm robot in one call is a valid use).  EVERY OTHER JOINT IS HELD AT THE ENV'S CURRENT qpos:
+ *               free and ball joints, gripper fingers, objects.  No range clamp: the candidate is evaluated as given.
+ *   moved body  a body with a controlled joint on its path to the world; its dof signature is the set of controlled columns on that path.  A body that is not
+ *               moved keeps its pose of RSIM_XPOS / RSIM_XQUAT, brought up to the current state first, as every derived read is.
+ *   FK          the position stage's: body_pos / body_quat offsets, a hinge about its anchor jnt_pos, a slide along its axis, qpos - qpos0, a held ball joint's
+ *               quaternion as it stands -- on the env's OWN float table (per_env_params overrides, domain-randomisation draws), as in rsim_ik_site.
+ *   pairs       a HOST list [npair][2] of MODEL geom ids, taken as given: whatever rsim_geom_distance accepts, static pairs included, with its refusals.  Or NULL
+ *               with npair 0, THE DEFAULT LIST: the model's collision pairs (pair_geom1 / pair_geom2) whose two bodies have DIFFERENT dof signatures, in the
+ *               collision list's order.  That drops the pairs no candidate can change (floor against an object, finger against finger, the last link against
+ *               the hand welded to it) and skips, silently, the pairs the distance query refuses (visual-only meshes, heightfields, plane against plane).
+ *               rsim_config_pairs returns that list (host only); an empty default list is an error.
+ *   result      per (env, k): dist = the minimum over the list of the pair's rsim_geom_distance result at the candidate's poses, by the same rules (signed where
+ *               exact, 0 with status 2 for other overlaps, a mesh geom is its convex hull); pair = the index INTO THE LIST of the pair that attains it, the lowest
+ *               index on ties; fromto and status are that pair's (RSIM_DIST_CAP or-ed in when its iteration was capped).  With no pair closer than distmax:
+ *               dist = distmax, pair = -1, fromto zero, status RSIM_DIST_FAR.
+ * Kernels: lane = candidate env * k + j, 64 consecutive candidates per wavefront.  The FK pass leaves the poses of the moved bodies in a scratch the batch owns
+ * (grown on demand: a batch that never asks holds none); the distance pass runs a grid of (pair chunks, candidate blocks), each lane handing its running
+ * minimum to the pair routine as distmax, so that pairs which cannot beat it leave after an iteration or two; with more than one chunk a last small pass
+ * reduces the chunks' partial results in pair order.  opts->chunks forces the chunk count (0: chosen from B * k and the list length).
+ * Both device calls are asynchronous on the batch's stream and take DEVICE pointers in and out.  PURE QUERIES: qpos, every derived array and the stale marks stay
+ * as they are, but for the refresh a stale derived read always does.  The body table of a dof list and the pair table of a pair list are built and uploaded by
+ * the first call that names them and kept in the batch: a repeat call allocates nothing.
+ * Refused by name (rsim_last_error): ndof outside 1 .. RSIM_JNT_MAX, a dof id out of range or listed twice, a dof of a free or ball joint, a mocap body among the
+ * moved bodies, k < 1, the pair refusals of rsim_geom_distance, an empty default list.
+ * NOT HANDLED: A GRASPED OBJECT DOES NOT MOVE WITH THE CANDIDATE -- it is a free body at its current pose.  Also not carried: candidates for free or ball joints,
+ * swept checks along a path, a clearance term inside IK or the fused step, heightfields.  robosuite_amd/clearance.py is the fp64 host mirror. */
+typedef struct rsim_clear_opts { float tol; int32_t max_iters; int32_t chunks; } rsim_clear_opts;   /* NULL: rsim_dist defaults, chunks 0 = automatic */
+/* poses of ALL bodies at the candidates (unmoved bodies: the env's current pose) */
+int rsim_config_fk(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev /* [B][k][ndof] */,
+                   float* xpos_dev /* [B][k][nbody][3] */, float* xquat_dev /* [B][k][nbody][4] wxyz */);
+/* the default pair list of a dof list: writes up to max_pairs rows [..][2] of model geom ids, returns the count (-1 on error); host only */
+int rsim_config_pairs(const rsim_model* m, int ndof, const int32_t* dof_ids, int max_pairs, int32_t* pairs_out);
+int rsim_config_clearance(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev,
+                          int npair, const int32_t* pairs /* HOST [npair][2], or NULL with npair 0: the default list */,
+                          float distmax, const rsim_clear_opts* opts,
+                          float* dist_dev /* [B][k] */, int32_t* pair_dev /* [B][k] */, float* fromto_dev /* [B][k][6] or NULL */, int32_t* status_dev /* or NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -275,6 +275,10 @@ def lib():
             L.rsim_ik_site.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, vp, vp, vp, C.POINTER(IkOpts), vp, vp, vp]
         if hasattr(L, "rsim_geom_distance"):
             L.rsim_geom_distance.argtypes = [vp, C.c_int, C.POINTER(C.c_int32), C.c_float, C.POINTER(DistOpts), vp, vp, vp]
+        if hasattr(L, "rsim_config_clearance"):
+            L.rsim_config_fk.argtypes = [vp, C.c_int, C.POINTER(C.c_int32), C.c_int, vp, vp, vp]
+            L.rsim_config_pairs.argtypes = [vp, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32)]
+            L.rsim_config_clearance.argtypes = [vp, C.c_int, C.POINTER(C.c_int32), C.c_int, vp, C.c_int, C.POINTER(C.c_int32), C.c_float, C.POINTER(ClearOpts), vp, vp, vp, vp]
         L.rsim_comm_unique_id.argtypes = [vp, C.c_size_t]
         L.rsim_comm_create.argtypes = [vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
         L.rsim_allreduce_stats.argtypes = [vp, vp, C.c_int, C.c_int]
@@ -474,6 +478,10 @@ class IkOpts(C.Structure):       # include/rsim.h rsim_ik_opts
 
 class DistOpts(C.Structure):     # include/rsim.h rsim_dist_opts
     _fields_ = [("tol", C.c_float), ("max_iters", C.c_int32)]
+
+
+class ClearOpts(C.Structure):    # include/rsim.h rsim_clear_opts
+    _fields_ = [("tol", C.c_float), ("max_iters", C.c_int32), ("chunks", C.c_int32)]
 
 
 class _DevArray:
@@ -897,6 +905,90 @@ class HipBatch:
                                         C.c_void_p(ft.data_ptr()) if fromto else None, C.c_void_p(st.data_ptr())))
         self._ray_fence_out()
         return dist, ft, st
+
+    # ---- configuration clearance (include/rsim.h rsim_config_fk / rsim_config_pairs / rsim_config_clearance, csrc/rsim_clear.hip) ------------------
+    def _config_q(self, who, dofs, q):
+        """the argument checks of solve_ik: -> (dof ids, contiguous float32 q [B, K, n], K, whether the caller's tensors are 2-D)"""
+        import torch
+
+        dofs = [int(d) for d in np.asarray(dofs).ravel()]
+        n = len(dofs)
+        if not (isinstance(q, torch.Tensor) and q.is_cuda):
+            raise RsimError(f"{who}: q must be a CUDA tensor")
+        if q.device.index != self.device:      # (the kernel is handed raw pointers: memory of another GPU is not its to read)
+            raise RsimError(f"{who}: q lives on {q.device}, the batch on cuda:{self.device}")
+        flat2 = q.dim() == 2
+        K = 1 if flat2 else (int(q.shape[1]) if q.dim() == 3 else 0)
+        if K < 1 or n < 1 or tuple(q.shape) != ((self.B, n) if flat2 else (self.B, K, n)):
+            raise RsimError(f"{who}: q must have shape ({self.B}, K, {n}) with K >= 1 (or ({self.B}, {n}) for K = 1), got {tuple(q.shape)}")
+        return dofs, q.contiguous().float().reshape(self.B, K, n), K, flat2
+
+    def config_fk(self, dofs, q):
+        """Body poses at candidate joint vectors, away from the state: q is a CUDA float32 tensor [B, K, n] of positions of the controlled `dofs` (dof ids of
+        hinge / slide joints, as for solve_ik; they need not lie on one chain), or [B, n] for K = 1.  Every other joint is held at the env's current qpos; no
+        range clamp.  -> (xpos [B, K, nbody, 3], xquat [B, K, nbody, 4] wxyz) of ALL bodies ([B, nbody, .] for 2-D q); a body the dofs do not move reads the
+        env's current pose.  FK on each env's own model parameters; a pure query on the batch's stream.  robosuite_amd/clearance.py is the fp64 mirror."""
+        import torch
+
+        dofs, qc, K, flat2 = self._config_q("config_fk", dofs, q)
+        nb = int(self.model.flat.nbody)
+        xp = torch.empty((self.B, K, nb, 3), dtype=torch.float32, device=qc.device)
+        xq = torch.empty((self.B, K, nb, 4), dtype=torch.float32, device=qc.device)
+        self._ray_fence_in()
+        _chk(self._L.rsim_config_fk(self.ptr, len(dofs), (C.c_int32 * len(dofs))(*dofs), K, C.c_void_p(qc.data_ptr()), C.c_void_p(xp.data_ptr()), C.c_void_p(xq.data_ptr())))
+        self._ray_fence_out()
+        return (xp[:, 0], xq[:, 0]) if flat2 else (xp, xq)
+
+    def config_pairs(self, dofs):
+        """The default pair list of config_clearance for `dofs`: int32 [P, 2] model geom ids -- the model's collision pairs whose two bodies the candidate can
+        move relative to each other (different dof signatures), in the collision list's order, without the pairs geom_distance refuses."""
+        dofs = [int(d) for d in np.asarray(dofs).ravel()]
+        arr = (C.c_int32 * max(len(dofs), 1))(*dofs)
+        n = self._L.rsim_config_pairs(self.model.ptr, len(dofs), arr, 0, None)
+        if n < 0:
+            raise RsimError(lib().rsim_last_error().decode())
+        out = np.zeros((n, 2), dtype=np.int32)
+        if self._L.rsim_config_pairs(self.model.ptr, len(dofs), arr, n, out.ctypes.data_as(C.POINTER(C.c_int32))) != n:
+            raise RsimError(lib().rsim_last_error().decode())
+        return out
+
+    def config_clearance(self, dofs, q, pairs=None, distmax=1.0, fromto=True, tol=None, max_iters=None, chunks=0):
+        """Is this joint configuration free, and by how much?  For K candidate joint vectors per env (q, dofs: as config_fk) the smallest distance between the
+        geoms of `pairs` at the candidate's poses: pairs is an int array [P, 2] of MODEL geom ids (host; anything geom_distance accepts), or None for the
+        default list (config_pairs).  -> (dist float32 [B, K], pair int32 [B, K] -- the index INTO THE LIST of the pair that attains dist, the lowest on ties
+        --, fromto float32 [B, K, 6] of that pair or None with fromto=False, status int32 [B, K] of that pair); 2-D q gives [B] / [B, 6].  dist follows
+        geom_distance: signed where exact, 0 with status 2 for other overlaps, a mesh geom is its convex hull; with no pair closer than distmax:
+        (distmax, -1, zeros, 1).  chunks: into how many pieces the pair list is cut for the device (0 = chosen from B K and P).  A grasped object does NOT move
+        with the candidate.  A pure query on the batch's stream; robosuite_amd/clearance.py is the fp64 host mirror."""
+        import torch
+
+        from . import distance as _dist
+
+        try:
+            o = _dist.options(**{k: v for k, v in (("tol", tol), ("max_iters", max_iters)) if v is not None})
+        except (TypeError, ValueError) as e:
+            raise RsimError(str(e).replace("geom_distance", "config_clearance")) from None
+        dofs, qc, K, flat2 = self._config_q("config_clearance", dofs, q)
+        if pairs is None:
+            n, parg = 0, None
+        else:
+            p = np.ascontiguousarray(np.asarray(pairs), dtype=np.int32)
+            if p.ndim != 2 or p.shape[1] != 2 or p.shape[0] < 1:
+                raise RsimError(f"config_clearance: npair < 1 or pairs not of shape [P, 2] (got shape {tuple(p.shape)})")
+            n, parg = int(p.shape[0]), p.ctypes.data_as(C.POINTER(C.c_int32))
+        dev = qc.device
+        dist = torch.empty((self.B, K), dtype=torch.float32, device=dev)
+        pid = torch.empty((self.B, K), dtype=torch.int32, device=dev)
+        ft = torch.empty((self.B, K, 6), dtype=torch.float32, device=dev) if fromto else None
+        st = torch.empty((self.B, K), dtype=torch.int32, device=dev)
+        co = ClearOpts(o["tol"], o["max_iters"], int(chunks))
+        self._ray_fence_in()
+        _chk(self._L.rsim_config_clearance(self.ptr, len(dofs), (C.c_int32 * len(dofs))(*dofs), K, C.c_void_p(qc.data_ptr()), n, parg, float(distmax), C.byref(co),
+                                           C.c_void_p(dist.data_ptr()), C.c_void_p(pid.data_ptr()), C.c_void_p(ft.data_ptr()) if fromto else None, C.c_void_p(st.data_ptr())))
+        self._ray_fence_out()
+        if flat2:
+            return dist[:, 0], pid[:, 0], (ft[:, 0] if fromto else None), st[:, 0]
+        return dist, pid, ft, st
 
     def set_schedule(self, longest_first=True):
         """Dispatch order of control_step: slowest envs of the previous step first (default) or identity."""

@@ -84,6 +84,19 @@ class BatchState:
         """Inverse kinematics of `site` over `dofs` for every env, away from the state (HipBatch.solve_ik): -> (q, err, iters, converged)."""
         return self.batch.solve_ik(site, dofs, pos, quat=quat, q_init=q_init, **opts)
 
+    def config_fk(self, dofs, q):
+        """Body poses at candidate joint vectors of `dofs`, away from the state (HipBatch.config_fk): -> (xpos, xquat).  Valid between step1 and step2."""
+        return self.batch.config_fk(dofs, q)
+
+    def config_pairs(self, dofs):
+        """The default pair list of config_clearance for `dofs` (HipBatch.config_pairs): int32 [P, 2] model geom ids."""
+        return self.batch.config_pairs(dofs)
+
+    def config_clearance(self, dofs, q, pairs=None, distmax=1.0, **opts):
+        """The smallest distance over `pairs` at candidate joint vectors of `dofs`, away from the state (HipBatch.config_clearance): -> (dist, pair, fromto,
+        status).  Unmoved bodies are at the poses as they stand: valid between step1 and step2, like the other views."""
+        return self.batch.config_clearance(dofs, q, pairs=pairs, distmax=distmax, **opts)
+
     def body_dofs(self, body: int):
         """bool [nv]: the dofs that move `body` (its own joints and those of its ancestors)."""
         import torch

@@ -87,6 +87,8 @@ extern "C" int rsim_launch_randomize(const DModel* m, const DBatch* b, const DDr
 #include "rsim_ray.h"
 #include "rsim_dist.h"
 #include "rsim_ik.h"
+#include "rsim_clear.h"
+#include "rsim_clear_core.h"
 #include "rsim_hull.h"
 
 struct rsim_model;
@@ -144,6 +146,9 @@ struct rsim_model {
 };
 
 enum { TIER_NONE, TIER_FUSED, TIER_LIST };   // rsim_batch.tier
+
+// configuration clearance (rsim_clear.hip): what the batch keeps per dof list -- the body table and the slot of every body on the device, and the default pair list
+struct ClearTab { int *d_tab, *d_slot; int nel, nslot; std::vector<int> def_pairs; };
 
 struct rsim_batch {
   rsim_model* m;
@@ -231,6 +236,11 @@ struct rsim_batch {
   std::map<std::vector<int>, std::pair<int*, int>> ik_chains;   // (site, dof ids) -> (table, chain elements)
   // geom distance (rsim_dist.hip): pair tables, one per pair list a call has named (dist_pairs) -- none for a batch that never asks
   std::map<std::vector<int>, int*> dist_tables;   // (geom1, geom2, ...) -> [npair][RSIM_DIST_REC] on the device
+  // configuration clearance (rsim_clear.hip): body tables per dof list (clear_table), and the scratch of the moved bodies' poses and of the pair chunks' partial
+  // results, grown on demand -- none for a batch that never asks
+  std::map<std::vector<int>, ClearTab> clear_tabs;
+  float *d_clear_scr, *d_clear_part;
+  size_t clear_scr_n, clear_part_n;   // floats held
   float* d_sens_f;       // [nsensor][3] touch-site sizes; then [B][nq + nv + nu]: qpos / qvel / ctrl as they were ahead of a debug launch that integrates
   int ended_outside;     // rsim_end_episodes left needs_reset flags for the next rsim_control_step (fresh controllers); rsim_step2_last, which runs no in-kernel controller, drops them first
   // stream groups: control steps of env block g run on gstream[g]; `forked` = the group streams hold work the main stream has not waited for
@@ -1109,6 +1119,9 @@ extern "C" void rsim_batch_free(rsim_batch* b) {
   if (b->d_ray_rf) hipFree(b->d_ray_rf);
   for (auto& kv : b->ik_chains) hipFree(kv.second.first);
   for (auto& kv : b->dist_tables) hipFree(kv.second);
+  for (auto& kv : b->clear_tabs) { hipFree(kv.second.d_tab); hipFree(kv.second.d_slot); }
+  if (b->d_clear_scr) hipFree(b->d_clear_scr);
+  if (b->d_clear_part) hipFree(b->d_clear_part);
   if (b->db.mprc) hipFree(b->db.mprc);
   if (b->db.jg) hipFree(b->db.jg);
   if (b->db.bpl) hipFree(b->db.bpl);
@@ -2265,6 +2278,195 @@ extern "C" int rsim_geom_distance(rsim_batch* b, int npair, const int32_t* pairs
   a.dist = dist_dev; a.fromto = fromto_dev; a.status = status_dev;
   const int e = rsim_launch_dist(&a, b->stream);
   if (e) return fail("rsim_geom_distance: kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+  return 0;
+}
+
+// ---- configuration clearance (rsim_clear.hip, include/rsim.h rsim_config_fk / rsim_config_pairs / rsim_config_clearance) -----------------------------------
+// Plain host code on the model's int tables: which bodies a dof list moves and with which controlled columns on their path (the dof signature), the body table
+// the FK walk reads (rsim_clear_core.h), and the default pair list.  What the query does not carry is refused here, by name.
+struct ClearPlan {
+  std::vector<unsigned> sig;   // [nbody] bit c set: controlled column c is on the body's path to the world
+  std::vector<int> tab, slot;  // the body table; [nbody] slot of a moved body or -1
+  int nel, nslot;
+};
+static int clear_plan(const rsim_model* m, const char* who, int ndof, const int32_t* dofs, ClearPlan* out) {
+  const int *parent = m->I("body_parentid"), *jadr = m->I("body_jntadr"), *jnum = m->I("body_jntnum"), *jtype = m->I("jnt_type"), *qadr = m->I("jnt_qposadr"),
+            *dadr = m->I("jnt_dofadr"), *mocap = m->I("body_mocapid");
+  if (!parent || !jadr || !jnum || !jtype || !qadr || !dadr) return fail("%s: the model lacks a joint / body table", who);
+  if (ndof < 1 || ndof > RSIM_JNT_MAX) return fail("%s: ndof %d outside 1..%d", who, ndof, RSIM_JNT_MAX);
+  if (!dofs) return fail("%s: dof_ids is NULL", who);
+  std::vector<int> col_of_jnt((size_t)m->njnt, -1);
+  for (int c = 0; c < ndof; c++) {
+    if (dofs[c] < 0 || dofs[c] >= m->nv) return fail("%s: controlled dof %d out of range (%d dofs)", who, dofs[c], m->nv);
+    for (int d = 0; d < c; d++) if (dofs[d] == dofs[c]) return fail("%s: dof %d is listed twice", who, dofs[c]);
+    int j = -1;
+    for (int k = 0; k < m->njnt; k++) {
+      const int w = jtype[k] == 0 ? 6 : jtype[k] == 1 ? 3 : 1;
+      if (dofs[c] >= dadr[k] && dofs[c] < dadr[k] + w) j = k;
+    }
+    if (j < 0) return fail("%s: controlled dof %d belongs to no joint", who, dofs[c]);
+    if (jtype[j] != rsim_clear::CL_HINGE && jtype[j] != rsim_clear::CL_SLIDE)
+      return fail("%s: controlled dof %d belongs to %s, a %s joint (hinge and slide joints only)", who, dofs[c], ik_joint_name(m, j).c_str(), jtype[j] == 0 ? "free" : "ball");
+    col_of_jnt[j] = c;
+  }
+  out->sig.assign((size_t)m->nbody, 0u);
+  out->slot.assign((size_t)m->nbody, -1);
+  out->tab.clear();
+  out->nel = out->nslot = 0;
+  auto push = [&](int kind, int o1, int o2, int id, int col, int o3, int slot, int pbody) {
+    const int r[RSIM_CLEAR_REC] = {kind, o1, o2, id, col, o3, slot, pbody};
+    out->tab.insert(out->tab.end(), r, r + RSIM_CLEAR_REC);
+    out->nel++;
+  };
+  for (int b = 1; b < m->nbody; b++) {
+    const int p = parent[b];
+    if (p < 0 || p >= b) return fail("%s: body %d names parent %d: the body tree is not in topological order", who, b, p);
+    unsigned s = out->sig[p];
+    for (int j = jadr[b]; j < jadr[b] + jnum[b]; j++) {
+      if (j < 0 || j >= m->njnt) return fail("%s: body %d names joint %d of %d", who, b, j, m->njnt);
+      if (col_of_jnt[j] >= 0) s |= 1u << col_of_jnt[j];
+    }
+    out->sig[b] = s;
+    if (!s) continue;
+    if (mocap && mocap[b] >= 0) return fail("%s: body %d, which the controlled dofs move, is a mocap body", who, b);
+    out->slot[b] = out->nslot;
+    push(rsim_clear::CL_BODY, m->fo[FO_body_pos] + 3 * b, m->fo[FO_body_quat] + 4 * b, b, out->slot[p], 0, out->nslot, p);
+    out->nslot++;
+    for (int j = jadr[b]; j < jadr[b] + jnum[b]; j++) {
+      if (jtype[j] == 0) return fail("%s: %s of body %d, which the controlled dofs move, is a free joint", who, ik_joint_name(m, j).c_str(), b);
+      push(jtype[j], m->fo[FO_jnt_pos] + 3 * j, m->fo[FO_jnt_axis] + 3 * j, qadr[j], col_of_jnt[j], jtype[j] == 1 ? 0 : m->fo[FO_qpos0] + qadr[j], 0, 0);
+    }
+  }
+  return 0;
+}
+// the default pair list: the model's collision pairs whose two bodies have different dof signatures, in the collision list's order; pairs the distance query
+// refuses (visual-only meshes, heightfields, plane against plane) are skipped
+static int clear_default_pairs(const rsim_model* m, const char* who, const ClearPlan& plan, std::vector<int>* out) {
+  const int *g1 = m->I("pair_geom1"), *g2 = m->I("pair_geom2"), *gt = m->I("geom_type"), *gb = m->I("geom_bodyid"), *gd = m->I("geom_dataid");
+  out->clear();
+  const int nmesh = (int)m->count("mesh_vertadr");
+  auto carried = [&](int g) {
+    if (g < 0 || g >= m->ngeom || gb[g] < 0 || gb[g] >= m->nbody) return false;
+    if (gt[g] == 7) return gd && gd[g] >= 0 && gd[g] < nmesh && m->D("mesh_vert") != nullptr;
+    return gt[g] == 0 || (gt[g] >= 2 && gt[g] <= 6);
+  };
+  if (g1 && g2 && gt && gb)
+    for (int p = 0; p < m->npair; p++) {
+      const int a = g1[p], c = g2[p];
+      if (a == c || !carried(a) || !carried(c) || (gt[a] == 0 && gt[c] == 0)) continue;
+      if (plan.sig[gb[a]] == plan.sig[gb[c]]) continue;   // the candidate cannot change this pair's relative pose
+      out->push_back(a); out->push_back(c);
+    }
+  if (out->empty()) return fail("%s: the default pair list is empty: no collision pair of the model depends on the controlled dofs", who);
+  return 0;
+}
+extern "C" int rsim_config_pairs(const rsim_model* m, int ndof, const int32_t* dof_ids, int max_pairs, int32_t* pairs_out) {
+  if (!m) { fail("rsim_config_pairs: model is NULL"); return -1; }
+  ClearPlan plan;
+  std::vector<int> pairs;
+  if (clear_plan(m, "rsim_config_pairs", ndof, dof_ids, &plan) || clear_default_pairs(m, "rsim_config_pairs", plan, &pairs)) return -1;
+  const int n = (int)(pairs.size() / 2);
+  if (pairs_out && max_pairs > 0) memcpy(pairs_out, pairs.data(), sizeof(int32_t) * 2 * (size_t)std::min(n, max_pairs));
+  return n;
+}
+static int clear_table(rsim_batch* b, const char* who, int ndof, const int32_t* dofs, const ClearTab** out) {
+  if (ndof < 1 || ndof > RSIM_JNT_MAX) return fail("%s: ndof %d outside 1..%d", who, ndof, RSIM_JNT_MAX);
+  if (!dofs) return fail("%s: dof_ids is NULL", who);
+  std::vector<int> key(dofs, dofs + ndof);
+  auto it = b->clear_tabs.find(key);
+  if (it == b->clear_tabs.end()) {
+    ClearPlan plan;
+    if (clear_plan(b->m, who, ndof, dofs, &plan)) return 1;
+    ClearTab t;
+    t.d_tab = t.d_slot = nullptr; t.nel = plan.nel; t.nslot = plan.nslot;
+    if (clear_default_pairs(b->m, who, plan, &t.def_pairs)) t.def_pairs.clear();   // (an error only for a call that asks for the default list)
+    if (dalloc(&t.d_tab, plan.tab.size()) || dalloc(&t.d_slot, plan.slot.size())) return 1;
+    HIPCHK(hipMemcpy(t.d_tab, plan.tab.data(), plan.tab.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(t.d_slot, plan.slot.data(), plan.slot.size() * sizeof(int), hipMemcpyHostToDevice));
+    it = b->clear_tabs.emplace(key, t).first;
+  }
+  *out = &it->second;
+  return 0;
+}
+// batch-owned scratch, grown on demand (the stream is drained first: a launch before may still read the old block)
+static int clear_grow(rsim_batch* b, float** p, size_t* have, size_t want) {
+  if (*have >= want) return 0;
+  HIPCHK(hipStreamSynchronize(b->stream));
+  if (*p) HIPCHK(hipFree(*p));
+  *p = nullptr; *have = 0;
+  HIPCHK(hipMalloc((void**)p, want * sizeof(float)));
+  *have = want;
+  return 0;
+}
+static int clear_args(rsim_batch* b, const char* who, int ndof, const int32_t* dof_ids, int k, const float* q_dev, DClear* a, const ClearTab** tab) {
+  if (k < 1) return fail("%s: k %d < 1", who, k);
+  if (!q_dev) return fail("%s: q_dev is NULL", who);
+  if ((long long)k * b->B > (long long)65535 * RSIM_CLEAR_LANES || (long long)k * b->B * b->m->nbody > 0x7fffffffLL / 4)
+    return fail("%s: %d candidates per env x %d envs is more than one call carries", who, k, b->B);
+  if (join_groups(b)) return 1;
+  HIPCHK(hipSetDevice(b->device));
+  if (clear_table(b, who, ndof, dof_ids, tab)) return 1;
+  const rsim_model* m = b->m;
+  memset(a, 0, sizeof(*a));
+  a->B = b->B; a->K = k; a->n = ndof; a->NC = b->B * k; a->nbody = m->nbody; a->nq = m->nq; a->fstride = b->dm.fstride;
+  a->nel = (*tab)->nel; a->nslot = (*tab)->nslot; a->tab = (*tab)->d_tab; a->slot_of_body = (*tab)->d_slot;
+  a->ft = b->d_ft; a->qpos = b->db.qpos; a->xpos = b->db.xpos; a->xquat = b->db.xquat; a->q = q_dev;
+  return 0;
+}
+extern "C" int rsim_config_fk(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, float* xpos_dev, float* xquat_dev) {
+  if (!b) return fail("rsim_config_fk: batch is NULL");
+  if (!xpos_dev || !xquat_dev) return fail("rsim_config_fk: %s is NULL", !xpos_dev ? "xpos_dev" : "xquat_dev");
+  DClear a;
+  const ClearTab* tab;
+  if (clear_args(b, "rsim_config_fk", ndof, dof_ids, k, q_dev, &a, &tab)) return 1;
+  if (refresh_derived(b, RSIM_XPOS)) return 1;
+  a.xpos_out = xpos_dev; a.xquat_out = xquat_dev;
+  const int e = rsim_launch_clear_fk(&a, b->stream);
+  if (e) return fail("rsim_config_fk: kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+  return 0;
+}
+extern "C" int rsim_config_clearance(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, int npair, const int32_t* pairs, float distmax,
+                                     const rsim_clear_opts* opts, float* dist_dev, int32_t* pair_dev, float* fromto_dev, int32_t* status_dev) {
+  const char* who = "rsim_config_clearance";
+  if (!b) return fail("%s: batch is NULL", who);
+  if (!dist_dev || !pair_dev) return fail("%s: %s is NULL", who, !dist_dev ? "dist_dev" : "pair_dev");
+  if (!(distmax >= 0.f)) return fail("%s: distmax %g is not >= 0", who, (double)distmax);
+  if (npair < 0 || (npair > 0 && !pairs) || (npair == 0 && pairs)) return fail("%s: npair %d with pairs %s (a list of npair >= 1 pairs, or NULL and 0 for the default list)", who, npair, pairs ? "given" : "NULL");
+  const rsim_clear_opts def = {1e-6f, 64, 0};
+  const rsim_clear_opts o = opts ? *opts : def;
+  if (!(o.tol >= 0.f) || o.max_iters < 1 || o.max_iters > RSIM_DIST_MAX_ITERS || o.chunks < 0)
+    return fail("%s: option out of range (tol %g, max_iters %d: 1..%d, chunks %d: >= 0)", who, (double)o.tol, o.max_iters, RSIM_DIST_MAX_ITERS, o.chunks);
+  DClear a;
+  const ClearTab* tab;
+  if (clear_args(b, who, ndof, dof_ids, k, q_dev, &a, &tab)) return 1;
+  if (!pairs) {
+    if (tab->def_pairs.empty()) return fail("%s: the default pair list is empty: no collision pair of the model depends on the controlled dofs", who);
+    npair = (int)(tab->def_pairs.size() / 2); pairs = tab->def_pairs.data();
+  }
+  if (dist_pairs(b, npair, pairs, &a.pairs)) return 1;   // (refusals come before anything is launched)
+  if (refresh_derived(b, RSIM_XPOS) || ray_scene(b)) return 1;
+  const rsim_model* m = b->m;
+  const int waves = (a.NC + RSIM_CLEAR_LANES - 1) / RSIM_CLEAR_LANES;
+  // automatic, from the sweep in profiles/clearance_bench.txt (Lift @4096, 128 pairs).  Every cut costs pruning -- a chunk starts its minimum at distmax again --
+  // and once each SIMD of the part has a wavefront (256 CUs x 4 = RSIM_CLEAR_FULL candidate blocks) that is all a cut does: K = 16 and 64 are fastest with ONE
+  // chunk (15 ms against 43 ms with 8).  Far below that the part stands empty behind a few wavefronts that walk the whole list: K = 1 (64 blocks) is fastest with
+  // one pair per chunk (3.7 ms against 12.6 ms).  Between the two measured ends the count falls with the square of the fill: r = FULL / blocks, chunks = r * r.
+  const int fill = RSIM_CLEAR_FULL / waves;
+  int chunks = o.chunks > 0 ? o.chunks : std::max(1, fill * fill);
+  chunks = std::max(1, std::min(std::min(chunks, npair), RSIM_CLEAR_MAX_CHUNKS));
+  const int per = (npair + chunks - 1) / chunks;
+  chunks = (npair + per - 1) / per;   // (no empty chunk)
+  if (clear_grow(b, &b->d_clear_scr, &b->clear_scr_n, (size_t)a.nslot * 7 * a.NC)) return 1;
+  if (chunks > 1 && clear_grow(b, &b->d_clear_part, &b->clear_part_n, (size_t)chunks * RSIM_CLEAR_PART * a.NC)) return 1;
+  a.scr = b->d_clear_scr; a.part = b->d_clear_part;
+  a.npair = npair; a.chunks = chunks;
+  a.fo_size = m->fo[FO_cg_size]; a.fo_pos = m->fo[FO_cg_pos]; a.fo_quat = m->fo[FO_cg_quat];
+  a.geom = b->d_ray_geom; a.mesh_vert = b->d_mesh;
+  a.distmax = distmax; a.tol = o.tol; a.max_iters = o.max_iters;
+  a.dist = dist_dev; a.pair = pair_dev; a.fromto = fromto_dev; a.status = status_dev;
+  int e = rsim_launch_clear_fk(&a, b->stream);
+  if (!e) e = rsim_launch_clear_dist(&a, b->stream);
+  if (e) return fail("%s: kernel launch failed: %s", who, hipGetErrorString((hipError_t)e));
   return 0;
 }
 

@@ -215,6 +215,38 @@ class VecEnv:
             raise ValueError(f"solve_ik: the controller description has no arm {arm}")
         return self.env.batch.solve_ik(site, dofs, pos, quat=quat, q_init=q_init, **opts)
 
+    def _arm_dofs(self, who, arm):
+        from .backend import ctrl_desc
+
+        d = ctrl_desc(self.env.cfg)
+        first = [int(d.dof_idx[i]) for i in range(d.ndof) if d.part_of[i] == 0]
+        if arm == 0:
+            return first
+        if arm in (1, "both") and d.narm == 2:
+            second = [int(d.dof_idx[8 + i]) for i in range(d.ndof2)]
+            return second if arm == 1 else first + second
+        raise ValueError(f"{who}: the controller description has no arm {arm!r}")
+
+    def config_fk(self, q, arm=0):
+        """Body poses at candidate arm joint vectors, away from the state: q [n_envs, K, n] (2-D for K = 1) device tensor of the arm's joint positions ->
+        (xpos [n_envs, K, nbody, 3], xquat [n_envs, K, nbody, 4]) of all bodies (HipBatch.config_fk).  The dofs are the arm's `dof_idx` of the env's
+        controller description; arm=1: the second arm of a two-arm description, arm="both": the two concatenated."""
+        return self.env.batch.config_fk(self._arm_dofs("config_fk", arm), q)
+
+    def config_clearance(self, q, arm=0, pairs=None, distmax=1.0, **opts):
+        """Is this arm configuration free, and by how much?  q [n_envs, K, n] (2-D for K = 1) candidate joint positions of the arm -> (dist, pair, fromto,
+        status) per candidate: the smallest distance over `pairs`, the index into the list of the pair that attains it, its nearest points and its status
+        (HipBatch.config_clearance: the status codes, the convex-hull and overlap rules).  pairs: a list of (geom, geom), names or model geom ids; None: the
+        model's collision pairs the arm's joints can change (HipBatch.config_pairs).  Every joint that is not the arm's -- fingers, objects, the other arm --
+        is held where it is, and A GRASPED OBJECT DOES NOT MOVE WITH THE CANDIDATE.  The simulation state is not touched.  arm: as config_fk.  With solve_ik:
+
+            q, err, it, ok = env.solve_ik(pos, quat)
+            d, pair, ft, st = env.config_clearance(q)
+            free = ok & (d > margin)
+        """
+        ids = None if pairs is None else self._geom_ids(pairs)
+        return self.env.batch.config_clearance(self._arm_dofs("config_clearance", arm), q, pairs=ids, distmax=distmax, **opts)
+
     def enable_applied_forces(self, on: bool = True):
         """Honour `qfrc_applied` and `xfrc_applied` in `step` (off by default: the control step then reads neither).  An env that reports `done`
         has both rows zeroed for its next episode, in the same step, so a force written after seeing `done` acts on the new episode."""
