@@ -452,6 +452,13 @@ extern "C" int rsim_model_create(const void* blob, size_t len, rsim_model** out)
       if (gt[c] == 7) {
         if (did < 0) { delete m; return fail("mesh geom %d without mesh data", g); }
         ma[c] = m->I("mesh_vertadr")[did]; mn[c] = m->I("mesh_vertnum")[did];
+        // geom_rcenter is MPR's interior point: a centre outside the hull gives phantom contacts and reversed normals (the compilers keep it inside)
+        const double* mvert = m->D("mesh_vert"); const double* rc = m->D("geom_rcenter");
+        double in = 0;
+        if (mvert && rc && mn[c] >= 4 && (size_t)(ma[c] + mn[c]) * 3 <= m->count("mesh_vert") && rsim_hull_inside_by(mvert + 3 * (size_t)ma[c], mn[c], rc + 3 * g, &in) == 0 && in < 0) {
+          delete m;
+          return fail("rsim_model_create: geom_rcenter of mesh geom %d lies outside its hull (by %g m): the narrow phase needs an interior point", g, -in);
+        }
       }
       if (gt[c] == 1) { delete m; return fail("hfield geoms unsupported"); }
     }

@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "../../include/rsim.h"
+#include "rsim_hull.h"
 
 namespace {
 
@@ -393,6 +394,7 @@ Mesh3 load_mesh(const std::string& path) {
 // case in CAD meshes, never do -- what qhull's merged facets amount to).
 struct Hull { std::vector<int> vert; std::vector<std::array<int, 3>> tri; };
 Hull quickhull(const std::vector<V3>& P);
+double hull_inside_by(const std::vector<V3>& P, V3 c);
 // The hull's vertices are the EXTREME points only: a point that quickhull picked up on the way and that ends up inside a flat facet or on a straight edge of the
 // final hull (its incident triangles lie in fewer than three distinct planes) is dropped and the hull of the rest is taken again -- what qhull's facet merging
 // does to such points, and fewer vertices for the kernel's support scans.
@@ -1128,8 +1130,16 @@ Flat compile(const char* xml, size_t len, const std::string& asset_dir) {
         V3 lo = hv[0], hi = hv[0];
         for (auto& p : hv) { lo = {std::min(lo.x, p.x), std::min(lo.y, p.y), std::min(lo.z, p.z)}; hi = {std::max(hi.x, p.x), std::max(hi.y, p.y), std::max(hi.z, p.z)}; }
         V3 c = (lo + hi) * 0.5;
-        rcenter[3 * gi] = c.x; rcenter[3 * gi + 1] = c.y; rcenter[3 * gi + 2] = c.z;
         double r = 0; for (auto& p : hv) r = std::max(r, norm(p - c));
+        // the narrow phase takes this centre as MPR's interior point: where the box centre is not inside the hull by RSIM_RCENTER_INSIDE of the radius (a
+        // tetrahedron's is outside), the mean of the hull vertices -- always interior -- and the radius about it
+        if (hull_inside_by(hv, c) < RSIM_RCENTER_INSIDE * r) {
+          c = {0, 0, 0};
+          for (auto& p : hv) c = c + p;
+          c = c * (1.0 / (double)hv.size());
+          r = 0; for (auto& p : hv) r = std::max(r, norm(p - c));
+        }
+        rcenter[3 * gi] = c.x; rcenter[3 * gi + 1] = c.y; rcenter[3 * gi + 2] = c.z;
         rbound[gi] = r;
       }
     }
@@ -1470,6 +1480,18 @@ Flat compile(const char* xml, size_t len, const std::string& asset_dir) {
   return m;
 }
 
+// how far (metres) point c lies inside the convex hull of P: the least distance to a face plane, negative outside
+double hull_inside_by(const std::vector<V3>& P, V3 c) {
+  const Hull h = quickhull(P);
+  double in = 1e300;
+  for (auto& t : h.tri) {
+    const V3 nn = cross(P[t[1]] - P[t[0]], P[t[2]] - P[t[0]]);
+    const double l = norm(nn);
+    if (l > 0) in = std::min(in, dot(nn, P[t[0]] - c) / l);
+  }
+  return in;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------------------------ C-ABI (declared in include/rsim.h)
@@ -1500,7 +1522,6 @@ extern "C" int rsim_model_compile(const char* xml, size_t len, const char* asset
 // ------------------------------------------------------------------------------------------------------------------ internal (rsim_hull.h)
 // Face planes of a hull for the ray kernel (rsim_ray.hip).  Triangles of one flat facet come out of quickhull with normals that differ by rounding: a
 // triangle whose three corners lie within 1e-9 of the hull's extent of an earlier facet's plane, and whose normal points the same way, joins that facet.
-#include "rsim_hull.h"
 extern "C" int rsim_hull_planes(const double* vert, int nvert, double* planes, int cap) {
   if (!vert || nvert < 4 || (cap > 0 && !planes)) { fail_msg("rsim_hull_planes: NULL argument or fewer than 4 points"); return -1; }
   try {
@@ -1532,4 +1553,13 @@ extern "C" int rsim_hull_planes(const double* vert, int nvert, double* planes, i
     for (size_t r = 0; r < out.size() && (int)r < cap; r++) for (int k = 0; k < 4; k++) planes[4 * r + k] = out[r][k];
     return (int)out.size();
   } catch (const std::exception& e) { fail_msg(std::string("rsim_hull_planes: ") + e.what()); return -1; }
+}
+extern "C" int rsim_hull_inside_by(const double* vert, int nvert, const double* point, double* inside_by) {
+  if (!vert || nvert < 4 || !point || !inside_by) { fail_msg("rsim_hull_inside_by: NULL argument or fewer than 4 points"); return -1; }
+  try {
+    std::vector<V3> P((size_t)nvert);
+    for (int i = 0; i < nvert; i++) P[i] = {vert[3 * i], vert[3 * i + 1], vert[3 * i + 2]};
+    *inside_by = hull_inside_by(P, {point[0], point[1], point[2]});
+    return 0;
+  } catch (const std::exception& e) { fail_msg(std::string("rsim_hull_inside_by: ") + e.what()); return -1; }
 }

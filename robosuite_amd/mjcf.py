@@ -242,6 +242,17 @@ def convex_hull(verts):
     return hv, faces
 
 
+RCENTER_INSIDE = 0.02        # geom_rcenter of a mesh geom lies inside its hull by at least this share of geom_rbound
+
+
+def hull_inside_by(hv, p):
+    """how far (metres) point p lies inside the convex hull of `hv`: the least distance to a face plane, negative outside"""
+    from scipy.spatial import ConvexHull
+
+    eq = ConvexHull(hv).equations      # n . x + c <= 0 inside
+    return float(-(eq[:, :3] @ np.asarray(p, dtype=np.float64) + eq[:, 3]).max())
+
+
 def mesh_volume_props(verts, faces):
     """Volume, centre of mass and inertia about the COM (unit density) of a closed triangle mesh."""
     vol = 0.0
@@ -934,8 +945,14 @@ def compile_mjcf(xml: str, asset_dir: str | None = None, max_hull_vert: int = 0)
         elif t == GEOM_MESH and g["dataid"] >= 0:
             hv = mesh_vert[g["dataid"]]
             c = 0.5 * (hv.min(axis=0) + hv.max(axis=0))
+            r = np.linalg.norm(hv - c, axis=1).max()
+            # the narrow phase takes this centre as MPR's interior point: where the box centre is not inside the hull by RCENTER_INSIDE of the radius
+            # (a tetrahedron's is outside), the mean of the hull vertices -- always interior -- and the radius about it
+            if hull_inside_by(hv, c) < RCENTER_INSIDE * r:
+                c = hv.mean(axis=0)
+                r = np.linalg.norm(hv - c, axis=1).max()
             rcenter[gi] = c
-            rbound[gi] = np.linalg.norm(hv - c, axis=1).max()
+            rbound[gi] = r
         else:
             rbound[gi] = 0.0  # plane: infinite, handled by type
     m.set("geom_rbound", rbound, F64), m.set("geom_rcenter", rcenter, F64)

@@ -189,6 +189,27 @@ def test_cpp_compiler_reads_stl_obj_msh_and_builds_the_same_hulls(tmp_path):
     compare(rel, str(tmp_path / "root"))
 
 
+def test_cpp_compiler_moves_a_mesh_centre_that_is_outside_its_hull_as_the_python_checker_does(tmp_path):
+    """geom_rcenter is MPR's interior point.  The bounding-box centre of a tetrahedron with three faces in the coordinate planes lies outside it: both compilers
+    take the mean of the hull vertices there, and geom_rbound about it; the polyhedron beside it keeps its box centre."""
+    from tests import contact_scenes as CS
+
+    CS.write_meshes(tmp_path)
+    ref, new, rep = compare(CS.XML, str(tmp_path))
+    print(rep)
+    for m in (ref, new):
+        rc, rb = np.asarray(m.geom_rcenter).reshape(-1, 3), np.asarray(m.geom_rbound).ravel()
+        for name, moved in (("tet", True), ("poly", False)):
+            g = m.names["geom"].index(name)
+            did = int(np.asarray(m.geom_dataid).ravel()[g])
+            V = np.asarray(m.mesh_vert).reshape(-1, 3)[m.mesh_vertadr[did]: m.mesh_vertadr[did] + m.mesh_vertnum[did]]
+            box = 0.5 * (V.min(axis=0) + V.max(axis=0))
+            want = V.mean(axis=0) if moved else box
+            assert (mjcf.hull_inside_by(V, box) < mjcf.RCENTER_INSIDE * np.linalg.norm(V - box, axis=1).max()) == moved
+            assert np.abs(rc[g] - want).max() <= 1e-15 and abs(rb[g] - np.linalg.norm(V - want, axis=1).max()) <= 1e-15, (name, rc[g], want)
+            assert mjcf.hull_inside_by(V, rc[g]) >= mjcf.RCENTER_INSIDE * rb[g]
+
+
 BAD = {
     "not xml": "<mujoco><worldbody></mujoco>",
     "root": "<notmujoco/>",
