@@ -599,7 +599,8 @@ int rsim_geom_distance(rsim_batch* b, int npair, const int32_t* pairs /* HOST [n
  * Refused by name (rsim_last_error): ndof outside 1 .. RSIM_JNT_MAX, a dof id out of range or listed twice, a dof of a free or ball joint, a mocap body among the
  * moved bodies, k < 1, the pair refusals of rsim_geom_distance, an empty default list.
  * NOT HANDLED: A GRASPED OBJECT DOES NOT MOVE WITH THE CANDIDATE -- it is a free body at its current pose.  Also not carried: candidates for free or ball joints,
- * swept checks along a path, a clearance term inside IK or the fused step, heightfields.  robosuite_amd/clearance.py is the fp64 host mirror. */
+ * a clearance term inside IK or the fused step, heightfields.  (Swept checks along a path: rsim_config_sweep below.)  robosuite_amd/clearance.py is the fp64
+ * host mirror. */
 typedef struct rsim_clear_opts { float tol; int32_t max_iters; int32_t chunks; } rsim_clear_opts;   /* NULL: rsim_dist defaults, chunks 0 = automatic */
 /* poses of ALL bodies at the candidates (unmoved bodies: the env's current pose) */
 int rsim_config_fk(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev /* [B][k][ndof] */,
@@ -610,6 +611,54 @@ int rsim_config_clearance(rsim_batch* b, int ndof, const int32_t* dof_ids, int k
                           int npair, const int32_t* pairs /* HOST [npair][2], or NULL with npair 0: the default list */,
                           float distmax, const rsim_clear_opts* opts,
                           float* dist_dev /* [B][k] */, int32_t* pair_dev /* [B][k] */, float* fromto_dev /* [B][k][6] or NULL */, int32_t* status_dev /* or NULL */);
+
+/* Swept clearance for the whole batch, on the device (csrc/rsim_sweep.hip): "is the motion from q0 to q1 free?" for k joint-space segments per env, answered by
+ * conservative advancement -- a certificate, not a set of samples: a thin obstacle between two samples is not missed, and a motion far from everything costs a
+ * sample or two.
+ *   segment     q(t) = q0 + t (q1 - q0), t in [0, 1], for the ndof controlled dofs: q0[env][k][0..ndof), q1 likewise; dof ids, rules and refusals as for
+ *               rsim_config_clearance.  EVERY OTHER JOINT IS HELD AT THE ENV'S CURRENT qpos; no range clamp.
+ *   clearance   c(t) is exactly what rsim_config_clearance returns for the candidate q(t) over the same pair list (the default list, explicit lists and the
+ *               overlap rules carry over) with the same distmax, tol and max_iters, the pair list in one chunk.
+ *   bound L     per segment, >= 0: the distance of every listed pair changes by at most L |dt|.  From the env's own float table, in the walk of the body table,
+ *               without trigonometry: a moved body carries Omega = the sum of |q1 - q0| over the controlled hinges on its path and V, a bound on the speed of
+ *               its origin: V(child) <= V(parent) + Omega(parent) |body_pos|; a slide adds |axis| (|dx| + Omega max(|x(0)|, |x(1)|)) to V (a held slide has
+ *               dx = 0, but its current displacement still lengthens the offset); a hinge adds |dq| to Omega and Omega |jnt_pos| to V on either side of its
+ *               anchor (a held hinge or ball joint: dq = 0).  A geom moves at most V(b) + Omega(b) r, r = |geom_pos| + a radius about the geom's origin that
+ *               contains it (the larger of what its type and geom_size give and |geom_rcenter| + geom_rbound); a geom of a body that is not moved, planes
+ *               included, has speed 0.  L = the maximum over the list of the sum of the pair's two bounds, times 1 + 2^-16 for fp32 rounding.
+ *               rsim_config_motion_bound returns it (the same device code).  L == 0 (q0 == q1, say): one sample decides.
+ *   loop        t = 0; sample c(t); c <= margin + slack: HIT, stop; t == 1: FREE, stop; else t <- min(1, t + (min(c, distmax) - margin) / L) -- a far sample
+ *               advances by (distmax - margin) / L; after max_steps samples without a decision: UNDECIDED.
+ *   options     margin >= 0 (0), slack > 0 (1e-3 m), max_steps 1 .. RSIM_SWEEP_MAX_STEPS (256): API defaults, not tolerances.  slack is what makes the loop
+ *               end: a motion that grazes the scene closer than margin + slack is reported HIT.
+ *   result      per (env, k): status = RSIM_SWEEP_FREE (0), RSIM_SWEEP_HIT (1) or RSIM_SWEEP_UNDECIDED (2), RSIM_DIST_CAP (bit 8) or-ed in if the distance
+ *               iteration of any sample was capped.  t = 1 for FREE, else the parameter of the last sample: THE MOTION IS CERTIFIED TO HAVE CLEARANCE > margin
+ *               ON [0, t).  dist, pair, fromto, t_min: those of the sample with the smallest distance, the earliest on ties (for a HIT the last sample); all
+ *               samples far: (distmax, -1, zeros, 0).  steps = the number of samples taken.
+ * One kernel, one launch: lane = segment env * k + j, 64 per wavefront, the bound pass and then the loop; a wavefront runs as long as its slowest lane.
+ * Asynchronous on the batch's stream, DEVICE pointers in and out, a PURE QUERY; body table, pair table, scratch and the refresh of stale poses are those of
+ * rsim_config_clearance: a batch that never sweeps allocates and launches nothing.
+ * Refused by name: what rsim_config_clearance refuses; margin < 0, slack <= 0, max_steps out of range, distmax <= margin + slack; a PLANE ON A MOVED BODY (an
+ * unbounded solid has no motion bound).
+ * NOTE on pairs that stay close: ONE bound L serves the whole list, so a listed pair that sits within margin + slack whatever the dofs do makes every segment a
+ * HIT at its first sample, and one that sits just above it holds every step to (its distance - margin) / L.  The Panda's link0 / link1 collision geoms stand
+ * 1.0 mm apart at every joint angle: hand in a list without such pairs (parent against child, as a rule).  Per-pair bounds are not carried.
+ * NOT HANDLED: A GRASPED OBJECT DOES NOT MOVE WITH THE MOTION -- it is a free body at its current pose.  Also not carried: free and ball joints as controlled
+ * dofs, interpolation other than linear in joint space, per-pair bounds, a sweep term inside IK or the fused step.  robosuite_amd/sweep.py is the fp64 host
+ * mirror. */
+#define RSIM_SWEEP_FREE 0
+#define RSIM_SWEEP_HIT 1
+#define RSIM_SWEEP_UNDECIDED 2
+#define RSIM_SWEEP_MAX_STEPS 4096
+typedef struct rsim_sweep_opts { float tol; int32_t max_iters; float margin; float slack; int32_t max_steps; } rsim_sweep_opts;
+/* defaults (opts == NULL): tol 1e-6, max_iters 64 (rsim_dist_opts), margin 0, slack 1e-3 m, max_steps 256 */
+int rsim_config_sweep(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q0_dev /* [B][k][ndof] */, const float* q1_dev /* [B][k][ndof] */,
+                      int npair, const int32_t* pairs /* HOST [npair][2], or NULL with npair 0: the default list */,
+                      float distmax, const rsim_sweep_opts* opts /* NULL: defaults */,
+                      int32_t* status_dev /* [B][k] */, float* t_dev /* [B][k] */, float* dist_dev /* [B][k] */, float* tmin_dev /* [B][k] */,
+                      int32_t* pair_dev /* [B][k] */, float* fromto_dev /* [B][k][6] or NULL */, int32_t* steps_dev /* [B][k] or NULL */);
+int rsim_config_motion_bound(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q0_dev, const float* q1_dev,
+                             int npair, const int32_t* pairs /* as above */, float* bound_dev /* [B][k] */);
 
 #ifdef __cplusplus
 }

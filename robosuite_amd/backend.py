@@ -279,6 +279,10 @@ def lib():
             L.rsim_config_fk.argtypes = [vp, C.c_int, C.POINTER(C.c_int32), C.c_int, vp, vp, vp]
             L.rsim_config_pairs.argtypes = [vp, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32)]
             L.rsim_config_clearance.argtypes = [vp, C.c_int, C.POINTER(C.c_int32), C.c_int, vp, C.c_int, C.POINTER(C.c_int32), C.c_float, C.POINTER(ClearOpts), vp, vp, vp, vp]
+        if hasattr(L, "rsim_config_sweep"):
+            L.rsim_config_sweep.argtypes = [vp, C.c_int, C.POINTER(C.c_int32), C.c_int, vp, vp, C.c_int, C.POINTER(C.c_int32), C.c_float, C.POINTER(SweepOpts), vp, vp, vp, vp,
+                                            vp, vp, vp]
+            L.rsim_config_motion_bound.argtypes = [vp, C.c_int, C.POINTER(C.c_int32), C.c_int, vp, vp, C.c_int, C.POINTER(C.c_int32), vp]
         L.rsim_comm_unique_id.argtypes = [vp, C.c_size_t]
         L.rsim_comm_create.argtypes = [vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
         L.rsim_allreduce_stats.argtypes = [vp, vp, C.c_int, C.c_int]
@@ -482,6 +486,10 @@ class DistOpts(C.Structure):     # include/rsim.h rsim_dist_opts
 
 class ClearOpts(C.Structure):    # include/rsim.h rsim_clear_opts
     _fields_ = [("tol", C.c_float), ("max_iters", C.c_int32), ("chunks", C.c_int32)]
+
+
+class SweepOpts(C.Structure):    # include/rsim.h rsim_sweep_opts
+    _fields_ = [("tol", C.c_float), ("max_iters", C.c_int32), ("margin", C.c_float), ("slack", C.c_float), ("max_steps", C.c_int32)]
 
 
 class _DevArray:
@@ -989,6 +997,67 @@ class HipBatch:
         if flat2:
             return dist[:, 0], pid[:, 0], (ft[:, 0] if fromto else None), st[:, 0]
         return dist, pid, ft, st
+
+    # ---- swept clearance (include/rsim.h rsim_config_sweep / rsim_config_motion_bound, csrc/rsim_sweep.hip) ------------------------------------------
+    def _sweep_q(self, who, dofs, q0, q1, pairs):
+        """the argument checks of _config_q for both ends of the segments, and the pair list: -> (dof ids, q0, q1 [B, K, n], K, 2-D?, npair, pairs pointer, keep)"""
+        import torch
+
+        dofs, a, K, flat2 = self._config_q(who, dofs, q0)
+        if not (isinstance(q1, torch.Tensor) and q1.is_cuda):
+            raise RsimError(f"{who}: q1 must be a CUDA tensor")
+        if q1.device != q0.device or tuple(q1.shape) != tuple(q0.shape):
+            raise RsimError(f"{who}: q1 must have the shape and device of q0 ({tuple(q0.shape)} on {q0.device}), got {tuple(q1.shape)} on {q1.device}")
+        b = q1.contiguous().float().reshape(self.B, K, len(dofs))
+        if pairs is None:
+            return dofs, a, b, K, flat2, 0, None, None
+        p = np.ascontiguousarray(np.asarray(pairs), dtype=np.int32)
+        if p.ndim != 2 or p.shape[1] != 2 or p.shape[0] < 1:
+            raise RsimError(f"{who}: npair < 1 or pairs not of shape [P, 2] (got shape {tuple(p.shape)})")
+        return dofs, a, b, K, flat2, int(p.shape[0]), p.ctypes.data_as(C.POINTER(C.c_int32)), p
+
+    def config_motion_bound(self, dofs, q0, q1, pairs=None):
+        """The motion bound L of config_sweep for K segments per env (q0, q1: as config_sweep): float32 [B, K] ([B] for 2-D ends) -- the distance of every
+        listed pair changes by at most L |dt| along q(t) = q0 + t (q1 - q0).  The same device code the sweep runs first."""
+        import torch
+
+        dofs, a, b, K, flat2, n, parg, _keep = self._sweep_q("config_motion_bound", dofs, q0, q1, pairs)
+        out = torch.empty((self.B, K), dtype=torch.float32, device=a.device)
+        self._ray_fence_in()
+        _chk(self._L.rsim_config_motion_bound(self.ptr, len(dofs), (C.c_int32 * len(dofs))(*dofs), K, C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), n, parg,
+                                              C.c_void_p(out.data_ptr())))
+        self._ray_fence_out()
+        return out[:, 0] if flat2 else out
+
+    def config_sweep(self, dofs, q0, q1, pairs=None, distmax=1.0, margin=0.0, slack=1e-3, max_steps=256, fromto=True, tol=None, max_iters=None):
+        """Is the motion from q0 to q1 free?  For K joint-space segments per env, q(t) = q0 + t (q1 - q0), t in [0, 1] (q0, q1: CUDA float32 [B, K, n] positions
+        of the controlled `dofs`, or [B, n] for K = 1; dofs, pairs, distmax, tol, max_iters: as config_clearance), by conservative advancement: a certificate,
+        not a set of samples.  -> (status int32 [B, K]: 0 FREE, 1 HIT, 2 UNDECIDED, bit 8 set if a sample's distance iteration was capped; t float32: 1 for
+        FREE, else the parameter of the last sample -- the motion has clearance > margin on [0, t); dist, t_min float32, pair int32, fromto float32 [B, K, 6] or
+        None: those of the sample with the smallest distance, exactly config_clearance at q(t_min); steps int32: samples taken).  HIT: a sample came within
+        margin + slack; UNDECIDED: max_steps samples did not decide.  A grasped object does NOT move with the motion.  A pure query on the batch's stream;
+        robosuite_amd/sweep.py is the fp64 host mirror."""
+        import torch
+
+        from . import distance as _dist
+
+        try:
+            o = _dist.options(**{k: v for k, v in (("tol", tol), ("max_iters", max_iters)) if v is not None})
+        except (TypeError, ValueError) as e:
+            raise RsimError(str(e).replace("geom_distance", "config_sweep")) from None
+        dofs, a, b, K, flat2, n, parg, _keep = self._sweep_q("config_sweep", dofs, q0, q1, pairs)
+        dev = a.device
+        new = lambda dt, *tail: torch.empty((self.B, K) + tail, dtype=dt, device=dev)      # noqa: E731
+        st, t, dist, tmin, pid, steps = new(torch.int32), new(torch.float32), new(torch.float32), new(torch.float32), new(torch.int32), new(torch.int32)
+        ft = new(torch.float32, 6) if fromto else None
+        so = SweepOpts(o["tol"], o["max_iters"], float(margin), float(slack), int(max_steps))
+        self._ray_fence_in()
+        _chk(self._L.rsim_config_sweep(self.ptr, len(dofs), (C.c_int32 * len(dofs))(*dofs), K, C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), n, parg, float(distmax),
+                                       C.byref(so), C.c_void_p(st.data_ptr()), C.c_void_p(t.data_ptr()), C.c_void_p(dist.data_ptr()), C.c_void_p(tmin.data_ptr()),
+                                       C.c_void_p(pid.data_ptr()), C.c_void_p(ft.data_ptr()) if fromto else None, C.c_void_p(steps.data_ptr())))
+        self._ray_fence_out()
+        out = (st, t, dist, tmin, pid, ft, steps)
+        return tuple(x[:, 0] if flat2 and x is not None else x for x in out)
 
     def set_schedule(self, longest_first=True):
         """Dispatch order of control_step: slowest envs of the previous step first (default) or identity."""

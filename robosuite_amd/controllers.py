@@ -97,6 +97,15 @@ class BatchState:
         status).  Unmoved bodies are at the poses as they stand: valid between step1 and step2, like the other views."""
         return self.batch.config_clearance(dofs, q, pairs=pairs, distmax=distmax, **opts)
 
+    def config_sweep(self, dofs, q0, q1, pairs=None, distmax=1.0, **opts):
+        """Is the motion from q0 to q1 of `dofs` free?  A certified check away from the state (HipBatch.config_sweep): -> (status, t, dist, t_min, pair, fromto,
+        steps).  Valid between step1 and step2."""
+        return self.batch.config_sweep(dofs, q0, q1, pairs=pairs, distmax=distmax, **opts)
+
+    def config_motion_bound(self, dofs, q0, q1, pairs=None):
+        """The motion bound L config_sweep uses for these segments (HipBatch.config_motion_bound)."""
+        return self.batch.config_motion_bound(dofs, q0, q1, pairs=pairs)
+
     def body_dofs(self, body: int):
         """bool [nv]: the dofs that move `body` (its own joints and those of its ancestors)."""
         import torch

@@ -89,6 +89,7 @@ extern "C" int rsim_launch_randomize(const DModel* m, const DBatch* b, const DDr
 #include "rsim_ik.h"
 #include "rsim_clear.h"
 #include "rsim_clear_core.h"
+#include "rsim_sweep.h"
 #include "rsim_hull.h"
 
 struct rsim_model;
@@ -148,7 +149,7 @@ struct rsim_model {
 enum { TIER_NONE, TIER_FUSED, TIER_LIST };   // rsim_batch.tier
 
 // configuration clearance (rsim_clear.hip): what the batch keeps per dof list -- the body table and the slot of every body on the device, and the default pair list
-struct ClearTab { int *d_tab, *d_slot; int nel, nslot; std::vector<int> def_pairs; };
+struct ClearTab { int *d_tab, *d_slot; int nel, nslot; std::vector<int> def_pairs, slot; };   // (slot: the host copy of d_slot, for the swept query's refusals)
 
 struct rsim_batch {
   rsim_model* m;
@@ -2385,7 +2386,7 @@ static int clear_table(rsim_batch* b, const char* who, int ndof, const int32_t* 
     ClearPlan plan;
     if (clear_plan(b->m, who, ndof, dofs, &plan)) return 1;
     ClearTab t;
-    t.d_tab = t.d_slot = nullptr; t.nel = plan.nel; t.nslot = plan.nslot;
+    t.d_tab = t.d_slot = nullptr; t.nel = plan.nel; t.nslot = plan.nslot; t.slot = plan.slot;
     if (clear_default_pairs(b->m, who, plan, &t.def_pairs)) t.def_pairs.clear();   // (an error only for a call that asks for the default list)
     if (dalloc(&t.d_tab, plan.tab.size()) || dalloc(&t.d_slot, plan.slot.size())) return 1;
     HIPCHK(hipMemcpy(t.d_tab, plan.tab.data(), plan.tab.size() * sizeof(int), hipMemcpyHostToDevice));
@@ -2473,6 +2474,74 @@ extern "C" int rsim_config_clearance(rsim_batch* b, int ndof, const int32_t* dof
   a.dist = dist_dev; a.pair = pair_dev; a.fromto = fromto_dev; a.status = status_dev;
   int e = rsim_launch_clear_fk(&a, b->stream);
   if (!e) e = rsim_launch_clear_dist(&a, b->stream);
+  if (e) return fail("%s: kernel launch failed: %s", who, hipGetErrorString((hipError_t)e));
+  return 0;
+}
+
+// ---- swept clearance (rsim_sweep.hip, include/rsim.h rsim_config_sweep / rsim_config_motion_bound) -----------------------------------------------------------
+// A segment is a candidate with two ends: the body table, the pair table, the scratch and the stale-pose refresh are the clearance query's (clear_args above).
+static int sweep_args(rsim_batch* b, const char* who, int ndof, const int32_t* dof_ids, int k, const float* q0_dev, const float* q1_dev, int npair, const int32_t* pairs,
+                      DSweep* a) {
+  if (!b) return fail("%s: batch is NULL", who);
+  if (!q0_dev || !q1_dev) return fail("%s: %s is NULL", who, !q0_dev ? "q0_dev" : "q1_dev");
+  if (npair < 0 || (npair > 0 && !pairs) || (npair == 0 && pairs)) return fail("%s: npair %d with pairs %s (a list of npair >= 1 pairs, or NULL and 0 for the default list)", who, npair, pairs ? "given" : "NULL");
+  memset(a, 0, sizeof(*a));
+  const ClearTab* tab;
+  if (clear_args(b, who, ndof, dof_ids, k, q0_dev, &a->c, &tab)) return 1;
+  if (!pairs) {
+    if (tab->def_pairs.empty()) return fail("%s: the default pair list is empty: no collision pair of the model depends on the controlled dofs", who);
+    npair = (int)(tab->def_pairs.size() / 2); pairs = tab->def_pairs.data();
+  }
+  if (dist_pairs(b, npair, pairs, &a->c.pairs)) return 1;   // (refusals come before anything is launched)
+  const rsim_model* m = b->m;
+  const int *gt = m->I("geom_type"), *gb = m->I("geom_bodyid");
+  for (int p = 0; p < npair; p++)
+    for (int j = 0; j < 2; j++) {
+      const int g = pairs[2 * p + j];
+      if (gt[g] == 0 && tab->slot[gb[g]] >= 0)
+        return fail("%s: pair %d: plane geom %d sits on body %d, which the controlled dofs move: an unbounded solid has no motion bound", who, p, g, gb[g]);
+    }
+  if (refresh_derived(b, RSIM_XPOS) || ray_scene(b)) return 1;
+  if (clear_grow(b, &b->d_clear_scr, &b->clear_scr_n, (size_t)a->c.nslot * 7 * a->c.NC)) return 1;
+  a->c.scr = b->d_clear_scr;
+  a->c.npair = npair; a->c.chunks = 1;
+  a->c.fo_size = m->fo[FO_cg_size]; a->c.fo_pos = m->fo[FO_cg_pos]; a->c.fo_quat = m->fo[FO_cg_quat];
+  a->fo_rcenter = m->fo[FO_cg_rcenter]; a->fo_rbound = m->fo[FO_cg_rbound];
+  a->c.geom = b->d_ray_geom; a->c.mesh_vert = b->d_mesh;
+  a->q1 = q1_dev;
+  return 0;
+}
+extern "C" int rsim_config_motion_bound(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q0_dev, const float* q1_dev, int npair, const int32_t* pairs,
+                                        float* bound_dev) {
+  const char* who = "rsim_config_motion_bound";
+  if (!bound_dev) return fail("%s: bound_dev is NULL", who);
+  DSweep a;
+  if (sweep_args(b, who, ndof, dof_ids, k, q0_dev, q1_dev, npair, pairs, &a)) return 1;
+  a.bound = bound_dev;
+  const int e = rsim_launch_sweep(&a, b->stream);
+  if (e) return fail("%s: kernel launch failed: %s", who, hipGetErrorString((hipError_t)e));
+  return 0;
+}
+extern "C" int rsim_config_sweep(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q0_dev, const float* q1_dev, int npair, const int32_t* pairs,
+                                 float distmax, const rsim_sweep_opts* opts, int32_t* status_dev, float* t_dev, float* dist_dev, float* tmin_dev, int32_t* pair_dev,
+                                 float* fromto_dev, int32_t* steps_dev) {
+  const char* who = "rsim_config_sweep";
+  if (!status_dev || !t_dev || !dist_dev || !tmin_dev || !pair_dev)
+    return fail("%s: %s is NULL", who, !status_dev ? "status_dev" : !t_dev ? "t_dev" : !dist_dev ? "dist_dev" : !tmin_dev ? "tmin_dev" : "pair_dev");
+  const rsim_sweep_opts def = {1e-6f, 64, 0.f, 1e-3f, 256};
+  const rsim_sweep_opts o = opts ? *opts : def;
+  if (!(o.tol >= 0.f) || o.max_iters < 1 || o.max_iters > RSIM_DIST_MAX_ITERS)
+    return fail("%s: option out of range (tol %g, max_iters %d: 1..%d)", who, (double)o.tol, o.max_iters, RSIM_DIST_MAX_ITERS);
+  if (!(o.margin >= 0.f)) return fail("%s: margin %g is not >= 0", who, (double)o.margin);
+  if (!(o.slack > 0.f)) return fail("%s: slack %g is not > 0", who, (double)o.slack);
+  if (o.max_steps < 1 || o.max_steps > RSIM_SWEEP_MAX_STEPS) return fail("%s: max_steps %d outside 1..%d", who, o.max_steps, RSIM_SWEEP_MAX_STEPS);
+  if (!(distmax > o.margin + o.slack)) return fail("%s: distmax %g is not above margin + slack = %g: no sample could pass", who, (double)distmax, (double)(o.margin + o.slack));
+  DSweep a;
+  if (sweep_args(b, who, ndof, dof_ids, k, q0_dev, q1_dev, npair, pairs, &a)) return 1;
+  a.c.distmax = distmax; a.c.tol = o.tol; a.c.max_iters = o.max_iters;
+  a.margin = o.margin; a.slack = o.slack; a.max_steps = o.max_steps;
+  a.c.status = status_dev; a.t = t_dev; a.c.dist = dist_dev; a.tmin = tmin_dev; a.c.pair = pair_dev; a.c.fromto = fromto_dev; a.steps = steps_dev;
+  const int e = rsim_launch_sweep(&a, b->stream);
   if (e) return fail("%s: kernel launch failed: %s", who, hipGetErrorString((hipError_t)e));
   return 0;
 }

@@ -105,9 +105,16 @@ RSIM_HD Pose fk_joint(const Pose& cur, int kind, const float* ft, int o_jpos, in
   return r;
 }
 
+// the value of controlled column `col`: the candidate's own entry.  (The swept query hands fk_walk another one: a point on a segment, rsim_sweep_core.h.)
+struct CandQ {
+  const float* q;
+  RSIM_HD float operator()(int col) const { return q[col]; }
+};
+
 // Walks the table and stores the pose of every moved body.  `last` is the body before in registers: a chain reads its parent from there, a branch from the store
-// (what this very candidate wrote earlier in the walk).
-RSIM_HD void fk_walk(const int* tab, int nel, const Cand& c, const PoseStore& st) {
+// (what this very candidate wrote earlier in the walk).  qv(col) is the position of controlled column col.
+template <class JointValue>
+RSIM_HD void fk_walk(const int* tab, int nel, const Cand& c, const PoseStore& st, const JointValue& qv) {
   Pose cur, last;
   cur.p = last.p = v3(0, 0, 0);
   cur.q.w = last.q.w = 1.f; cur.q.x = cur.q.y = cur.q.z = last.q.x = last.q.y = last.q.z = 0.f;
@@ -132,10 +139,14 @@ RSIM_HD void fk_walk(const int* tab, int nel, const Cand& c, const PoseStore& st
     } else {
       const int col = RSIM_CLEAR_U(el[CLE_COL]), qadr = RSIM_CLEAR_U(el[CLE_ID]);
       float x = 0.f;
-      if (kind != CL_BALL) x = (col >= 0 ? c.q[col] : c.qpos[qadr]) - c.ft[RSIM_CLEAR_U(el[CLE_O3])];
+      if (kind != CL_BALL) x = (col >= 0 ? qv(col) : c.qpos[qadr]) - c.ft[RSIM_CLEAR_U(el[CLE_O3])];
       cur = fk_joint(cur, kind, c.ft, RSIM_CLEAR_U(el[CLE_O1]), RSIM_CLEAR_U(el[CLE_O2]), x, c.qpos + qadr);
     }
   }
+}
+RSIM_HD void fk_walk(const int* tab, int nel, const Cand& c, const PoseStore& st) {
+  const CandQ qv = {c.q};
+  fk_walk(tab, nel, c, st, qv);
 }
 
 // ---- the pair loop ----------------------------------------------------------------------------------------------------------------------------------------

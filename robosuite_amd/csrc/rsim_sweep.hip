@@ -1,0 +1,66 @@
+// rsim_sweep.hip -- "is the motion from q0 to q1 free?" for K joint-space segments per env, for the whole batch, on the device: rsim_config_sweep and
+// rsim_config_motion_bound (include/rsim.h).  Conservative advancement: from the clearance c at q(t) and a bound L on how fast any listed pair can approach per
+// unit t, the motion is free on [t, t + (c - margin) / L]; the work per segment follows how close the motion comes to the scene, and the answer is a
+// certificate, not a sample.  The per-segment code is rsim_sweep_core.h on rsim_clear_core.h (FK walk, pruned pair loop) and rsim_dist_core.h (GJK), shared
+// with the host rehearsal (tests/san/sweep_core_driver.cpp); robosuite_amd/sweep.py is the fp64 host mirror.
+//
+// Like k_clear_* a kernel in a code object of its own that takes everything as its argument; a pure query.
+// Mapping: lane = segment s = env * K + k; 64 consecutive segments are one wavefront; the pose scratch is k_clear_dist's, [slot][7][B K].
+//   k_sweep   grid ceil(B K / 64).  ONE launch: the bound pass (a table walk that leaves Omega and V of each moved body in the scratch, then the maximum over the
+//             pair list), then the loop of samples -- FK at q(t) into the scratch, the whole pair list with the lane's running minimum as distmax, the step.
+//             A wavefront runs as long as its slowest lane: decided lanes are masked, the trip count max_steps is wave-uniform and the loop leaves early once
+//             every lane of the wavefront is decided.  Every inner loop is bounded by a table length, max_iters or a vertex count.
+// No LDS, no barrier, no atomics, no private array.
+#include <hip/hip_runtime.h>
+#include "../../include/rsim.h"
+#include "rsim_sweep.h"
+#include "rsim_sweep_core.h"
+
+using namespace rsim_sweep;
+
+__global__ __launch_bounds__(RSIM_CLEAR_LANES) void k_sweep(DSweep a) {
+  const DClear& d = a.c;
+  const int c = (int)blockIdx.x * RSIM_CLEAR_LANES + (int)threadIdx.x;
+  if (c >= d.NC) return;
+  const int env = c / d.K;
+  Seg s;
+  s.env.ft = d.ft + (size_t)env * d.fstride;
+  s.env.qpos = d.qpos + (size_t)env * d.nq;
+  s.env.xpos = d.xpos + (size_t)env * d.nbody * 3;
+  s.env.xquat = d.xquat + (size_t)env * d.nbody * 4;
+  s.q0 = d.q + (size_t)c * d.n; s.q1 = a.q1 + (size_t)c * d.n;
+  s.env.q = s.q0;
+  const size_t nc = (size_t)d.NC;
+  PoseStore st;
+  st.pos = d.scr + c; st.quat = d.scr + 3 * nc + c;
+  st.pe = st.qe = 7 * nc; st.ps = st.qs = nc; st.by_body = 0;
+  Scene<DRayGeom> sc;
+  sc.geom = d.geom; sc.pairs = d.pairs; sc.rec = RSIM_DIST_REC; sc.slot_of_body = d.slot_of_body; sc.mesh_vert = d.mesh_vert;
+  sc.fo_size = d.fo_size; sc.fo_pos = d.fo_pos; sc.fo_quat = d.fo_quat;
+
+  const float L = motion_bound(d.tab, d.nel, sc, a.fo_rcenter, a.fo_rbound, d.npair, s, st);
+  if (a.bound) { a.bound[c] = L; return; }
+
+  Opts op;
+  op.distmax = d.distmax; op.tol = d.tol; op.max_iters = d.max_iters; op.margin = a.margin; op.slack = a.slack; op.max_steps = a.max_steps;
+  Out o = sweep_begin(op.distmax);
+  float t = 0.f;
+  bool done = false;
+  for (int i = 0; i < a.max_steps; i++) {
+    if (!done) done = sweep_sample(d.tab, d.nel, sc, d.npair, s, st, op, L, t, o);
+    if (__all(done)) break;
+  }
+  a.c.status[c] = o.status; a.t[c] = o.t; a.tmin[c] = o.t_min;
+  d.dist[c] = o.best.dist; d.pair[c] = o.best.pair;
+  if (a.steps) a.steps[c] = o.steps;
+  if (d.fromto) {
+    float* f = d.fromto + 6 * (size_t)c;
+    f[0] = o.best.p1.x; f[1] = o.best.p1.y; f[2] = o.best.p1.z; f[3] = o.best.p2.x; f[4] = o.best.p2.y; f[5] = o.best.p2.z;
+  }
+}
+
+extern "C" int rsim_launch_sweep(const DSweep* a, hipStream_t stream) {
+  if (a->c.NC <= 0 || a->c.nel <= 0 || a->c.npair <= 0) return 0;
+  hipLaunchKernelGGL(k_sweep, dim3((a->c.NC + RSIM_CLEAR_LANES - 1) / RSIM_CLEAR_LANES), dim3(RSIM_CLEAR_LANES), 0, stream, *a);
+  return (int)hipGetLastError();
+}

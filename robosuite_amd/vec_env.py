@@ -247,6 +247,36 @@ class VecEnv:
         ids = None if pairs is None else self._geom_ids(pairs)
         return self.env.batch.config_clearance(self._arm_dofs("config_clearance", arm), q, pairs=ids, distmax=distmax, **opts)
 
+    def config_sweep(self, q0, q1, arm=0, pairs=None, distmax=1.0, **opts):
+        """Is the arm motion from q0 to q1 free?  q0, q1 [n_envs, K, n] (2-D for K = 1) ends of K joint-space segments per env, interpolated linearly ->
+        (status, t, dist, t_min, pair, fromto, steps) per segment (HipBatch.config_sweep: 0 FREE, 1 HIT, 2 UNDECIDED; the motion is certified to keep more
+        than `margin` of clearance on [0, t)).  arm, pairs: as config_clearance; opts: margin, slack, max_steps, fromto, tol, max_iters.  Every joint that is
+        not the arm's is held where it is, and A GRASPED OBJECT DOES NOT MOVE WITH THE MOTION.  The simulation state is not touched.  One motion bound serves the
+        whole list: a listed pair that stays within margin + slack whatever the arm does (the Panda's link0 / link1 geoms, 1.0 mm apart) decides every segment
+        at its first sample -- pass `pairs` without it."""
+        ids = None if pairs is None else self._geom_ids(pairs)
+        return self.env.batch.config_sweep(self._arm_dofs("config_sweep", arm), q0, q1, pairs=ids, distmax=distmax, **opts)
+
+    def path_clearance(self, waypoints, arm=0, pairs=None, distmax=1.0, **opts):
+        """Is this joint-space path free?  waypoints [n_envs, K, W, n]: K paths per env of W >= 2 arm joint vectors, joined by straight joint-space segments
+        -> (free bool [n_envs, K], first_segment int64, t, dist float32, pair int32).  One config_sweep call over the K (W - 1) segments, reduced in torch: a
+        path is free only if EVERY segment is FREE; otherwise first_segment is the first segment that is not (HIT or UNDECIDED) and t, dist, pair are that
+        segment's (the path is certified up to parameter t of it).  A free path reads first_segment -1, t 1 and the smallest dist over its segments with that
+        segment's pair.  arm, pairs, opts: as config_sweep."""
+        import torch
+
+        if not (isinstance(waypoints, torch.Tensor) and waypoints.dim() == 4 and waypoints.shape[2] >= 2):
+            raise ValueError(f"path_clearance: waypoints must be a tensor [n_envs, K, W, n] with W >= 2, got {tuple(getattr(waypoints, 'shape', ()))}")
+        B, K, W, n = waypoints.shape
+        q0, q1 = waypoints[:, :, :-1].reshape(B, K * (W - 1), n), waypoints[:, :, 1:].reshape(B, K * (W - 1), n)
+        st, t, dist, _, pair, _, _ = self.config_sweep(q0, q1, arm=arm, pairs=pairs, distmax=distmax, **dict(opts, fromto=False))
+        st, t, dist, pair = (x.reshape(B, K, W - 1) for x in (st, t, dist, pair))
+        bad = (st & 3) != 0
+        free = ~bad.any(dim=2)
+        seg = torch.where(free, dist.argmin(dim=2), bad.int().argmax(dim=2))      # (argmax of a 0 / 1 tensor: the first 1)
+        pick = lambda x: x.gather(2, seg[..., None])[..., 0]                        # noqa: E731
+        return free, torch.where(free, torch.full_like(seg, -1), seg), pick(t), pick(dist), pick(pair)
+
     def enable_applied_forces(self, on: bool = True):
         """Honour `qfrc_applied` and `xfrc_applied` in `step` (off by default: the control step then reads neither).  An env that reports `done`
         has both rows zeroed for its next episode, in the same step, so a force written after seeing `done` acts on the new episode."""

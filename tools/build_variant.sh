@@ -11,5 +11,5 @@ $HIPCC $CXXFLAGS -I. -DRSIM_CFG=3 $CFG3FLAGS $f3 -x hip -c $SRC -o $D/cfg3.o &
 $HIPCC $CXXFLAGS -I. -DRSIM_CFG=5 $CFG3FLAGS $f3 -x hip -c $SRC -o $D/cfg5.o &
 if [ -n "$fa" ]; then $HIPCC $CXXFLAGS $fa -x hip -c rsim_api.cpp -o $D/api.o & else cp rsim_api.o $D/api.o; fi
 wait
-$HIPCC --offload-arch=$ARCH -shared -fPIC -o ../librsim_hip_$name.so rsim_step.o rsim_step_cfg1.o rsim_step_cfg2.o $D/cfg3.o rsim_step_cfg4.o $D/cfg5.o rsim_episode.o rsim_sensors.o rsim_ray.o rsim_ik.o rsim_dist.o rsim_clear.o $D/api.o rsim_mjcf.o -L$TORCH_LIB -Wl,-rpath,$TORCH_LIB
+$HIPCC --offload-arch=$ARCH -shared -fPIC -o ../librsim_hip_$name.so rsim_step.o rsim_step_cfg1.o rsim_step_cfg2.o $D/cfg3.o rsim_step_cfg4.o $D/cfg5.o rsim_episode.o rsim_sensors.o rsim_ray.o rsim_ik.o rsim_dist.o rsim_clear.o rsim_sweep.o $D/api.o rsim_mjcf.o -L$TORCH_LIB -Wl,-rpath,$TORCH_LIB
 echo built ../librsim_hip_$name.so

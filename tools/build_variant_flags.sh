@@ -21,5 +21,5 @@ for c in 0 1 2 3 4 5; do
   [ -f $D/cfg$c.o ] && [[ " $* " == *" $c "* ]] && o=$D/cfg$c.o
   objs="$objs $o"
 done
-$HIPCC --offload-arch=$ARCH -shared -fPIC -o ../librsim_hip_$name.so $objs rsim_episode.o rsim_sensors.o rsim_ray.o rsim_ik.o rsim_dist.o rsim_clear.o rsim_api.o rsim_mjcf.o -L$TORCH_LIB -Wl,-rpath,$TORCH_LIB
+$HIPCC --offload-arch=$ARCH -shared -fPIC -o ../librsim_hip_$name.so $objs rsim_episode.o rsim_sensors.o rsim_ray.o rsim_ik.o rsim_dist.o rsim_clear.o rsim_sweep.o rsim_api.o rsim_mjcf.o -L$TORCH_LIB -Wl,-rpath,$TORCH_LIB
 echo built ../librsim_hip_$name.so
