@@ -2120,6 +2120,19 @@ extern "C" int rsim_render_depth(rsim_batch* b, const rsim_camera* cam, int heig
   return ray_launch(b, &a, "rsim_render_depth");
 }
 
+// ---- shared by the queries below ------------------------------------------------------------------------------------------------------------------
+// the tail of a query entry: the status of its launch as the entry's return value
+static int launched(const char* who, int e) {
+  if (e) return fail("%s: kernel launch failed: %s", who, hipGetErrorString((hipError_t)e));
+  return 0;
+}
+// entry c of a list of controlled dofs: in range and not listed before (called per entry, so a caller's own checks of entry c - 1 still come first)
+static int dof_check(const char* who, const rsim_model* m, const int32_t* dofs, int c) {
+  if (dofs[c] < 0 || dofs[c] >= m->nv) return fail("%s: controlled dof %d out of range (%d dofs)", who, dofs[c], m->nv);
+  for (int d = 0; d < c; d++) if (dofs[d] == dofs[c]) return fail("%s: dof %d is listed twice", who, dofs[c]);
+  return 0;
+}
+
 // ---- inverse kinematics (rsim_ik.hip, include/rsim.h rsim_ik_site) -------------------------------------------------------------------------------
 // The chain table of one (site, dofs) key (rsim_ik.h): the bodies from the world to the site's body in order, each followed by its joints, then the site.
 // Plain host code on the model's int tables; what the solver does not carry is refused here, by name.
@@ -2134,10 +2147,7 @@ static int ik_chain_build(const rsim_model* m, int site, int ndof, const int32_t
   const int *parent = m->I("body_parentid"), *jadr = m->I("body_jntadr"), *jnum = m->I("body_jntnum"), *jtype = m->I("jnt_type"), *qadr = m->I("jnt_qposadr"),
             *dadr = m->I("jnt_dofadr"), *lim = m->I("jnt_limited"), *sb = m->I("site_bodyid"), *mocap = m->I("body_mocapid");
   if (!parent || !jadr || !jnum || !jtype || !qadr || !dadr || !lim || !sb) return fail("rsim_ik_site: the model lacks a joint / body table");
-  for (int c = 0; c < ndof; c++) {
-    if (dofs[c] < 0 || dofs[c] >= m->nv) return fail("rsim_ik_site: controlled dof %d out of range (%d dofs)", dofs[c], m->nv);
-    for (int d = 0; d < c; d++) if (dofs[d] == dofs[c]) return fail("rsim_ik_site: dof %d is listed twice", dofs[c]);
-  }
+  for (int c = 0; c < ndof; c++) if (dof_check("rsim_ik_site", m, dofs, c)) return 1;
   std::vector<int> path;
   for (int b = sb[site]; b > 0; b = parent[b]) {
     if (b >= m->nbody || (int)path.size() >= m->nbody) return fail("rsim_ik_site: the body tree above site %d is malformed", site);
@@ -2213,9 +2223,7 @@ extern "C" int rsim_ik_site(rsim_batch* b, int site, int ndof, const int32_t* do
   a.damping = o.damping; a.max_dq = o.max_dq; a.pos_tol = o.pos_tol; a.rot_tol = o.rot_tol; a.posture_gain = o.posture_gain;
   a.max_iters = o.max_iters; a.clamp_range = o.clamp_range ? 1 : 0;
   a.q_out = q_out_dev; a.err = err_dev; a.iters = iters_dev;
-  const int e = rsim_launch_ik(&a, b->stream);
-  if (e) return fail("rsim_ik_site: kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-  return 0;
+  return launched("rsim_ik_site", rsim_launch_ik(&a, b->stream));
 }
 
 // ---- geom distance (rsim_dist.hip, include/rsim.h rsim_geom_distance) ----------------------------------------------------------------------------------
@@ -2284,9 +2292,7 @@ extern "C" int rsim_geom_distance(rsim_batch* b, int npair, const int32_t* pairs
   a.geom = b->d_ray_geom; a.mesh_vert = b->d_mesh; a.ft = b->d_ft; a.xpos = b->db.xpos; a.xquat = b->db.xquat;
   a.distmax = distmax; a.tol = o.tol; a.max_iters = o.max_iters;
   a.dist = dist_dev; a.fromto = fromto_dev; a.status = status_dev;
-  const int e = rsim_launch_dist(&a, b->stream);
-  if (e) return fail("rsim_geom_distance: kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-  return 0;
+  return launched("rsim_geom_distance", rsim_launch_dist(&a, b->stream));
 }
 
 // ---- configuration clearance (rsim_clear.hip, include/rsim.h rsim_config_fk / rsim_config_pairs / rsim_config_clearance) -----------------------------------
@@ -2305,8 +2311,7 @@ static int clear_plan(const rsim_model* m, const char* who, int ndof, const int3
   if (!dofs) return fail("%s: dof_ids is NULL", who);
   std::vector<int> col_of_jnt((size_t)m->njnt, -1);
   for (int c = 0; c < ndof; c++) {
-    if (dofs[c] < 0 || dofs[c] >= m->nv) return fail("%s: controlled dof %d out of range (%d dofs)", who, dofs[c], m->nv);
-    for (int d = 0; d < c; d++) if (dofs[d] == dofs[c]) return fail("%s: dof %d is listed twice", who, dofs[c]);
+    if (dof_check(who, m, dofs, c)) return 1;
     int j = -1;
     for (int k = 0; k < m->njnt; k++) {
       const int w = jtype[k] == 0 ? 6 : jtype[k] == 1 ? 3 : 1;
@@ -2396,6 +2401,19 @@ static int clear_table(rsim_batch* b, const char* who, int ndof, const int32_t* 
   *out = &it->second;
   return 0;
 }
+// the pair list of a clearance / sweep call, in two steps because a call's own checks come between them: the argument as given ...
+static int pairs_check(const char* who, int npair, const int32_t* pairs) {
+  if (npair < 0 || (npair > 0 && !pairs) || (npair == 0 && pairs)) return fail("%s: npair %d with pairs %s (a list of npair >= 1 pairs, or NULL and 0 for the default list)", who, npair, pairs ? "given" : "NULL");
+  return 0;
+}
+// ... and, once the dof list has its table, the table's default list in place of NULL, and the pair table of the list (refusals come before anything is launched)
+static int pairs_resolve(rsim_batch* b, const char* who, const ClearTab* tab, int* npair, const int32_t** pairs, const int** d_tab) {
+  if (!*pairs) {
+    if (tab->def_pairs.empty()) return fail("%s: the default pair list is empty: no collision pair of the model depends on the controlled dofs", who);
+    *npair = (int)(tab->def_pairs.size() / 2); *pairs = tab->def_pairs.data();
+  }
+  return dist_pairs(b, *npair, *pairs, d_tab);
+}
 // batch-owned scratch, grown on demand (the stream is drained first: a launch before may still read the old block)
 static int clear_grow(rsim_batch* b, float** p, size_t* have, size_t want) {
   if (*have >= want) return 0;
@@ -2429,9 +2447,7 @@ extern "C" int rsim_config_fk(rsim_batch* b, int ndof, const int32_t* dof_ids, i
   if (clear_args(b, "rsim_config_fk", ndof, dof_ids, k, q_dev, &a, &tab)) return 1;
   if (refresh_derived(b, RSIM_XPOS)) return 1;
   a.xpos_out = xpos_dev; a.xquat_out = xquat_dev;
-  const int e = rsim_launch_clear_fk(&a, b->stream);
-  if (e) return fail("rsim_config_fk: kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-  return 0;
+  return launched("rsim_config_fk", rsim_launch_clear_fk(&a, b->stream));
 }
 extern "C" int rsim_config_clearance(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, int npair, const int32_t* pairs, float distmax,
                                      const rsim_clear_opts* opts, float* dist_dev, int32_t* pair_dev, float* fromto_dev, int32_t* status_dev) {
@@ -2439,7 +2455,7 @@ extern "C" int rsim_config_clearance(rsim_batch* b, int ndof, const int32_t* dof
   if (!b) return fail("%s: batch is NULL", who);
   if (!dist_dev || !pair_dev) return fail("%s: %s is NULL", who, !dist_dev ? "dist_dev" : "pair_dev");
   if (!(distmax >= 0.f)) return fail("%s: distmax %g is not >= 0", who, (double)distmax);
-  if (npair < 0 || (npair > 0 && !pairs) || (npair == 0 && pairs)) return fail("%s: npair %d with pairs %s (a list of npair >= 1 pairs, or NULL and 0 for the default list)", who, npair, pairs ? "given" : "NULL");
+  if (pairs_check(who, npair, pairs)) return 1;
   const rsim_clear_opts def = {1e-6f, 64, 0};
   const rsim_clear_opts o = opts ? *opts : def;
   if (!(o.tol >= 0.f) || o.max_iters < 1 || o.max_iters > RSIM_DIST_MAX_ITERS || o.chunks < 0)
@@ -2447,11 +2463,7 @@ extern "C" int rsim_config_clearance(rsim_batch* b, int ndof, const int32_t* dof
   DClear a;
   const ClearTab* tab;
   if (clear_args(b, who, ndof, dof_ids, k, q_dev, &a, &tab)) return 1;
-  if (!pairs) {
-    if (tab->def_pairs.empty()) return fail("%s: the default pair list is empty: no collision pair of the model depends on the controlled dofs", who);
-    npair = (int)(tab->def_pairs.size() / 2); pairs = tab->def_pairs.data();
-  }
-  if (dist_pairs(b, npair, pairs, &a.pairs)) return 1;   // (refusals come before anything is launched)
+  if (pairs_resolve(b, who, tab, &npair, &pairs, &a.pairs)) return 1;
   if (refresh_derived(b, RSIM_XPOS) || ray_scene(b)) return 1;
   const rsim_model* m = b->m;
   const int waves = (a.NC + RSIM_CLEAR_LANES - 1) / RSIM_CLEAR_LANES;
@@ -2474,8 +2486,7 @@ extern "C" int rsim_config_clearance(rsim_batch* b, int ndof, const int32_t* dof
   a.dist = dist_dev; a.pair = pair_dev; a.fromto = fromto_dev; a.status = status_dev;
   int e = rsim_launch_clear_fk(&a, b->stream);
   if (!e) e = rsim_launch_clear_dist(&a, b->stream);
-  if (e) return fail("%s: kernel launch failed: %s", who, hipGetErrorString((hipError_t)e));
-  return 0;
+  return launched(who, e);
 }
 
 // ---- swept clearance (rsim_sweep.hip, include/rsim.h rsim_config_sweep / rsim_config_motion_bound) -----------------------------------------------------------
@@ -2484,15 +2495,11 @@ static int sweep_args(rsim_batch* b, const char* who, int ndof, const int32_t* d
                       DSweep* a) {
   if (!b) return fail("%s: batch is NULL", who);
   if (!q0_dev || !q1_dev) return fail("%s: %s is NULL", who, !q0_dev ? "q0_dev" : "q1_dev");
-  if (npair < 0 || (npair > 0 && !pairs) || (npair == 0 && pairs)) return fail("%s: npair %d with pairs %s (a list of npair >= 1 pairs, or NULL and 0 for the default list)", who, npair, pairs ? "given" : "NULL");
+  if (pairs_check(who, npair, pairs)) return 1;
   memset(a, 0, sizeof(*a));
   const ClearTab* tab;
   if (clear_args(b, who, ndof, dof_ids, k, q0_dev, &a->c, &tab)) return 1;
-  if (!pairs) {
-    if (tab->def_pairs.empty()) return fail("%s: the default pair list is empty: no collision pair of the model depends on the controlled dofs", who);
-    npair = (int)(tab->def_pairs.size() / 2); pairs = tab->def_pairs.data();
-  }
-  if (dist_pairs(b, npair, pairs, &a->c.pairs)) return 1;   // (refusals come before anything is launched)
+  if (pairs_resolve(b, who, tab, &npair, &pairs, &a->c.pairs)) return 1;
   const rsim_model* m = b->m;
   const int *gt = m->I("geom_type"), *gb = m->I("geom_bodyid");
   for (int p = 0; p < npair; p++)
@@ -2518,9 +2525,7 @@ extern "C" int rsim_config_motion_bound(rsim_batch* b, int ndof, const int32_t* 
   DSweep a;
   if (sweep_args(b, who, ndof, dof_ids, k, q0_dev, q1_dev, npair, pairs, &a)) return 1;
   a.bound = bound_dev;
-  const int e = rsim_launch_sweep(&a, b->stream);
-  if (e) return fail("%s: kernel launch failed: %s", who, hipGetErrorString((hipError_t)e));
-  return 0;
+  return launched(who, rsim_launch_sweep(&a, b->stream));
 }
 extern "C" int rsim_config_sweep(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q0_dev, const float* q1_dev, int npair, const int32_t* pairs,
                                  float distmax, const rsim_sweep_opts* opts, int32_t* status_dev, float* t_dev, float* dist_dev, float* tmin_dev, int32_t* pair_dev,
@@ -2541,9 +2546,7 @@ extern "C" int rsim_config_sweep(rsim_batch* b, int ndof, const int32_t* dof_ids
   a.c.distmax = distmax; a.c.tol = o.tol; a.c.max_iters = o.max_iters;
   a.margin = o.margin; a.slack = o.slack; a.max_steps = o.max_steps;
   a.c.status = status_dev; a.t = t_dev; a.c.dist = dist_dev; a.tmin = tmin_dev; a.c.pair = pair_dev; a.c.fromto = fromto_dev; a.steps = steps_dev;
-  const int e = rsim_launch_sweep(&a, b->stream);
-  if (e) return fail("%s: kernel launch failed: %s", who, hipGetErrorString((hipError_t)e));
-  return 0;
+  return launched(who, rsim_launch_sweep(&a, b->stream));
 }
 
 // mj_fullM (controllers/parts/controller.py:226-227: `mujoco.mj_fullM(model, mass_matrix, data.qM)`): the dense joint-space inertia of one env

@@ -42,8 +42,6 @@ struct Cand { const float *ft, *qpos, *q, *xpos, *xquat; };
 // rows of the candidate, indexed by body id (by_body).
 struct PoseStore { float *pos, *quat; size_t pe, ps, qe, qs; int by_body; };
 
-RSIM_HD V3 ld3(const float* p) { return v3(p[0], p[1], p[2]); }
-RSIM_HD Q4 ldq(const float* p) { Q4 q = {p[0], p[1], p[2], p[3]}; return q; }
 RSIM_HD Pose load_pose(const PoseStore& s, int i) {
   const float *p = s.pos + (size_t)i * s.pe, *q = s.quat + (size_t)i * s.qe;
   Pose r;
@@ -60,20 +58,6 @@ RSIM_HD Pose env_pose(const Cand& c, int body) {
   Pose r;
   r.p = ld3(c.xpos + 3 * (size_t)body); r.q = ldq(c.xquat + 4 * (size_t)body);
   return r;
-}
-
-// sine and cosine by quadrant reduction and two short polynomials, as the step kernel's position stage takes them (rsim_step.hip sincos_f)
-RSIM_HD void sincos_f(float x, float& sn, float& cs) {
-  const float k = rintf(x * 0.636619772367581343f);
-  float r = fmaf(-k, 1.57079625129699707031f, x);
-  r = fmaf(-k, 7.54978941586159635335e-08f, r);
-  const float r2 = r * r;
-  const float sp = r * fmaf(r2, fmaf(r2, fmaf(r2, fmaf(r2, 2.7557319e-6f, -1.9841270e-4f), 8.3333333e-3f), -1.6666667e-1f), 1.0f);
-  const float cp = fmaf(r2, fmaf(r2, fmaf(r2, fmaf(r2, fmaf(r2, -2.7557319e-7f, 2.4801587e-5f), -1.3888889e-3f), 4.1666667e-2f), -0.5f), 1.0f);
-  const int q = (int)k & 3;
-  const float s1 = (q & 1) ? cp : sp, c1 = (q & 1) ? sp : cp;
-  sn = (q & 2) ? -s1 : s1;
-  cs = ((q + 1) & 2) ? -c1 : c1;
 }
 
 // ---- the per-body FK step ---------------------------------------------------------------------------------------------------------------------------------

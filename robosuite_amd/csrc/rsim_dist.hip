@@ -18,9 +18,6 @@
 using namespace rsim_dist;
 
 namespace {
-__device__ __forceinline__ V3 ld3(const float* p) { return v3(p[0], p[1], p[2]); }
-__device__ __forceinline__ Q4 ldq(const float* p) { Q4 q = {p[0], p[1], p[2], p[3]}; return q; }
-
 // world pose of geom g in this lane's env; the position is left absolute (the caller subtracts the pair's origin)
 __device__ __forceinline__ Geom load_geom(const DDist& a, int g, const float* ft, const float* xpos, const float* xquat, int vadr, int vnum) {
   const DRayGeom& s = a.geom[g];

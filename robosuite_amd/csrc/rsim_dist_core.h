@@ -17,38 +17,11 @@
 #pragma once
 #include <math.h>
 #include <stdint.h>
-#if defined(__HIPCC__)
-#define RSIM_HD __host__ __device__ __forceinline__
-#else
-#define RSIM_HD inline
-#endif
+#include "rsim_vec.h"
 
 namespace rsim_dist {
-struct V3 { float x, y, z; };
-struct Q4 { float w, x, y, z; };
-RSIM_HD V3 v3(float x, float y, float z) { V3 r = {x, y, z}; return r; }
-RSIM_HD V3 operator+(V3 a, V3 b) { return v3(a.x + b.x, a.y + b.y, a.z + b.z); }
-RSIM_HD V3 operator-(V3 a, V3 b) { return v3(a.x - b.x, a.y - b.y, a.z - b.z); }
-RSIM_HD V3 operator-(V3 a) { return v3(-a.x, -a.y, -a.z); }
-RSIM_HD V3 operator*(V3 a, float s) { return v3(a.x * s, a.y * s, a.z * s); }
-RSIM_HD float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-RSIM_HD V3 cross(V3 a, V3 b) { return v3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
+using namespace rsim_vec;
 RSIM_HD float triple(V3 a, V3 b, V3 c) { return dot(a, cross(b, c)); }
-RSIM_HD Q4 qmul(Q4 a, Q4 b) {
-  Q4 r = {a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z, a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y,
-          a.w * b.y - a.x * b.z + a.y * b.w + a.z * b.x, a.w * b.z + a.x * b.y - a.y * b.x + a.z * b.w};
-  return r;
-}
-RSIM_HD Q4 qunit(Q4 q) {
-  const float n = 1.f / sqrtf(q.w * q.w + q.x * q.x + q.y * q.y + q.z * q.z);
-  Q4 r = {q.w * n, q.x * n, q.y * n, q.z * n};
-  return r;
-}
-RSIM_HD V3 qrot(Q4 q, V3 v) {   // v + 2 w (u x v) + 2 u x (u x v)
-  const V3 u = v3(q.x, q.y, q.z);
-  const V3 t = cross(u, v) * 2.f;
-  return v + t * q.w + cross(u, t);
-}
 
 enum { G_PLANE = 0, G_SPHERE = 2, G_CAPSULE = 3, G_ELLIPSOID = 4, G_CYLINDER = 5, G_BOX = 6, G_MESH = 7 };   // mjtGeom
 enum { DIST_OK = 0, DIST_FAR = 1, DIST_OVERLAP = 2, DIST_CAP = 256 };                                        // include/rsim.h RSIM_DIST_*

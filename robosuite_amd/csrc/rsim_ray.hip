@@ -20,34 +20,11 @@
 #include <hip/hip_runtime.h>
 #include "../../include/rsim.h"
 #include "rsim_ray.h"
+#include "rsim_vec.h"
 
 namespace {
-struct V3 { float x, y, z; };
-struct Q4 { float w, x, y, z; };
+using namespace rsim_vec;
 struct Iv { float n, f; };   // parameter interval of a line inside a convex solid; n > f: empty
-__device__ __forceinline__ V3 v3(float x, float y, float z) { V3 r = {x, y, z}; return r; }
-__device__ __forceinline__ V3 operator+(V3 a, V3 b) { return v3(a.x + b.x, a.y + b.y, a.z + b.z); }
-__device__ __forceinline__ V3 operator-(V3 a, V3 b) { return v3(a.x - b.x, a.y - b.y, a.z - b.z); }
-__device__ __forceinline__ V3 operator*(V3 a, float s) { return v3(a.x * s, a.y * s, a.z * s); }
-__device__ __forceinline__ float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ V3 cross(V3 a, V3 b) { return v3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
-__device__ __forceinline__ V3 ld3(const float* p) { return v3(p[0], p[1], p[2]); }
-__device__ __forceinline__ Q4 ldq(const float* p) { Q4 q = {p[0], p[1], p[2], p[3]}; return q; }
-__device__ __forceinline__ Q4 qmul(Q4 a, Q4 b) {
-  Q4 r = {a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z, a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y,
-          a.w * b.y - a.x * b.z + a.y * b.w + a.z * b.x, a.w * b.z + a.x * b.y - a.y * b.x + a.z * b.w};
-  return r;
-}
-__device__ __forceinline__ Q4 qunit(Q4 q) {
-  const float n = 1.f / sqrtf(q.w * q.w + q.x * q.x + q.y * q.y + q.z * q.z);
-  Q4 r = {q.w * n, q.x * n, q.y * n, q.z * n};
-  return r;
-}
-__device__ __forceinline__ V3 qrot(Q4 q, V3 v) {   // v + 2 w (u x v) + 2 u x (u x v)
-  const V3 u = v3(q.x, q.y, q.z);
-  const V3 t = cross(u, v) * 2.f;
-  return v + t * q.w + cross(u, t);
-}
 
 constexpr float BIG = 3.0e38f;
 constexpr float PAR = 1e-14f;   // a direction component below sqrt(PAR) |dir| counts as parallel (far below what fp32 resolves of a direction)

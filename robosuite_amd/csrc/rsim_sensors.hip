@@ -21,28 +21,10 @@
 #include <hip/hip_runtime.h>
 #include "../../include/rsim.h"
 #include "rsim_sensors.h"
+#include "rsim_vec.h"
 
 namespace {
-struct V3 { float x, y, z; };
-struct Q4 { float w, x, y, z; };
-__device__ __forceinline__ V3 v3(float x, float y, float z) { V3 r = {x, y, z}; return r; }
-__device__ __forceinline__ V3 operator+(V3 a, V3 b) { return v3(a.x + b.x, a.y + b.y, a.z + b.z); }
-__device__ __forceinline__ V3 operator-(V3 a, V3 b) { return v3(a.x - b.x, a.y - b.y, a.z - b.z); }
-__device__ __forceinline__ V3 operator*(V3 a, float s) { return v3(a.x * s, a.y * s, a.z * s); }
-__device__ __forceinline__ float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ V3 cross(V3 a, V3 b) { return v3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
-__device__ __forceinline__ V3 ld3(const float* p) { return v3(p[0], p[1], p[2]); }
-__device__ __forceinline__ Q4 ldq(const float* p) { Q4 q = {p[0], p[1], p[2], p[3]}; return q; }
-__device__ __forceinline__ Q4 qmul(Q4 a, Q4 b) {
-  Q4 r = {a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z, a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y,
-          a.w * b.y - a.x * b.z + a.y * b.w + a.z * b.x, a.w * b.z + a.x * b.y - a.y * b.x + a.z * b.w};
-  return r;
-}
-__device__ __forceinline__ V3 qrot(Q4 q, V3 v) {   // v + 2 w (u x v) + 2 u x (u x v)
-  const V3 u = v3(q.x, q.y, q.z);
-  const V3 t = cross(u, v) * 2.f;
-  return v + t * q.w + cross(u, t);
-}
+using namespace rsim_vec;
 __device__ __forceinline__ V3 qrot_inv(Q4 q, V3 v) { Q4 c = {q.w, -q.x, -q.y, -q.z}; return qrot(c, v); }
 
 // does the ray p + t d, t >= 0, meet the solid (sphere of radius s.x | ellipsoid of semi-axes s | box of half-sizes s) centred at the origin?  A ray that

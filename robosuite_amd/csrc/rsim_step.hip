@@ -263,16 +263,9 @@ struct ProfT<false> {
 // ------------------------------------------------------------------------------------------------------------
 // small math (float)
 // ------------------------------------------------------------------------------------------------------------
-struct V3 { float x, y, z; };
-__device__ __forceinline__ V3 v3(float x, float y, float z) { V3 r = {x, y, z}; return r; }
-__device__ __forceinline__ V3 ld3(const float* p) { return v3(p[0], p[1], p[2]); }
+#include "rsim_vec.h"   // V3, Q4, their arithmetic, ld3 / ldq, qmul, qunit, qrot, sincos_f: shared with every other kernel
+using namespace rsim_vec;
 __device__ __forceinline__ void st3(float* p, V3 a) { p[0] = a.x; p[1] = a.y; p[2] = a.z; }
-__device__ __forceinline__ V3 operator+(V3 a, V3 b) { return v3(a.x + b.x, a.y + b.y, a.z + b.z); }
-__device__ __forceinline__ V3 operator-(V3 a, V3 b) { return v3(a.x - b.x, a.y - b.y, a.z - b.z); }
-__device__ __forceinline__ V3 operator*(V3 a, float s) { return v3(a.x * s, a.y * s, a.z * s); }
-__device__ __forceinline__ V3 operator-(V3 a) { return v3(-a.x, -a.y, -a.z); }
-__device__ __forceinline__ float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ V3 cross(V3 a, V3 b) { return v3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
 __device__ __forceinline__ float norm(V3 a) { return sqrtf(dot(a, a)); }
 __device__ __forceinline__ V3 normalized(V3 a, float* len = nullptr) {
   float n = norm(a);
@@ -280,14 +273,7 @@ __device__ __forceinline__ V3 normalized(V3 a, float* len = nullptr) {
   if (n < FMIN) return v3(1, 0, 0);
   return a * (1.0f / n);
 }
-struct Q4 { float w, x, y, z; };
-__device__ __forceinline__ Q4 ldq(const float* p) { Q4 q = {p[0], p[1], p[2], p[3]}; return q; }
 __device__ __forceinline__ void stq(float* p, Q4 q) { p[0] = q.w; p[1] = q.x; p[2] = q.y; p[3] = q.z; }
-__device__ __forceinline__ Q4 qmul(Q4 a, Q4 b) {
-  Q4 r = {a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z, a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y,
-          a.w * b.y - a.x * b.z + a.y * b.w + a.z * b.x, a.w * b.z + a.x * b.y - a.y * b.x + a.z * b.w};
-  return r;
-}
 __device__ __forceinline__ Q4 qnorm(Q4 q) {
   float n = sqrtf(q.w * q.w + q.x * q.x + q.y * q.y + q.z * q.z);
   if (n < FMIN) { Q4 r = {1, 0, 0, 0}; return r; }
@@ -629,19 +615,6 @@ __device__ __forceinline__ void solve3(const float* A, const float* b, float* x)
   x[1] = (c01 * b[0] + c11 * b[1] + c21 * b[2]) * id;
   x[2] = (c02 * b[0] + c12 * b[1] + c22 * b[2]) * id;
 }
-// sin and cos of a bounded angle (|x| < ~1e3): Cody-Waite reduction to [-pi/4, pi/4] + Taylor kernels (abs error < 2e-7)
-__device__ __forceinline__ void sincos_f(float x, float& sn, float& cs) {
-  const float k = rintf(x * 0.636619772367581343f);
-  float r = fmaf(-k, 1.57079625129699707031f, x);
-  r = fmaf(-k, 7.54978941586159635335e-08f, r);
-  const float r2 = r * r;
-  const float sp = r * fmaf(r2, fmaf(r2, fmaf(r2, fmaf(r2, 2.7557319e-6f, -1.9841270e-4f), 8.3333333e-3f), -1.6666667e-1f), 1.0f);
-  const float cp = fmaf(r2, fmaf(r2, fmaf(r2, fmaf(r2, fmaf(r2, -2.7557319e-7f, 2.4801587e-5f), -1.3888889e-3f), 4.1666667e-2f), -0.5f), 1.0f);
-  const int q = (int)k & 3;
-  const float s1 = (q & 1) ? cp : sp, c1 = (q & 1) ? sp : cp;
-  sn = (q & 2) ? -s1 : s1;
-  cs = ((q + 1) & 2) ? -c1 : c1;
-}
 
 // ---- orientation interpolator of OSC_POSE (LinearInterpolator in 'euler' mode, utils/traj_utils.py:129-146) ------------------------------
 // start / goal are orientation-error vectors that the reference treats as Euler angles:
@@ -680,12 +653,6 @@ __device__ __forceinline__ V3 euler_slerp(V3 start, V3 goal, float fraction) {
   const float m21 = k * (qy * qz + qx * qw), m22 = 1.f - k * (qx * qx + qy * qy);
   const float cy = sqrtf(m00 * m00 + m10 * m10);
   return v3(atan2f(m21, m22), atan2f(-m20, cy), atan2f(m10, m00));   // cy = 0 (gimbal lock) needs a pi/2 error component: out of the |e| <= 1 range
-}
-// rotate v by unit quaternion q
-__device__ __forceinline__ V3 qrot(Q4 q, V3 v) {
-  const V3 u = v3(q.x, q.y, q.z);
-  const V3 t = cross(u, v) * 2.0f;
-  return v + t * q.w + cross(u, t);
 }
 __device__ __forceinline__ float bitf(unsigned bits, int i) { return (float)((bits >> i) & 1u); }
 __device__ __forceinline__ float comp6(S6 a, int r) { return r < 3 ? (r == 0 ? a.a.x : (r == 1 ? a.a.y : a.a.z)) : (r == 3 ? a.l.x : (r == 4 ? a.l.y : a.l.z)); }

@@ -23,7 +23,7 @@ VARIANT = os.path.join(ROOT, "robosuite_amd", "librsim_hip_pretest.so")
 
 def _source_key():
     h = hashlib.sha256()
-    for f in ("rsim_step.hip", "rsim_internal.h", "rsim_api.cpp", "Makefile", os.path.join("..", "..", "include", "rsim.h")):
+    for f in ("rsim_step.hip", "rsim_vec.h", "rsim_internal.h", "rsim_api.cpp", "Makefile", os.path.join("..", "..", "include", "rsim.h")):
         h.update(open(os.path.join(CSRC, f), "rb").read())
     return h.hexdigest()
 
