@@ -598,9 +598,9 @@ int rsim_geom_distance(rsim_batch* b, int npair, const int32_t* pairs /* HOST [n
  * the first call that names them and kept in the batch: a repeat call allocates nothing.
  * Refused by name (rsim_last_error): ndof outside 1 .. RSIM_JNT_MAX, a dof id out of range or listed twice, a dof of a free or ball joint, a mocap body among the
  * moved bodies, k < 1, the pair refusals of rsim_geom_distance, an empty default list.
- * NOT HANDLED: A GRASPED OBJECT DOES NOT MOVE WITH THE CANDIDATE -- it is a free body at its current pose.  Also not carried: candidates for free or ball joints,
- * a clearance term inside IK or the fused step, heightfields.  (Swept checks along a path: rsim_config_sweep below.)  robosuite_amd/clearance.py is the fp64
- * host mirror. */
+ * A GRASPED OBJECT moves with the candidate only where the caller says so: the _attached entries below (rsim_attach).  In the entries here it is a free body at
+ * its current pose.  Not carried: candidates for free or ball joints, a clearance term inside IK or the fused step, heightfields.  (Swept checks along a path:
+ * rsim_config_sweep below.)  robosuite_amd/clearance.py is the fp64 host mirror. */
 typedef struct rsim_clear_opts { float tol; int32_t max_iters; int32_t chunks; } rsim_clear_opts;   /* NULL: rsim_dist defaults, chunks 0 = automatic */
 /* poses of ALL bodies at the candidates (unmoved bodies: the env's current pose) */
 int rsim_config_fk(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev /* [B][k][ndof] */,
@@ -643,9 +643,9 @@ int rsim_config_clearance(rsim_batch* b, int ndof, const int32_t* dof_ids, int k
  * NOTE on pairs that stay close: ONE bound L serves the whole list, so a listed pair that sits within margin + slack whatever the dofs do makes every segment a
  * HIT at its first sample, and one that sits just above it holds every step to (its distance - margin) / L.  The Panda's link0 / link1 collision geoms stand
  * 1.0 mm apart at every joint angle: hand in a list without such pairs (parent against child, as a rule).  Per-pair bounds are not carried.
- * NOT HANDLED: A GRASPED OBJECT DOES NOT MOVE WITH THE MOTION -- it is a free body at its current pose.  Also not carried: free and ball joints as controlled
- * dofs, interpolation other than linear in joint space, per-pair bounds, a sweep term inside IK or the fused step.  robosuite_amd/sweep.py is the fp64 host
- * mirror. */
+ * A GRASPED OBJECT moves with the motion only where the caller says so: rsim_config_sweep_attached below (rsim_attach); here it is a free body at its current
+ * pose.  Not carried: free and ball joints as controlled dofs, interpolation other than linear in joint space, per-pair bounds, a sweep term inside IK or the
+ * fused step.  robosuite_amd/sweep.py is the fp64 host mirror. */
 #define RSIM_SWEEP_FREE 0
 #define RSIM_SWEEP_HIT 1
 #define RSIM_SWEEP_UNDECIDED 2
@@ -659,6 +659,58 @@ int rsim_config_sweep(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, co
                       int32_t* pair_dev /* [B][k] */, float* fromto_dev /* [B][k][6] or NULL */, int32_t* steps_dev /* [B][k] or NULL */);
 int rsim_config_motion_bound(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q0_dev, const float* q1_dev,
                              int npair, const int32_t* pairs /* as above */, float* bound_dev /* [B][k] */);
+
+/* Carried objects: the five queries above with bodies ATTACHED to links, for the transport half of a pick-and-place.  Each _attached entry is the entry of the
+ * same name plus a const rsim_attach*; NULL or n == 0 IS that entry, with its results, its tables and its kernels.
+ *   attachment  a pair (body, carrier) of model body ids, up to RSIM_ATTACH_MAX per call, a HOST list like the dof list.  `body` is a child of the world whose
+ *               only joint is a free joint (what a robosuite object is); `carrier` is a body the controlled dofs move.  While HELD, body rides rigidly on
+ *               carrier: X_body(q) = X_carrier(q) o rel, the quaternion normalised once, as for every walked body.  Its free joint is ignored; the bodies below
+ *               it are walked as ordinary moved bodies with their joints held at the env's qpos.
+ *   held_dev    DEVICE [B][n] uint8, or NULL: every attachment is held in every env.  An env with 0 treats that body exactly as the plain entries do: a free body
+ *               at its current pose, bit for bit (its subtree too).  The caller decides what is grasped; nothing on the device does.
+ *   rel_dev     DEVICE [B][n][7], position and wxyz quaternion of body in the carrier's frame ("what if I held it like this", before the grasp exists; the
+ *               quaternion is normalised), or NULL: taken in the walk, in fp32, from the env's current RSIM_XPOS / RSIM_XQUAT, brought up to date first as every
+ *               derived read is: p_rel = R_c^T (p_b - p_c), q_rel = conj(q_c) q_b.
+ *   signature   a held body and its subtree take the carrier's dof signature; not held, they keep their own (empty) one.
+ *   pairs       THE DEFAULT LIST with attachments is the model's collision pairs whose two bodies' signatures differ under at least one held row, in the collision
+ *               list's order, without the distance query's refusals; rsim_config_pairs_attached returns it.  PER ENV A LISTED PAIR IS EVALUATED ONLY IF ITS TWO
+ *               SIGNATURES DIFFER UNDER THAT ENV'S held ROW: a held cube against the fingers that hold it drops out (it would read 0 for ever), a held cube
+ *               against the table comes in, and in an env that holds nothing cube against table drops out as it does in the plain entry.  An env that evaluates
+ *               no pair reads far.  AN EXPLICIT LIST IS TAKEN AS GIVEN, as in the plain entries: every pair in every env, no skipping.  `pair` in the results
+ *               indexes the list handed in or returned.
+ *   bound L     a held body has Omega = Omega(carrier) and V = V(carrier) + Omega(carrier) |p_rel|, and its subtree follows by the plain rules; one that is not
+ *               held stands still.  L is the maximum over the pairs the env evaluates, times the same 1 + 2^-16.  The certificate carries over unchanged: a held
+ *               body's origin is p_c(t) + R_c(t) p_rel with p_rel constant along the motion, so its speed is at most V(carrier) + Omega(carrier) |p_rel| and
+ *               its angular speed Omega(carrier) -- the body step's bound with p_rel for body_pos; and the set of evaluated pairs does not depend on t, so c(t) is
+ *               L-Lipschitz as before.  A plane on an attached body is refused, as on any moved body.
+ * Refused by name, before anything is launched: n outside 0 .. RSIM_ATTACH_MAX or a NULL list; a body id out of range; a body attached twice; a body that is
+ * not a world child with exactly one free joint; a mocap body; a free joint, or a controlled joint, anywhere below it; a carrier that is an attached body or
+ * below one; a carrier the dof list does not move.
+ * The body table's key in the batch is the dof list plus the attachment list: a batch that never names an attachment builds no new table.  A call with
+ * attachments runs a second instantiation of the kernels (k_clear_fk_att, k_clear_dist_att, k_sweep_att); the plain kernels are the instantiation with the
+ * attachment branches compiled away (the registers and instruction counts they had; the order of the prologue's loads and the size of the kernel argument differ).
+ * NOT HANDLED: deciding on the device whether an object is grasped; an object attached to another attached object; attachments in rsim_ik_site, the fused step
+ * or rsim_geom_distance; per-env skipping for explicit pair lists; per-pair motion bounds; free or ball joints as controlled dofs; heightfields. */
+#define RSIM_ATTACH_MAX 4
+typedef struct rsim_attach {
+  int32_t n;
+  const int32_t* bodies;      /* HOST [n][2]: (body, carrier) */
+  const uint8_t* held_dev;    /* DEVICE [B][n], or NULL: all held */
+  const float* rel_dev;       /* DEVICE [B][n][7], or NULL: from the env's current poses */
+} rsim_attach;
+int rsim_config_fk_attached(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, float* xpos_dev, float* xquat_dev, const rsim_attach* att);
+int rsim_config_pairs_attached(const rsim_model* m, int ndof, const int32_t* dof_ids, int max_pairs, int32_t* pairs_out,
+                               int nattach, const int32_t* attach_bodies /* HOST [nattach][2] */);
+int rsim_config_clearance_attached(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, int npair, const int32_t* pairs, float distmax,
+                                   const rsim_clear_opts* opts, float* dist_dev, int32_t* pair_dev, float* fromto_dev, int32_t* status_dev, const rsim_attach* att);
+int rsim_config_sweep_attached(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q0_dev, const float* q1_dev, int npair, const int32_t* pairs,
+                               float distmax, const rsim_sweep_opts* opts, int32_t* status_dev, float* t_dev, float* dist_dev, float* tmin_dev, int32_t* pair_dev,
+                               float* fromto_dev, int32_t* steps_dev, const rsim_attach* att);
+int rsim_config_motion_bound_attached(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q0_dev, const float* q1_dev,
+                                      int npair, const int32_t* pairs, float* bound_dev, const rsim_attach* att);
+/* how many body tables the batch holds: one per (dof list, attachment list) a config_* call has named so far.  A DIAGNOSTIC, not part of the query contract:
+ * it exists so that "a batch that never names an attachment builds no new table" can be checked from outside (tests/test_attach.py); no result depends on it. */
+int rsim_config_tables(const rsim_batch* b);
 
 #ifdef __cplusplus
 }

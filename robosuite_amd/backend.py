@@ -283,6 +283,11 @@ def lib():
             L.rsim_config_sweep.argtypes = [vp, C.c_int, C.POINTER(C.c_int32), C.c_int, vp, vp, C.c_int, C.POINTER(C.c_int32), C.c_float, C.POINTER(SweepOpts), vp, vp, vp, vp,
                                             vp, vp, vp]
             L.rsim_config_motion_bound.argtypes = [vp, C.c_int, C.POINTER(C.c_int32), C.c_int, vp, vp, C.c_int, C.POINTER(C.c_int32), vp]
+        if hasattr(L, "rsim_config_sweep_attached"):
+            for f in ("rsim_config_fk", "rsim_config_clearance", "rsim_config_sweep", "rsim_config_motion_bound"):
+                getattr(L, f + "_attached").argtypes = list(getattr(L, f).argtypes) + [C.POINTER(Attach)]
+            L.rsim_config_pairs_attached.argtypes = list(L.rsim_config_pairs.argtypes) + [C.c_int, C.POINTER(C.c_int32)]
+            L.rsim_config_tables.argtypes = [vp]
         L.rsim_comm_unique_id.argtypes = [vp, C.c_size_t]
         L.rsim_comm_create.argtypes = [vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
         L.rsim_allreduce_stats.argtypes = [vp, vp, C.c_int, C.c_int]
@@ -490,6 +495,10 @@ class ClearOpts(C.Structure):    # include/rsim.h rsim_clear_opts
 
 class SweepOpts(C.Structure):    # include/rsim.h rsim_sweep_opts
     _fields_ = [("tol", C.c_float), ("max_iters", C.c_int32), ("margin", C.c_float), ("slack", C.c_float), ("max_steps", C.c_int32)]
+
+
+class Attach(C.Structure):       # include/rsim.h rsim_attach
+    _fields_ = [("n", C.c_int32), ("bodies", C.POINTER(C.c_int32)), ("held_dev", C.c_void_p), ("rel_dev", C.c_void_p)]
 
 
 class _DevArray:
@@ -931,43 +940,88 @@ class HipBatch:
             raise RsimError(f"{who}: q must have shape ({self.B}, K, {n}) with K >= 1 (or ({self.B}, {n}) for K = 1), got {tuple(q.shape)}")
         return dofs, q.contiguous().float().reshape(self.B, K, n), K, flat2
 
-    def config_fk(self, dofs, q):
+    def _attach(self, who, attach, held, rel):
+        """the carried objects of a config_* call (include/rsim.h rsim_attach): attach = [(body id, carrier body id), ...] on the host, held = None (all held) or
+        a bool / uint8 CUDA tensor [B] or [B, n], rel = None (from the env's current poses) or a float32 CUDA tensor [B, n, 7].  -> (the C argument or None for a
+        call without attachments, what must stay alive until the call returns)"""
+        import torch
+
+        if attach is None or len(attach) == 0:
+            if held is not None or rel is not None:
+                raise RsimError(f"{who}: held / rel given without attach")
+            return None, None
+        a = np.ascontiguousarray(np.asarray(attach), dtype=np.int32)
+        if a.ndim != 2 or a.shape[1] != 2:
+            raise RsimError(f"{who}: attach must be a list of (body, carrier) pairs, got shape {tuple(a.shape)}")
+        n = int(a.shape[0])
+        dev = torch.device(f"cuda:{self.device}")
+        h = r = None
+        if held is not None:
+            h = torch.as_tensor(held)
+            if h.device != dev or h.dtype not in (torch.bool, torch.uint8) or tuple(h.shape) not in ((self.B,), (self.B, n)):
+                raise RsimError(f"{who}: held must be a bool or uint8 tensor of shape ({self.B},) or ({self.B}, {n}) on {dev}, got {h.dtype} {tuple(h.shape)} on {h.device}")
+            h = (h.reshape(self.B, -1).expand(self.B, n) != 0).to(torch.uint8).contiguous()
+        if rel is not None:
+            if not isinstance(rel, torch.Tensor) or rel.device != dev or tuple(rel.shape) != (self.B, n, 7):
+                raise RsimError(f"{who}: rel must be a float32 tensor of shape ({self.B}, {n}, 7) on {dev}")
+            r = rel.contiguous().float()
+        arg = Attach(n, a.ctypes.data_as(C.POINTER(C.c_int32)), h.data_ptr() if h is not None else None, r.data_ptr() if r is not None else None)
+        return arg, (a, h, r)
+
+    def config_tables(self):
+        """how many body tables the batch holds: one per (dof list, attachment list) a config_* call has named so far.  A diagnostic (include/rsim.h)."""
+        if not hasattr(self._L, "rsim_config_tables"):      # (a library built before carried objects, as the A/B tools load through RSIM_LIB)
+            raise RsimError("config_tables: the loaded library has no rsim_config_tables")
+        return int(self._L.rsim_config_tables(self.ptr))
+
+    def config_fk(self, dofs, q, attach=None, held=None, rel=None):
         """Body poses at candidate joint vectors, away from the state: q is a CUDA float32 tensor [B, K, n] of positions of the controlled `dofs` (dof ids of
         hinge / slide joints, as for solve_ik; they need not lie on one chain), or [B, n] for K = 1.  Every other joint is held at the env's current qpos; no
         range clamp.  -> (xpos [B, K, nbody, 3], xquat [B, K, nbody, 4] wxyz) of ALL bodies ([B, nbody, .] for 2-D q); a body the dofs do not move reads the
-        env's current pose.  FK on each env's own model parameters; a pure query on the batch's stream.  robosuite_amd/clearance.py is the fp64 mirror."""
+        env's current pose.  FK on each env's own model parameters; a pure query on the batch's stream.  robosuite_amd/clearance.py is the fp64 mirror.
+        attach / held / rel: carried objects (_attach) -- in the envs that hold it an attached free body rides on its carrier, X_carrier(q) o rel."""
         import torch
 
         dofs, qc, K, flat2 = self._config_q("config_fk", dofs, q)
+        att, _keep = self._attach("config_fk", attach, held, rel)
         nb = int(self.model.flat.nbody)
         xp = torch.empty((self.B, K, nb, 3), dtype=torch.float32, device=qc.device)
         xq = torch.empty((self.B, K, nb, 4), dtype=torch.float32, device=qc.device)
         self._ray_fence_in()
-        _chk(self._L.rsim_config_fk(self.ptr, len(dofs), (C.c_int32 * len(dofs))(*dofs), K, C.c_void_p(qc.data_ptr()), C.c_void_p(xp.data_ptr()), C.c_void_p(xq.data_ptr())))
+        args = (self.ptr, len(dofs), (C.c_int32 * len(dofs))(*dofs), K, C.c_void_p(qc.data_ptr()), C.c_void_p(xp.data_ptr()), C.c_void_p(xq.data_ptr()))
+        _chk(self._L.rsim_config_fk(*args) if att is None else self._L.rsim_config_fk_attached(*args, C.byref(att)))
         self._ray_fence_out()
         return (xp[:, 0], xq[:, 0]) if flat2 else (xp, xq)
 
-    def config_pairs(self, dofs):
+    def config_pairs(self, dofs, attach=None):
         """The default pair list of config_clearance for `dofs`: int32 [P, 2] model geom ids -- the model's collision pairs whose two bodies the candidate can
-        move relative to each other (different dof signatures), in the collision list's order, without the pairs geom_distance refuses."""
+        move relative to each other (different dof signatures; with attach: under at least one held row), in the collision list's order, without the pairs
+        geom_distance refuses."""
         dofs = [int(d) for d in np.asarray(dofs).ravel()]
         arr = (C.c_int32 * max(len(dofs), 1))(*dofs)
-        n = self._L.rsim_config_pairs(self.model.ptr, len(dofs), arr, 0, None)
+        if attach is None or len(attach) == 0:
+            call = lambda cap, out: self._L.rsim_config_pairs(self.model.ptr, len(dofs), arr, cap, out)      # noqa: E731
+        else:
+            a = np.ascontiguousarray(np.asarray(attach), dtype=np.int32).reshape(-1, 2)
+            call = lambda cap, out: self._L.rsim_config_pairs_attached(self.model.ptr, len(dofs), arr, cap, out, len(a), a.ctypes.data_as(C.POINTER(C.c_int32)))   # noqa: E731
+        n = call(0, None)
         if n < 0:
             raise RsimError(lib().rsim_last_error().decode())
         out = np.zeros((n, 2), dtype=np.int32)
-        if self._L.rsim_config_pairs(self.model.ptr, len(dofs), arr, n, out.ctypes.data_as(C.POINTER(C.c_int32))) != n:
+        if call(n, out.ctypes.data_as(C.POINTER(C.c_int32))) != n:
             raise RsimError(lib().rsim_last_error().decode())
         return out
 
-    def config_clearance(self, dofs, q, pairs=None, distmax=1.0, fromto=True, tol=None, max_iters=None, chunks=0):
+    def config_clearance(self, dofs, q, pairs=None, distmax=1.0, fromto=True, tol=None, max_iters=None, chunks=0, attach=None, held=None, rel=None):
         """Is this joint configuration free, and by how much?  For K candidate joint vectors per env (q, dofs: as config_fk) the smallest distance between the
         geoms of `pairs` at the candidate's poses: pairs is an int array [P, 2] of MODEL geom ids (host; anything geom_distance accepts), or None for the
         default list (config_pairs).  -> (dist float32 [B, K], pair int32 [B, K] -- the index INTO THE LIST of the pair that attains dist, the lowest on ties
         --, fromto float32 [B, K, 6] of that pair or None with fromto=False, status int32 [B, K] of that pair); 2-D q gives [B] / [B, 6].  dist follows
         geom_distance: signed where exact, 0 with status 2 for other overlaps, a mesh geom is its convex hull; with no pair closer than distmax:
-        (distmax, -1, zeros, 1).  chunks: into how many pieces the pair list is cut for the device (0 = chosen from B K and P).  A grasped object does NOT move
-        with the candidate.  A pure query on the batch's stream; robosuite_amd/clearance.py is the fp64 host mirror."""
+        (distmax, -1, zeros, 1).  chunks: into how many pieces the pair list is cut for the device (0 = chosen from B K and P).  A grasped object moves with
+        the candidate only if the call says so: attach / held / rel (_attach).  With them the default list is config_pairs(dofs, attach), and an env evaluates
+        only the pairs its own held row makes candidate-dependent (a held cube against its fingers drops out, against the table comes in); an explicit list is
+        taken as given, every pair in every env.  A pure query on the batch's stream; robosuite_amd/clearance.py is the fp64 host mirror."""
         import torch
 
         from . import distance as _dist
@@ -977,6 +1031,7 @@ class HipBatch:
         except (TypeError, ValueError) as e:
             raise RsimError(str(e).replace("geom_distance", "config_clearance")) from None
         dofs, qc, K, flat2 = self._config_q("config_clearance", dofs, q)
+        att, _keep = self._attach("config_clearance", attach, held, rel)
         if pairs is None:
             n, parg = 0, None
         else:
@@ -991,8 +1046,9 @@ class HipBatch:
         st = torch.empty((self.B, K), dtype=torch.int32, device=dev)
         co = ClearOpts(o["tol"], o["max_iters"], int(chunks))
         self._ray_fence_in()
-        _chk(self._L.rsim_config_clearance(self.ptr, len(dofs), (C.c_int32 * len(dofs))(*dofs), K, C.c_void_p(qc.data_ptr()), n, parg, float(distmax), C.byref(co),
-                                           C.c_void_p(dist.data_ptr()), C.c_void_p(pid.data_ptr()), C.c_void_p(ft.data_ptr()) if fromto else None, C.c_void_p(st.data_ptr())))
+        args = (self.ptr, len(dofs), (C.c_int32 * len(dofs))(*dofs), K, C.c_void_p(qc.data_ptr()), n, parg, float(distmax), C.byref(co),
+                C.c_void_p(dist.data_ptr()), C.c_void_p(pid.data_ptr()), C.c_void_p(ft.data_ptr()) if fromto else None, C.c_void_p(st.data_ptr()))
+        _chk(self._L.rsim_config_clearance(*args) if att is None else self._L.rsim_config_clearance_attached(*args, C.byref(att)))
         self._ray_fence_out()
         if flat2:
             return dist[:, 0], pid[:, 0], (ft[:, 0] if fromto else None), st[:, 0]
@@ -1016,27 +1072,29 @@ class HipBatch:
             raise RsimError(f"{who}: npair < 1 or pairs not of shape [P, 2] (got shape {tuple(p.shape)})")
         return dofs, a, b, K, flat2, int(p.shape[0]), p.ctypes.data_as(C.POINTER(C.c_int32)), p
 
-    def config_motion_bound(self, dofs, q0, q1, pairs=None):
+    def config_motion_bound(self, dofs, q0, q1, pairs=None, attach=None, held=None, rel=None):
         """The motion bound L of config_sweep for K segments per env (q0, q1: as config_sweep): float32 [B, K] ([B] for 2-D ends) -- the distance of every
         listed pair changes by at most L |dt| along q(t) = q0 + t (q1 - q0).  The same device code the sweep runs first."""
         import torch
 
         dofs, a, b, K, flat2, n, parg, _keep = self._sweep_q("config_motion_bound", dofs, q0, q1, pairs)
+        att, _keep2 = self._attach("config_motion_bound", attach, held, rel)
         out = torch.empty((self.B, K), dtype=torch.float32, device=a.device)
         self._ray_fence_in()
-        _chk(self._L.rsim_config_motion_bound(self.ptr, len(dofs), (C.c_int32 * len(dofs))(*dofs), K, C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), n, parg,
-                                              C.c_void_p(out.data_ptr())))
+        args = (self.ptr, len(dofs), (C.c_int32 * len(dofs))(*dofs), K, C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), n, parg, C.c_void_p(out.data_ptr()))
+        _chk(self._L.rsim_config_motion_bound(*args) if att is None else self._L.rsim_config_motion_bound_attached(*args, C.byref(att)))
         self._ray_fence_out()
         return out[:, 0] if flat2 else out
 
-    def config_sweep(self, dofs, q0, q1, pairs=None, distmax=1.0, margin=0.0, slack=1e-3, max_steps=256, fromto=True, tol=None, max_iters=None):
+    def config_sweep(self, dofs, q0, q1, pairs=None, distmax=1.0, margin=0.0, slack=1e-3, max_steps=256, fromto=True, tol=None, max_iters=None, attach=None,
+                     held=None, rel=None):
         """Is the motion from q0 to q1 free?  For K joint-space segments per env, q(t) = q0 + t (q1 - q0), t in [0, 1] (q0, q1: CUDA float32 [B, K, n] positions
         of the controlled `dofs`, or [B, n] for K = 1; dofs, pairs, distmax, tol, max_iters: as config_clearance), by conservative advancement: a certificate,
         not a set of samples.  -> (status int32 [B, K]: 0 FREE, 1 HIT, 2 UNDECIDED, bit 8 set if a sample's distance iteration was capped; t float32: 1 for
         FREE, else the parameter of the last sample -- the motion has clearance > margin on [0, t); dist, t_min float32, pair int32, fromto float32 [B, K, 6] or
         None: those of the sample with the smallest distance, exactly config_clearance at q(t_min); steps int32: samples taken).  HIT: a sample came within
-        margin + slack; UNDECIDED: max_steps samples did not decide.  A grasped object does NOT move with the motion.  A pure query on the batch's stream;
-        robosuite_amd/sweep.py is the fp64 host mirror."""
+        margin + slack; UNDECIDED: max_steps samples did not decide.  A grasped object moves with the motion only if the call says so: attach / held / rel,
+        as for config_clearance; the bound L then covers the carried bodies.  A pure query on the batch's stream; robosuite_amd/sweep.py is the fp64 host mirror."""
         import torch
 
         from . import distance as _dist
@@ -1046,15 +1104,17 @@ class HipBatch:
         except (TypeError, ValueError) as e:
             raise RsimError(str(e).replace("geom_distance", "config_sweep")) from None
         dofs, a, b, K, flat2, n, parg, _keep = self._sweep_q("config_sweep", dofs, q0, q1, pairs)
+        att, _keep2 = self._attach("config_sweep", attach, held, rel)
         dev = a.device
         new = lambda dt, *tail: torch.empty((self.B, K) + tail, dtype=dt, device=dev)      # noqa: E731
         st, t, dist, tmin, pid, steps = new(torch.int32), new(torch.float32), new(torch.float32), new(torch.float32), new(torch.int32), new(torch.int32)
         ft = new(torch.float32, 6) if fromto else None
         so = SweepOpts(o["tol"], o["max_iters"], float(margin), float(slack), int(max_steps))
         self._ray_fence_in()
-        _chk(self._L.rsim_config_sweep(self.ptr, len(dofs), (C.c_int32 * len(dofs))(*dofs), K, C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), n, parg, float(distmax),
-                                       C.byref(so), C.c_void_p(st.data_ptr()), C.c_void_p(t.data_ptr()), C.c_void_p(dist.data_ptr()), C.c_void_p(tmin.data_ptr()),
-                                       C.c_void_p(pid.data_ptr()), C.c_void_p(ft.data_ptr()) if fromto else None, C.c_void_p(steps.data_ptr())))
+        args = (self.ptr, len(dofs), (C.c_int32 * len(dofs))(*dofs), K, C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), n, parg, float(distmax),
+                C.byref(so), C.c_void_p(st.data_ptr()), C.c_void_p(t.data_ptr()), C.c_void_p(dist.data_ptr()), C.c_void_p(tmin.data_ptr()),
+                C.c_void_p(pid.data_ptr()), C.c_void_p(ft.data_ptr()) if fromto else None, C.c_void_p(steps.data_ptr()))
+        _chk(self._L.rsim_config_sweep(*args) if att is None else self._L.rsim_config_sweep_attached(*args, C.byref(att)))
         self._ray_fence_out()
         out = (st, t, dist, tmin, pid, ft, steps)
         return tuple(x[:, 0] if flat2 and x is not None else x for x in out)

@@ -14,8 +14,19 @@ force (tests/test_clearance_host.py).
 Semantics (include/rsim.h).  A candidate holds positions of the controlled dofs, each of a hinge or slide joint; every other joint is held at `qpos`, and no
 range clamp is applied.  dist is the minimum over the pair list of that pair's geom distance at the candidate's poses, pair the index into the list of the pair
 that attains it (the lowest on ties), fromto and status that pair's; with no pair closer than distmax: (distmax, -1, zeros, distance.FAR).  A pair whose two
-bodies have the same signature cannot be changed by any candidate: the default list drops it, and skips what the distance query refuses.  NOT HANDLED: a
-grasped object does not move with the candidate -- it is a free body at its current pose."""
+bodies have the same signature cannot be changed by any candidate: the default list drops it, and skips what the distance query refuses.
+
+Carried objects (include/rsim.h rsim_attach).  attach = [(body, carrier), ...], up to ATTACH_MAX pairs of body ids: `body` a child of the world whose only joint
+is a free joint, `carrier` a body the dofs move.  held = ONE env's row, a bool per attachment (None: all held); rel = that env's [n, 7] rows, position and wxyz
+quaternion of body in the carrier's frame (None: from the poses at qpos, p_rel = R_c^T (p_b - p_c), q_rel = conj(q_c) q_b).  A held body rides on its carrier,
+X_body(q) = X_carrier(q) o rel, its free joint ignored, the bodies below it walked with their joints at qpos; it and its subtree take the carrier's signature.
+One that is not held is the free body at its current pose, with its own (empty) signature.  The default list with attachments holds the pairs whose two
+signatures differ under at least one held row; an env evaluates a listed pair only if they differ under its own row (active_pairs); an explicit list is taken
+as given, every pair in every env.  Without attach every function here is what it was.
+
+    active_pairs(flat, dofs, pairs, attach, held) -> bool [P]: which pairs of the default list an env with that held row evaluates
+
+NOT HANDLED: deciding whether an object is grasped (the caller says so); an object attached to an attached object; per-env skipping for explicit lists."""
 from __future__ import annotations
 
 from collections import OrderedDict
@@ -25,6 +36,7 @@ import numpy as np
 from . import distance, ik, mjcf
 
 MAX_DOFS = 16      # RSIM_JNT_MAX
+ATTACH_MAX = 4     # RSIM_ATTACH_MAX
 
 
 class ClearanceError(ValueError):
@@ -35,13 +47,18 @@ def _I(flat, name):
     return np.asarray(flat.arrays[name]).ravel().astype(int)
 
 
+def _joint_name(flat, j):
+    """'joint 3 (name)', the words of rsim_api.cpp ik_joint_name"""
+    names = flat.names.get("joint", []) if hasattr(flat, "names") else []
+    return f"joint {j}" + (f" ({names[j]})" if j < len(names) and names[j] else "")
+
+
 def _columns(flat, dofs):
     """{joint id: controlled column}, or ClearanceError naming what the query refuses"""
     dofs = [int(d) for d in np.asarray(dofs).ravel()]
     if not 1 <= len(dofs) <= MAX_DOFS:
         raise ClearanceError(f"clearance: ndof {len(dofs)} outside 1..{MAX_DOFS}")
     jtype, dadr, nv = _I(flat, "jnt_type"), _I(flat, "jnt_dofadr"), int(flat.nv)
-    names = flat.names.get("joint", []) if hasattr(flat, "names") else []
     out = {}
     for c, d in enumerate(dofs):
         if d < 0 or d >= nv:
@@ -51,14 +68,81 @@ def _columns(flat, dofs):
         width = np.where(jtype == mjcf.JNT_FREE, 6, np.where(jtype == mjcf.JNT_BALL, 3, 1))
         j = int(np.flatnonzero((dadr <= d) & (d < dadr + width))[0])
         if jtype[j] not in (mjcf.JNT_HINGE, mjcf.JNT_SLIDE):
-            nm = f"joint {j}" + (f" ({names[j]})" if j < len(names) and names[j] else "")
-            raise ClearanceError(f"clearance: controlled dof {d} belongs to {nm}, a {'free' if jtype[j] == mjcf.JNT_FREE else 'ball'} joint (hinge and slide joints only)")
+            raise ClearanceError(f"clearance: controlled dof {d} belongs to {_joint_name(flat, j)}, a {'free' if jtype[j] == mjcf.JNT_FREE else 'ball'} joint (hinge and slide joints only)")
         out[j] = c
     return out
 
 
-def signatures(flat, dofs):
-    """int [nbody]: the dof signature of every body as a bit mask of controlled columns"""
+def signatures(flat, dofs, attach=None, held=None):
+    """int [nbody]: the dof signature of every body as a bit mask of controlled columns; with attach, under one env's held row (None: all held)"""
+    sig = _signatures(flat, dofs)
+    att = _attachments(flat, dofs, attach, sig)
+    for (body, carrier), h in zip(att, _held_row(att, held)):
+        if h:
+            sig[subtree(flat, body)] = sig[carrier]
+    return sig
+
+
+def subtree(flat, body):
+    """the body and every body below it, ascending"""
+    parent = _I(flat, "body_parentid")
+    out = [int(body)]
+    for b in range(int(body) + 1, int(flat.nbody)):
+        if parent[b] in out:
+            out.append(b)
+    return out
+
+
+def _held_row(att, held):
+    if held is None:
+        return [True] * len(att)
+    row = [bool(h) for h in np.asarray(held).ravel()]
+    if len(row) != len(att):
+        raise ClearanceError(f"clearance: held has {len(row)} entries for {len(att)} attachments")
+    return row
+
+
+def _attachments(flat, dofs, attach, sig=None):
+    """[(body, carrier), ...] as ints, or ClearanceError naming what the query refuses (the order and the words of rsim_api.cpp clear_plan)"""
+    if attach is None or len(attach) == 0:
+        return []
+    att = [(int(b), int(c)) for b, c in np.asarray(attach).reshape(-1, 2)]
+    if len(att) > ATTACH_MAX:
+        raise ClearanceError(f"clearance: {len(att)} attachments outside 0..{ATTACH_MAX} (RSIM_ATTACH_MAX)")
+    sig = _signatures(flat, dofs) if sig is None else sig
+    col = _columns(flat, dofs)
+    nbody = int(flat.nbody)
+    parent, jadr, jnum, jtype = _I(flat, "body_parentid"), _I(flat, "body_jntadr"), _I(flat, "body_jntnum"), _I(flat, "jnt_type")
+    mocap = _I(flat, "body_mocapid") if "body_mocapid" in flat.arrays else np.full(nbody, -1)
+    att_of = np.full(nbody, -1)
+    for i, (body, carrier) in enumerate(att):
+        for x in (body, carrier):
+            if not 0 <= x < nbody:
+                raise ClearanceError(f"clearance: attachment {i}: body id {x} out of range ({nbody} bodies)")
+        if body in [a[0] for a in att[:i]]:
+            raise ClearanceError(f"clearance: attachment {i}: body {body} is attached twice")
+        if mocap[body] >= 0:
+            raise ClearanceError(f"clearance: attachment {i}: body {body} is a mocap body")
+        if body == 0 or parent[body] != 0 or jnum[body] != 1 or jtype[jadr[body]] != mjcf.JNT_FREE:
+            raise ClearanceError(f"clearance: attachment {i}: body {body} is not a child of the world with exactly one free joint")
+        for c in subtree(flat, body):
+            att_of[c] = i
+            for j in range(jadr[c], jadr[c] + jnum[c]) if c != body else ():
+                if jtype[j] == mjcf.JNT_FREE:
+                    raise ClearanceError(f"clearance: attachment {i}: {_joint_name(flat, j)} of body {c}, below the attached body {body}, is a free joint")
+                if j in col:
+                    raise ClearanceError(f"clearance: attachment {i}: {_joint_name(flat, j)} of body {c}, below the attached body {body}, is a controlled joint")
+            if c != body and mocap[c] >= 0:
+                raise ClearanceError(f"clearance: attachment {i}: body {c}, below the attached body {body}, is a mocap body")
+    for i, (body, carrier) in enumerate(att):
+        if att_of[carrier] >= 0:
+            raise ClearanceError(f"clearance: attachment {i}: carrier {carrier} is an attached body or below one")
+        if not sig[carrier]:
+            raise ClearanceError(f"clearance: attachment {i}: carrier {carrier} is not moved by the controlled dofs")
+    return att
+
+
+def _signatures(flat, dofs):
     col = _columns(flat, dofs)
     parent, jadr, jnum = _I(flat, "body_parentid"), _I(flat, "body_jntadr"), _I(flat, "body_jntnum")
     jtype = _I(flat, "jnt_type")
@@ -83,10 +167,21 @@ def moved_bodies(flat, dofs):
     return [int(b) for b in np.flatnonzero(signatures(flat, dofs))]
 
 
-def default_pairs(flat, dofs):
-    """The model's collision pair list restricted to candidate-dependent pairs (the two bodies' signatures differ), in the list's order; pairs the distance
-    query refuses (visual-only meshes, heightfields, plane against plane) are skipped.  An empty list is an error."""
-    sig = signatures(flat, dofs)
+def _held_rows(n):
+    return [[bool((r >> i) & 1) for i in range(n)] for r in range(1 << n)]
+
+
+def active_pairs(flat, dofs, pairs, attach, held):
+    """bool [P]: the pairs of a default list that an env with this held row evaluates -- those whose two bodies' signatures differ under it"""
+    sig, gbody = signatures(flat, dofs, attach, held), _I(flat, "geom_bodyid")
+    return np.array([sig[gbody[a]] != sig[gbody[b]] for a, b in np.asarray(pairs).reshape(-1, 2)], dtype=bool)
+
+
+def default_pairs(flat, dofs, attach=None):
+    """The model's collision pair list restricted to candidate-dependent pairs (the two bodies' signatures differ; with attach: under at least one held row),
+    in the list's order; pairs the distance query refuses (visual-only meshes, heightfields, plane against plane) are skipped.  An empty list is an error."""
+    att = _attachments(flat, dofs, attach)
+    sigs = [signatures(flat, dofs, att, row) for row in _held_rows(len(att))]
     gbody, gtype = _I(flat, "geom_bodyid"), _I(flat, "geom_type")
     carried = (mjcf.GEOM_PLANE, mjcf.GEOM_SPHERE, mjcf.GEOM_CAPSULE, mjcf.GEOM_ELLIPSOID, mjcf.GEOM_CYLINDER, mjcf.GEOM_BOX, mjcf.GEOM_MESH)
     ok = lambda g: gtype[g] in carried and not (gtype[g] == mjcf.GEOM_MESH and distance.mesh_verts(flat, g) is None)      # noqa: E731
@@ -95,7 +190,7 @@ def default_pairs(flat, dofs):
         for a, b in zip(_I(flat, "pair_geom1"), _I(flat, "pair_geom2")):
             if a == b or not ok(a) or not ok(b) or (gtype[a] == mjcf.GEOM_PLANE and gtype[b] == mjcf.GEOM_PLANE):
                 continue
-            if sig[gbody[a]] != sig[gbody[b]]:
+            if any(sig[gbody[a]] != sig[gbody[b]] for sig in sigs):
                 out.append((int(a), int(b)))
     if not out:
         raise ClearanceError("clearance: the default pair list is empty: no collision pair of the model depends on the controlled dofs")
@@ -125,22 +220,66 @@ def candidate_qpos(flat, qpos, dofs, q):
     return out
 
 
-def fk(flat, qpos, dofs, q, overrides=None, model32=None):
+def relative_poses(flat, qpos, attach, rel=None, overrides=None, model32=None, xpos=None, xquat=None):
+    """[n, 7]: position and unit wxyz quaternion of every attached body in its carrier's frame -- the rows of rel, the quaternion normalised, or (rel None)
+    from the env's current poses: xpos / xquat if given, else FK at qpos"""
+    att = [(int(b), int(c)) for b, c in np.asarray(attach).reshape(-1, 2)]
+    if rel is not None:
+        out = np.asarray(rel, dtype=np.float64).reshape(len(att), 7).copy()
+        out[:, 3:] /= np.linalg.norm(out[:, 3:], axis=1, keepdims=True)
+        return out
+    if xpos is None:
+        m = model32 if model32 is not None else _model32(flat, overrides)
+        xpos, xquat = mjcf.kinematics_np(m, np.asarray(qpos, dtype=np.float64).ravel())[:2]
+    out = np.zeros((len(att), 7))
+    for i, (body, carrier) in enumerate(att):
+        conj = np.asarray(xquat[carrier], dtype=np.float64) * [1, -1, -1, -1]
+        out[i, :3] = mjcf.quat2mat(xquat[carrier]).T @ (np.asarray(xpos[body], dtype=np.float64) - xpos[carrier])
+        out[i, 3:] = mjcf.quat_mul(conj, xquat[body])
+    return out
+
+
+def fk(flat, qpos, dofs, q, overrides=None, model32=None, attach=None, held=None, rel=None, now=None):
     """(xpos [nbody, 3], xquat [nbody, 4]) of every body with the controlled dofs at q and every other joint at qpos: mjcf.kinematics_np on the parameters
-    rounded to fp32.  overrides: {field: array} the env's own tables (ik.FIELDS); model32: the result of an earlier _model32 call, to save the rounding."""
-    signatures(flat, dofs)      # (the refusals)
+    rounded to fp32.  overrides: {field: array} the env's own tables (ik.FIELDS); model32: the result of an earlier _model32 call, to save the rounding.
+    attach / held / rel: the env's carried objects (the module's docstring); now: (xpos, xquat) the env's current poses, which rel=None is taken from and a
+    body that is not held keeps (None: FK at qpos)."""
+    sig = _signatures(flat, dofs)      # (the refusals)
+    att = _attachments(flat, dofs, attach, sig)
     m = model32 if model32 is not None else _model32(flat, overrides)
-    xpos, xquat = mjcf.kinematics_np(m, candidate_qpos(flat, qpos, dofs, q))[:2]
+    qc = candidate_qpos(flat, qpos, dofs, q)
+    xpos, xquat = mjcf.kinematics_np(m, qc)[:2]
+    if not att:
+        return xpos, xquat
+    r = relative_poses(flat, qpos, att, rel, model32=m, xpos=None if now is None else now[0], xquat=None if now is None else now[1])
+    jadr, qa = _I(flat, "body_jntadr"), _I(flat, "jnt_qposadr")
+    for (body, carrier), h, ri in zip(att, _held_row(att, held), r):
+        below = subtree(flat, body)
+        if h:
+            p = xpos[carrier] + mjcf.quat2mat(xquat[carrier]) @ ri[:3]
+            qb = mjcf.quat_normalize(mjcf.quat_mul(xquat[carrier], ri[3:]))
+            if len(below) > 1:      # the bodies below it: the walk from the composed pose, their joints at qpos
+                a = qa[jadr[body]]
+                qc[a:a + 3], qc[a + 3:a + 7] = p, qb
+                sp, sq = mjcf.kinematics_np(m, qc)[:2]
+                xpos[below], xquat[below] = sp[below], sq[below]
+            xpos[body], xquat[body] = p, qb
+        elif now is not None:
+            xpos[below], xquat[below] = np.asarray(now[0])[below], np.asarray(now[1])[below]
     return xpos, xquat
 
 
 def clearance(flat, qpos, dofs, q, pairs=None, distmax=1.0, tol=distance.DEFAULTS["tol"], max_iters=distance.DEFAULTS["max_iters"], params=None, overrides=None,
-              poses=None):
+              poses=None, attach=None, held=None, rel=None):
     """One candidate: -> (dist, pair, fromto [6], status).  pairs=None: default_pairs.  params: the env's geom arrays (distance.world_geoms); overrides: its FK
-    tables; poses: (xpos, xquat) to use instead of fk() -- the device tests hand the device's own poses in, to hold the distance layer apart from FK."""
-    p = default_pairs(flat, dofs) if pairs is None else distance.check_pairs(flat, pairs)
-    xpos, xquat = fk(flat, qpos, dofs, q, overrides) if poses is None else poses
+    tables; poses: (xpos, xquat) to use instead of fk() -- the device tests hand the device's own poses in, to hold the distance layer apart from FK.
+    attach / held / rel: the env's carried objects; with the default list the pairs the env does not evaluate (active_pairs) are left out of the minimum,
+    `pair` still indexing the whole list."""
+    p = default_pairs(flat, dofs, attach) if pairs is None else distance.check_pairs(flat, pairs)
+    xpos, xquat = fk(flat, qpos, dofs, q, overrides, attach=attach, held=held, rel=rel) if poses is None else poses
     d, ft, st = distance.geom_distance(flat, xpos, xquat, p, distmax, tol, max_iters, params)
+    if pairs is None and attach is not None and len(attach):
+        st = np.where(active_pairs(flat, dofs, p, attach, held), st, st | distance.FAR)      # (reads far: never attains the minimum)
     near = np.where((st & distance.FAR) == 0, d, np.inf)      # (a far pair reads distmax: it never attains the minimum)
     rd, rf, rk = distance.reduce_min(near, ft)
     if not rd < distmax:

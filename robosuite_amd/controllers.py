@@ -84,27 +84,29 @@ class BatchState:
         """Inverse kinematics of `site` over `dofs` for every env, away from the state (HipBatch.solve_ik): -> (q, err, iters, converged)."""
         return self.batch.solve_ik(site, dofs, pos, quat=quat, q_init=q_init, **opts)
 
-    def config_fk(self, dofs, q):
+    def config_fk(self, dofs, q, attach=None, held=None, rel=None):
         """Body poses at candidate joint vectors of `dofs`, away from the state (HipBatch.config_fk): -> (xpos, xquat).  Valid between step1 and step2."""
-        return self.batch.config_fk(dofs, q)
+        return self.batch.config_fk(dofs, q, attach=attach, held=held, rel=rel)
 
-    def config_pairs(self, dofs):
+    def config_pairs(self, dofs, attach=None):
         """The default pair list of config_clearance for `dofs` (HipBatch.config_pairs): int32 [P, 2] model geom ids."""
-        return self.batch.config_pairs(dofs)
+        return self.batch.config_pairs(dofs, attach=attach)
 
     def config_clearance(self, dofs, q, pairs=None, distmax=1.0, **opts):
         """The smallest distance over `pairs` at candidate joint vectors of `dofs`, away from the state (HipBatch.config_clearance): -> (dist, pair, fromto,
-        status).  Unmoved bodies are at the poses as they stand: valid between step1 and step2, like the other views."""
+        status).  Unmoved bodies are at the poses as they stand: valid between step1 and step2, like the other views.  opts: fromto, tol, max_iters, chunks, and the
+        carried objects attach / held / rel (HipBatch._attach), handed through as they are."""
         return self.batch.config_clearance(dofs, q, pairs=pairs, distmax=distmax, **opts)
 
     def config_sweep(self, dofs, q0, q1, pairs=None, distmax=1.0, **opts):
         """Is the motion from q0 to q1 of `dofs` free?  A certified check away from the state (HipBatch.config_sweep): -> (status, t, dist, t_min, pair, fromto,
-        steps).  Valid between step1 and step2."""
+        steps).  Valid between step1 and step2.  opts: margin, slack, max_steps, fromto, tol, max_iters, and the carried objects attach / held / rel
+        (HipBatch._attach), handed through as they are."""
         return self.batch.config_sweep(dofs, q0, q1, pairs=pairs, distmax=distmax, **opts)
 
-    def config_motion_bound(self, dofs, q0, q1, pairs=None):
+    def config_motion_bound(self, dofs, q0, q1, pairs=None, attach=None, held=None, rel=None):
         """The motion bound L config_sweep uses for these segments (HipBatch.config_motion_bound)."""
-        return self.batch.config_motion_bound(dofs, q0, q1, pairs=pairs)
+        return self.batch.config_motion_bound(dofs, q0, q1, pairs=pairs, attach=attach, held=held, rel=rel)
 
     def body_dofs(self, body: int):
         """bool [nv]: the dofs that move `body` (its own joints and those of its ancestors)."""

@@ -149,7 +149,7 @@ struct rsim_model {
 enum { TIER_NONE, TIER_FUSED, TIER_LIST };   // rsim_batch.tier
 
 // configuration clearance (rsim_clear.hip): what the batch keeps per dof list -- the body table and the slot of every body on the device, and the default pair list
-struct ClearTab { int *d_tab, *d_slot; int nel, nslot; std::vector<int> def_pairs, slot; };   // (slot: the host copy of d_slot, for the swept query's refusals)
+struct ClearTab { int *d_tab, *d_slot, *d_att; int nel, nslot, natt; std::vector<int> def_pairs, slot; };   // (slot: the host copy of d_slot, for the swept query's refusals)
 
 struct rsim_batch {
   rsim_model* m;
@@ -1127,7 +1127,7 @@ extern "C" void rsim_batch_free(rsim_batch* b) {
   if (b->d_ray_rf) hipFree(b->d_ray_rf);
   for (auto& kv : b->ik_chains) hipFree(kv.second.first);
   for (auto& kv : b->dist_tables) hipFree(kv.second);
-  for (auto& kv : b->clear_tabs) { hipFree(kv.second.d_tab); hipFree(kv.second.d_slot); }
+  for (auto& kv : b->clear_tabs) { hipFree(kv.second.d_tab); hipFree(kv.second.d_slot); if (kv.second.d_att) hipFree(kv.second.d_att); }
   if (b->d_clear_scr) hipFree(b->d_clear_scr);
   if (b->d_clear_part) hipFree(b->d_clear_part);
   if (b->db.mprc) hipFree(b->db.mprc);
@@ -2302,8 +2302,14 @@ struct ClearPlan {
   std::vector<unsigned> sig;   // [nbody] bit c set: controlled column c is on the body's path to the world
   std::vector<int> tab, slot;  // the body table; [nbody] slot of a moved body or -1
   int nel, nslot;
+  // attachments (include/rsim.h rsim_attach): [nbody] the signature with the body's attachment held (sig: not held), and the index of the attachment a body
+  // belongs to -- itself or above it --, -1 for none
+  int natt;
+  std::vector<unsigned> sig_held;
+  std::vector<int> att_of;
+  unsigned sig_at(int body, unsigned row) const { return att_of[body] >= 0 && ((row >> att_of[body]) & 1u) ? sig_held[body] : sig[body]; }
 };
-static int clear_plan(const rsim_model* m, const char* who, int ndof, const int32_t* dofs, ClearPlan* out) {
+static int clear_plan(const rsim_model* m, const char* who, int ndof, const int32_t* dofs, int natt, const int32_t* att, ClearPlan* out) {
   const int *parent = m->I("body_parentid"), *jadr = m->I("body_jntadr"), *jnum = m->I("body_jntnum"), *jtype = m->I("jnt_type"), *qadr = m->I("jnt_qposadr"),
             *dadr = m->I("jnt_dofadr"), *mocap = m->I("body_mocapid");
   if (!parent || !jadr || !jnum || !jtype || !qadr || !dadr) return fail("%s: the model lacks a joint / body table", who);
@@ -2350,10 +2356,56 @@ static int clear_plan(const rsim_model* m, const char* who, int ndof, const int3
       push(jtype[j], m->fo[FO_jnt_pos] + 3 * j, m->fo[FO_jnt_axis] + 3 * j, qadr[j], col_of_jnt[j], jtype[j] == 1 ? 0 : m->fo[FO_qpos0] + qadr[j], 0, 0);
     }
   }
+  // attached subtrees go BEHIND the ordinary moved bodies (a carrier may have the larger body id); they always own a slot
+  out->natt = 0;
+  out->sig_held = out->sig;
+  out->att_of.assign((size_t)m->nbody, -1);
+  if (natt == 0) return 0;
+  if (natt < 0 || natt > RSIM_ATTACH_MAX) return fail("%s: %d attachments outside 0..%d (RSIM_ATTACH_MAX)", who, natt, RSIM_ATTACH_MAX);
+  if (!att) return fail("%s: %d attachments with a NULL list", who, natt);
+  for (int i = 0; i < natt; i++) {
+    const int body = att[2 * i], car = att[2 * i + 1];
+    if (body < 0 || body >= m->nbody || car < 0 || car >= m->nbody)
+      return fail("%s: attachment %d: body id %d out of range (%d bodies)", who, i, body < 0 || body >= m->nbody ? body : car, m->nbody);
+    for (int k = 0; k < i; k++)
+      if (att[2 * k] == body) return fail("%s: attachment %d: body %d is attached twice", who, i, body);
+    if (mocap && mocap[body] >= 0) return fail("%s: attachment %d: body %d is a mocap body", who, i, body);
+    if (body == 0 || parent[body] != 0 || jnum[body] != 1 || jtype[jadr[body]] != 0)
+      return fail("%s: attachment %d: body %d is not a child of the world with exactly one free joint", who, i, body);
+    out->att_of[body] = i;
+    for (int c = body + 1; c < m->nbody; c++) {
+      if (out->att_of[parent[c]] != i) continue;
+      out->att_of[c] = i;
+      for (int j = jadr[c]; j < jadr[c] + jnum[c]; j++) {
+        if (jtype[j] == 0) return fail("%s: attachment %d: %s of body %d, below the attached body %d, is a free joint", who, i, ik_joint_name(m, j).c_str(), c, body);
+        if (col_of_jnt[j] >= 0) return fail("%s: attachment %d: %s of body %d, below the attached body %d, is a controlled joint", who, i, ik_joint_name(m, j).c_str(), c, body);
+      }
+      if (mocap && mocap[c] >= 0) return fail("%s: attachment %d: body %d, below the attached body %d, is a mocap body", who, i, c, body);
+    }
+  }
+  for (int i = 0; i < natt; i++) {
+    const int body = att[2 * i], car = att[2 * i + 1];
+    if (out->att_of[car] >= 0) return fail("%s: attachment %d: carrier %d is an attached body or below one", who, i, car);
+    if (!out->sig[car]) return fail("%s: attachment %d: carrier %d is not moved by the controlled dofs", who, i, car);
+    for (int c = body; c < m->nbody; c++) {
+      if (out->att_of[c] != i) continue;
+      out->sig_held[c] = out->sig[car];
+      out->slot[c] = out->nslot;
+      if (c == body) {
+        push(rsim_clear::CL_ATTACH, 0, 0, c, out->slot[car], i, out->nslot, car);
+      } else {
+        push(rsim_clear::CL_BODY, m->fo[FO_body_pos] + 3 * c, m->fo[FO_body_quat] + 4 * c, c, out->slot[parent[c]], i + 1, out->nslot, parent[c]);
+        for (int j = jadr[c]; j < jadr[c] + jnum[c]; j++)
+          push(jtype[j], m->fo[FO_jnt_pos] + 3 * j, m->fo[FO_jnt_axis] + 3 * j, qadr[j], -1, jtype[j] == 1 ? 0 : m->fo[FO_qpos0] + qadr[j], 0, 0);
+      }
+      out->nslot++;
+    }
+  }
+  out->natt = natt;
   return 0;
 }
-// the default pair list: the model's collision pairs whose two bodies have different dof signatures, in the collision list's order; pairs the distance query
-// refuses (visual-only meshes, heightfields, plane against plane) are skipped
+// the default pair list: the model's collision pairs whose two bodies have different dof signatures -- with attachments: under at least one held row --, in the
+// collision list's order; pairs the distance query refuses (visual-only meshes, heightfields, plane against plane) are skipped
 static int clear_default_pairs(const rsim_model* m, const char* who, const ClearPlan& plan, std::vector<int>* out) {
   const int *g1 = m->I("pair_geom1"), *g2 = m->I("pair_geom2"), *gt = m->I("geom_type"), *gb = m->I("geom_bodyid"), *gd = m->I("geom_dataid");
   out->clear();
@@ -2367,7 +2419,9 @@ static int clear_default_pairs(const rsim_model* m, const char* who, const Clear
     for (int p = 0; p < m->npair; p++) {
       const int a = g1[p], c = g2[p];
       if (a == c || !carried(a) || !carried(c) || (gt[a] == 0 && gt[c] == 0)) continue;
-      if (plan.sig[gb[a]] == plan.sig[gb[c]]) continue;   // the candidate cannot change this pair's relative pose
+      bool differ = false;
+      for (unsigned row = 0; row < (1u << plan.natt) && !differ; row++) differ = plan.sig_at(gb[a], row) != plan.sig_at(gb[c], row);
+      if (!differ) continue;   // the candidate cannot change this pair's relative pose
       out->push_back(a); out->push_back(c);
     }
   if (out->empty()) return fail("%s: the default pair list is empty: no collision pair of the model depends on the controlled dofs", who);
@@ -2377,30 +2431,66 @@ extern "C" int rsim_config_pairs(const rsim_model* m, int ndof, const int32_t* d
   if (!m) { fail("rsim_config_pairs: model is NULL"); return -1; }
   ClearPlan plan;
   std::vector<int> pairs;
-  if (clear_plan(m, "rsim_config_pairs", ndof, dof_ids, &plan) || clear_default_pairs(m, "rsim_config_pairs", plan, &pairs)) return -1;
+  if (clear_plan(m, "rsim_config_pairs", ndof, dof_ids, 0, nullptr, &plan) || clear_default_pairs(m, "rsim_config_pairs", plan, &pairs)) return -1;
   const int n = (int)(pairs.size() / 2);
   if (pairs_out && max_pairs > 0) memcpy(pairs_out, pairs.data(), sizeof(int32_t) * 2 * (size_t)std::min(n, max_pairs));
   return n;
 }
-static int clear_table(rsim_batch* b, const char* who, int ndof, const int32_t* dofs, const ClearTab** out) {
+extern "C" int rsim_config_pairs_attached(const rsim_model* m, int ndof, const int32_t* dof_ids, int max_pairs, int32_t* pairs_out, int nattach,
+                                          const int32_t* attach_bodies) {
+  const char* who = "rsim_config_pairs_attached";
+  if (!m) { fail("%s: model is NULL", who); return -1; }
+  ClearPlan plan;
+  std::vector<int> pairs;
+  if (clear_plan(m, who, ndof, dof_ids, nattach, attach_bodies, &plan) || clear_default_pairs(m, who, plan, &pairs)) return -1;
+  const int n = (int)(pairs.size() / 2);
+  if (pairs_out && max_pairs > 0) memcpy(pairs_out, pairs.data(), sizeof(int32_t) * 2 * (size_t)std::min(n, max_pairs));
+  return n;
+}
+// the table of a dof list and an attachment list, built by the first call that names them.  The key of a call without attachments is the dof list alone.
+static int clear_table(rsim_batch* b, const char* who, int ndof, const int32_t* dofs, const rsim_attach* att, const ClearTab** out) {
   if (ndof < 1 || ndof > RSIM_JNT_MAX) return fail("%s: ndof %d outside 1..%d", who, ndof, RSIM_JNT_MAX);
   if (!dofs) return fail("%s: dof_ids is NULL", who);
+  const int natt = att ? att->n : 0;
+  if (natt < 0 || natt > RSIM_ATTACH_MAX) return fail("%s: %d attachments outside 0..%d (RSIM_ATTACH_MAX)", who, natt, RSIM_ATTACH_MAX);
+  if (natt > 0 && !att->bodies) return fail("%s: %d attachments with a NULL list", who, natt);
   std::vector<int> key(dofs, dofs + ndof);
+  if (natt > 0) {
+    key.push_back(-1);   // (no dof id is negative)
+    key.insert(key.end(), att->bodies, att->bodies + 2 * natt);
+  }
   auto it = b->clear_tabs.find(key);
   if (it == b->clear_tabs.end()) {
     ClearPlan plan;
-    if (clear_plan(b->m, who, ndof, dofs, &plan)) return 1;
+    if (clear_plan(b->m, who, ndof, dofs, natt, natt > 0 ? att->bodies : nullptr, &plan)) return 1;
     ClearTab t;
-    t.d_tab = t.d_slot = nullptr; t.nel = plan.nel; t.nslot = plan.nslot; t.slot = plan.slot;
+    t.d_tab = t.d_slot = t.d_att = nullptr; t.nel = plan.nel; t.nslot = plan.nslot; t.slot = plan.slot; t.natt = plan.natt;
+    std::vector<int> h;   // what the pair loop's skip rule reads: [nbody] both signatures in one word, [nbody] the attachment a body belongs to
+    if (plan.natt > 0) {
+      h.resize(2 * (size_t)b->m->nbody);
+      for (int i = 0; i < b->m->nbody; i++) {
+        h[i] = (int)((plan.sig[i] & 0xffffu) | (plan.sig_held[i] << 16));
+        h[(size_t)b->m->nbody + i] = plan.att_of[i];
+      }
+    }
     if (clear_default_pairs(b->m, who, plan, &t.def_pairs)) t.def_pairs.clear();   // (an error only for a call that asks for the default list)
-    if (dalloc(&t.d_tab, plan.tab.size()) || dalloc(&t.d_slot, plan.slot.size())) return 1;
-    HIPCHK(hipMemcpy(t.d_tab, plan.tab.data(), plan.tab.size() * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(t.d_slot, plan.slot.data(), plan.slot.size() * sizeof(int), hipMemcpyHostToDevice));
+    auto up = [](int** d, const std::vector<int>& v) -> int {
+      if (v.empty()) return 0;
+      if (dalloc(d, v.size())) return 1;
+      HIPCHK(hipMemcpy(*d, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice));
+      return 0;
+    };
+    if (up(&t.d_tab, plan.tab) || up(&t.d_slot, plan.slot) || up(&t.d_att, h)) {   // (the error is named): a table that is not kept owns nothing
+      for (int* d : {t.d_tab, t.d_slot, t.d_att})
+        if (d) (void)hipFree(d);
+      return 1;
+    }
     it = b->clear_tabs.emplace(key, t).first;
   }
   *out = &it->second;
   return 0;
 }
+extern "C" int rsim_config_tables(const rsim_batch* b) { return b ? (int)b->clear_tabs.size() : 0; }
 // the pair list of a clearance / sweep call, in two steps because a call's own checks come between them: the argument as given ...
 static int pairs_check(const char* who, int npair, const int32_t* pairs) {
   if (npair < 0 || (npair > 0 && !pairs) || (npair == 0 && pairs)) return fail("%s: npair %d with pairs %s (a list of npair >= 1 pairs, or NULL and 0 for the default list)", who, npair, pairs ? "given" : "NULL");
@@ -2424,34 +2514,46 @@ static int clear_grow(rsim_batch* b, float** p, size_t* have, size_t want) {
   *have = want;
   return 0;
 }
-static int clear_args(rsim_batch* b, const char* who, int ndof, const int32_t* dof_ids, int k, const float* q_dev, DClear* a, const ClearTab** tab) {
+static int clear_args(rsim_batch* b, const char* who, int ndof, const int32_t* dof_ids, int k, const float* q_dev, const rsim_attach* att, DClear* a,
+                      const ClearTab** tab) {
   if (k < 1) return fail("%s: k %d < 1", who, k);
   if (!q_dev) return fail("%s: q_dev is NULL", who);
   if ((long long)k * b->B > (long long)65535 * RSIM_CLEAR_LANES || (long long)k * b->B * b->m->nbody > 0x7fffffffLL / 4)
     return fail("%s: %d candidates per env x %d envs is more than one call carries", who, k, b->B);
   if (join_groups(b)) return 1;
   HIPCHK(hipSetDevice(b->device));
-  if (clear_table(b, who, ndof, dof_ids, tab)) return 1;
+  if (clear_table(b, who, ndof, dof_ids, att, tab)) return 1;
   const rsim_model* m = b->m;
   memset(a, 0, sizeof(*a));
   a->B = b->B; a->K = k; a->n = ndof; a->NC = b->B * k; a->nbody = m->nbody; a->nq = m->nq; a->fstride = b->dm.fstride;
   a->nel = (*tab)->nel; a->nslot = (*tab)->nslot; a->tab = (*tab)->d_tab; a->slot_of_body = (*tab)->d_slot;
   a->ft = b->d_ft; a->qpos = b->db.qpos; a->xpos = b->db.xpos; a->xquat = b->db.xquat; a->q = q_dev;
+  a->natt = (*tab)->natt;
+  if (a->natt > 0) {   // (body_sig is set by the entries that use the default pair list: an explicit list is not skipped in)
+    a->held = att->held_dev; a->rel = att->rel_dev; a->body_att = (*tab)->d_att + m->nbody;
+  }
   return 0;
 }
-extern "C" int rsim_config_fk(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, float* xpos_dev, float* xquat_dev) {
-  if (!b) return fail("rsim_config_fk: batch is NULL");
-  if (!xpos_dev || !xquat_dev) return fail("rsim_config_fk: %s is NULL", !xpos_dev ? "xpos_dev" : "xquat_dev");
+static int config_fk(const char* who, rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, float* xpos_dev, float* xquat_dev,
+                     const rsim_attach* att) {
+  if (!b) return fail("%s: batch is NULL", who);
+  if (!xpos_dev || !xquat_dev) return fail("%s: %s is NULL", who, !xpos_dev ? "xpos_dev" : "xquat_dev");
   DClear a;
   const ClearTab* tab;
-  if (clear_args(b, "rsim_config_fk", ndof, dof_ids, k, q_dev, &a, &tab)) return 1;
+  if (clear_args(b, who, ndof, dof_ids, k, q_dev, att, &a, &tab)) return 1;
   if (refresh_derived(b, RSIM_XPOS)) return 1;
   a.xpos_out = xpos_dev; a.xquat_out = xquat_dev;
-  return launched("rsim_config_fk", rsim_launch_clear_fk(&a, b->stream));
+  return launched(who, rsim_launch_clear_fk(&a, b->stream));
 }
-extern "C" int rsim_config_clearance(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, int npair, const int32_t* pairs, float distmax,
-                                     const rsim_clear_opts* opts, float* dist_dev, int32_t* pair_dev, float* fromto_dev, int32_t* status_dev) {
-  const char* who = "rsim_config_clearance";
+extern "C" int rsim_config_fk(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, float* xpos_dev, float* xquat_dev) {
+  return config_fk("rsim_config_fk", b, ndof, dof_ids, k, q_dev, xpos_dev, xquat_dev, nullptr);
+}
+extern "C" int rsim_config_fk_attached(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, float* xpos_dev, float* xquat_dev,
+                                       const rsim_attach* att) {
+  return config_fk(att && att->n ? "rsim_config_fk_attached" : "rsim_config_fk", b, ndof, dof_ids, k, q_dev, xpos_dev, xquat_dev, att);
+}
+static int config_clearance(const char* who, rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, int npair, const int32_t* pairs, float distmax,
+                            const rsim_clear_opts* opts, float* dist_dev, int32_t* pair_dev, float* fromto_dev, int32_t* status_dev, const rsim_attach* att) {
   if (!b) return fail("%s: batch is NULL", who);
   if (!dist_dev || !pair_dev) return fail("%s: %s is NULL", who, !dist_dev ? "dist_dev" : "pair_dev");
   if (!(distmax >= 0.f)) return fail("%s: distmax %g is not >= 0", who, (double)distmax);
@@ -2462,7 +2564,8 @@ extern "C" int rsim_config_clearance(rsim_batch* b, int ndof, const int32_t* dof
     return fail("%s: option out of range (tol %g, max_iters %d: 1..%d, chunks %d: >= 0)", who, (double)o.tol, o.max_iters, RSIM_DIST_MAX_ITERS, o.chunks);
   DClear a;
   const ClearTab* tab;
-  if (clear_args(b, who, ndof, dof_ids, k, q_dev, &a, &tab)) return 1;
+  if (clear_args(b, who, ndof, dof_ids, k, q_dev, att, &a, &tab)) return 1;
+  if (a.natt > 0 && !pairs) a.body_sig = tab->d_att;   // the default list: per env, only the pairs its held row makes candidate-dependent
   if (pairs_resolve(b, who, tab, &npair, &pairs, &a.pairs)) return 1;
   if (refresh_derived(b, RSIM_XPOS) || ray_scene(b)) return 1;
   const rsim_model* m = b->m;
@@ -2488,17 +2591,28 @@ extern "C" int rsim_config_clearance(rsim_batch* b, int ndof, const int32_t* dof
   if (!e) e = rsim_launch_clear_dist(&a, b->stream);
   return launched(who, e);
 }
+extern "C" int rsim_config_clearance(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, int npair, const int32_t* pairs, float distmax,
+                                     const rsim_clear_opts* opts, float* dist_dev, int32_t* pair_dev, float* fromto_dev, int32_t* status_dev) {
+  return config_clearance("rsim_config_clearance", b, ndof, dof_ids, k, q_dev, npair, pairs, distmax, opts, dist_dev, pair_dev, fromto_dev, status_dev, nullptr);
+}
+extern "C" int rsim_config_clearance_attached(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, int npair, const int32_t* pairs,
+                                              float distmax, const rsim_clear_opts* opts, float* dist_dev, int32_t* pair_dev, float* fromto_dev,
+                                              int32_t* status_dev, const rsim_attach* att) {
+  return config_clearance(att && att->n ? "rsim_config_clearance_attached" : "rsim_config_clearance", b, ndof, dof_ids, k, q_dev, npair, pairs, distmax, opts,
+                          dist_dev, pair_dev, fromto_dev, status_dev, att);
+}
 
 // ---- swept clearance (rsim_sweep.hip, include/rsim.h rsim_config_sweep / rsim_config_motion_bound) -----------------------------------------------------------
 // A segment is a candidate with two ends: the body table, the pair table, the scratch and the stale-pose refresh are the clearance query's (clear_args above).
 static int sweep_args(rsim_batch* b, const char* who, int ndof, const int32_t* dof_ids, int k, const float* q0_dev, const float* q1_dev, int npair, const int32_t* pairs,
-                      DSweep* a) {
+                      const rsim_attach* att, DSweep* a) {
   if (!b) return fail("%s: batch is NULL", who);
   if (!q0_dev || !q1_dev) return fail("%s: %s is NULL", who, !q0_dev ? "q0_dev" : "q1_dev");
   if (pairs_check(who, npair, pairs)) return 1;
   memset(a, 0, sizeof(*a));
   const ClearTab* tab;
-  if (clear_args(b, who, ndof, dof_ids, k, q0_dev, &a->c, &tab)) return 1;
+  if (clear_args(b, who, ndof, dof_ids, k, q0_dev, att, &a->c, &tab)) return 1;
+  if (a->c.natt > 0 && !pairs) a->c.body_sig = tab->d_att;
   if (pairs_resolve(b, who, tab, &npair, &pairs, &a->c.pairs)) return 1;
   const rsim_model* m = b->m;
   const int *gt = m->I("geom_type"), *gb = m->I("geom_bodyid");
@@ -2518,19 +2632,26 @@ static int sweep_args(rsim_batch* b, const char* who, int ndof, const int32_t* d
   a->q1 = q1_dev;
   return 0;
 }
-extern "C" int rsim_config_motion_bound(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q0_dev, const float* q1_dev, int npair, const int32_t* pairs,
-                                        float* bound_dev) {
-  const char* who = "rsim_config_motion_bound";
+static int config_motion_bound(const char* who, rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q0_dev, const float* q1_dev, int npair,
+                               const int32_t* pairs, float* bound_dev, const rsim_attach* att) {
   if (!bound_dev) return fail("%s: bound_dev is NULL", who);
   DSweep a;
-  if (sweep_args(b, who, ndof, dof_ids, k, q0_dev, q1_dev, npair, pairs, &a)) return 1;
+  if (sweep_args(b, who, ndof, dof_ids, k, q0_dev, q1_dev, npair, pairs, att, &a)) return 1;
   a.bound = bound_dev;
   return launched(who, rsim_launch_sweep(&a, b->stream));
 }
-extern "C" int rsim_config_sweep(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q0_dev, const float* q1_dev, int npair, const int32_t* pairs,
-                                 float distmax, const rsim_sweep_opts* opts, int32_t* status_dev, float* t_dev, float* dist_dev, float* tmin_dev, int32_t* pair_dev,
-                                 float* fromto_dev, int32_t* steps_dev) {
-  const char* who = "rsim_config_sweep";
+extern "C" int rsim_config_motion_bound(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q0_dev, const float* q1_dev, int npair, const int32_t* pairs,
+                                        float* bound_dev) {
+  return config_motion_bound("rsim_config_motion_bound", b, ndof, dof_ids, k, q0_dev, q1_dev, npair, pairs, bound_dev, nullptr);
+}
+extern "C" int rsim_config_motion_bound_attached(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q0_dev, const float* q1_dev, int npair,
+                                                 const int32_t* pairs, float* bound_dev, const rsim_attach* att) {
+  return config_motion_bound(att && att->n ? "rsim_config_motion_bound_attached" : "rsim_config_motion_bound", b, ndof, dof_ids, k, q0_dev, q1_dev, npair, pairs,
+                             bound_dev, att);
+}
+static int config_sweep(const char* who, rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q0_dev, const float* q1_dev, int npair, const int32_t* pairs,
+                        float distmax, const rsim_sweep_opts* opts, int32_t* status_dev, float* t_dev, float* dist_dev, float* tmin_dev, int32_t* pair_dev,
+                        float* fromto_dev, int32_t* steps_dev, const rsim_attach* att) {
   if (!status_dev || !t_dev || !dist_dev || !tmin_dev || !pair_dev)
     return fail("%s: %s is NULL", who, !status_dev ? "status_dev" : !t_dev ? "t_dev" : !dist_dev ? "dist_dev" : !tmin_dev ? "tmin_dev" : "pair_dev");
   const rsim_sweep_opts def = {1e-6f, 64, 0.f, 1e-3f, 256};
@@ -2542,11 +2663,23 @@ extern "C" int rsim_config_sweep(rsim_batch* b, int ndof, const int32_t* dof_ids
   if (o.max_steps < 1 || o.max_steps > RSIM_SWEEP_MAX_STEPS) return fail("%s: max_steps %d outside 1..%d", who, o.max_steps, RSIM_SWEEP_MAX_STEPS);
   if (!(distmax > o.margin + o.slack)) return fail("%s: distmax %g is not above margin + slack = %g: no sample could pass", who, (double)distmax, (double)(o.margin + o.slack));
   DSweep a;
-  if (sweep_args(b, who, ndof, dof_ids, k, q0_dev, q1_dev, npair, pairs, &a)) return 1;
+  if (sweep_args(b, who, ndof, dof_ids, k, q0_dev, q1_dev, npair, pairs, att, &a)) return 1;
   a.c.distmax = distmax; a.c.tol = o.tol; a.c.max_iters = o.max_iters;
   a.margin = o.margin; a.slack = o.slack; a.max_steps = o.max_steps;
   a.c.status = status_dev; a.t = t_dev; a.c.dist = dist_dev; a.tmin = tmin_dev; a.c.pair = pair_dev; a.c.fromto = fromto_dev; a.steps = steps_dev;
   return launched(who, rsim_launch_sweep(&a, b->stream));
+}
+extern "C" int rsim_config_sweep(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q0_dev, const float* q1_dev, int npair, const int32_t* pairs,
+                                 float distmax, const rsim_sweep_opts* opts, int32_t* status_dev, float* t_dev, float* dist_dev, float* tmin_dev, int32_t* pair_dev,
+                                 float* fromto_dev, int32_t* steps_dev) {
+  return config_sweep("rsim_config_sweep", b, ndof, dof_ids, k, q0_dev, q1_dev, npair, pairs, distmax, opts, status_dev, t_dev, dist_dev, tmin_dev, pair_dev, fromto_dev,
+                      steps_dev, nullptr);
+}
+extern "C" int rsim_config_sweep_attached(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q0_dev, const float* q1_dev, int npair,
+                                          const int32_t* pairs, float distmax, const rsim_sweep_opts* opts, int32_t* status_dev, float* t_dev, float* dist_dev,
+                                          float* tmin_dev, int32_t* pair_dev, float* fromto_dev, int32_t* steps_dev, const rsim_attach* att) {
+  return config_sweep(att && att->n ? "rsim_config_sweep_attached" : "rsim_config_sweep", b, ndof, dof_ids, k, q0_dev, q1_dev, npair, pairs, distmax, opts, status_dev,
+                      t_dev, dist_dev, tmin_dev, pair_dev, fromto_dev, steps_dev, att);
 }
 
 // mj_fullM (controllers/parts/controller.py:226-227: `mujoco.mj_fullM(model, mass_matrix, data.qM)`): the dense joint-space inertia of one env

@@ -35,6 +35,11 @@ struct DClear {
   int* pair;                      // [B][K]
   float* fromto;                  // [B][K][6] or null
   int* status;                    // [B][K] or null
+  // attachments (include/rsim.h rsim_attach; rsim_clear_core.h Att): natt == 0 is a call without them, which runs the kernels' plain instantiation
+  int natt;
+  const unsigned char* held;      // [B][natt] or null: every attachment is held in every env
+  const float* rel;               // [B][natt][7] or null: from the env's current poses
+  const int *body_sig, *body_att; // [nbody] each; body_sig null: no pair is skipped (an explicit pair list)
 };
 
 extern "C" int rsim_launch_clear_fk(const DClear* a, hipStream_t stream);

@@ -14,6 +14,9 @@
 //                 as distmax, so a pair that cannot beat it leaves at the far exit.  One chunk writes the results; several write partial results,
 //   k_clear_min   which a last small pass reduces in chunk order, a strictly smaller distance replacing the minimum: the lowest pair index wins ties.  No atomics.
 // Every loop is bounded by a table length, max_iters or a vertex count.  No LDS, no barrier.
+// A call with attachments (rsim_attach) runs k_clear_fk_att / k_clear_dist_att: the same bodies with rsim_clear_core.h's ATT branches compiled in -- the walk of
+// the attached subtrees and the per-lane skip of the pairs the lane's env does not evaluate.  Same grids, same scratch layout; k_clear_min serves both.  The
+// kernels without the suffix are the instantiation with those branches compiled away: what a call without attachments ran before there were any.
 #include <hip/hip_runtime.h>
 #include "../../include/rsim.h"
 #include "rsim_clear.h"
@@ -39,25 +42,31 @@ __device__ __forceinline__ PoseStore scratch(const DClear& a, int c) {
   s.pe = s.qe = 7 * nc; s.ps = s.qs = nc; s.by_body = 0;
   return s;
 }
-}  // namespace
+// the lane's env's view of the attachments (rsim_clear_core.h att_of_env)
+__device__ __forceinline__ Att attachments(const DClear& a, int c) { return att_of_env(a.natt, a.held, a.rel, a.body_sig, a.body_att, c / a.K); }
 
-__global__ __launch_bounds__(RSIM_CLEAR_LANES) void k_clear_fk(DClear a) {
+template <bool ATT>
+__device__ __forceinline__ void clear_fk(const DClear& a) {
   const int c = (int)blockIdx.x * RSIM_CLEAR_LANES + (int)threadIdx.x;
   if (c >= a.NC) return;   // (the loops below have the same trip count in every lane that stays)
   const Cand cd = candidate(a, c);
+  const CandQ qv = {cd.q};
+  Att at = {0u, nullptr, nullptr, nullptr};
+  if (ATT) at = attachments(a, c);
   if (a.xpos_out) {
     PoseStore s;
     s.pos = a.xpos_out + (size_t)c * a.nbody * 3; s.quat = a.xquat_out + (size_t)c * a.nbody * 4;
     s.pe = 3; s.ps = 1; s.qe = 4; s.qs = 1; s.by_body = 1;
     for (int b = 0; b < a.nbody; b++)
       if (__builtin_amdgcn_readfirstlane(a.slot_of_body[b]) < 0) store_pose(s, b, env_pose(cd, b));   // bit for bit the env's pose
-    fk_walk(a.tab, a.nel, cd, s);
+    fk_walk<ATT>(a.tab, a.nel, cd, s, qv, at);
   } else {
-    fk_walk(a.tab, a.nel, cd, scratch(a, c));
+    fk_walk<ATT>(a.tab, a.nel, cd, scratch(a, c), qv, at);
   }
 }
 
-__global__ __launch_bounds__(RSIM_CLEAR_LANES) void k_clear_dist(DClear a) {
+template <bool ATT>
+__device__ __forceinline__ void clear_dist(const DClear& a) {
   const int chunk = (int)blockIdx.x;
   const int c = (int)blockIdx.y * RSIM_CLEAR_LANES + (int)threadIdx.x;
   if (c >= a.NC) return;
@@ -66,7 +75,9 @@ __global__ __launch_bounds__(RSIM_CLEAR_LANES) void k_clear_dist(DClear a) {
   Scene<DRayGeom> sc;
   sc.geom = a.geom; sc.pairs = a.pairs; sc.rec = RSIM_DIST_REC; sc.slot_of_body = a.slot_of_body; sc.mesh_vert = a.mesh_vert;
   sc.fo_size = a.fo_size; sc.fo_pos = a.fo_pos; sc.fo_quat = a.fo_quat;
-  const Best r = clear_pairs(sc, p0, p1, candidate(a, c), scratch(a, c), a.distmax, a.tol, a.max_iters);
+  Att at = {0u, nullptr, nullptr, nullptr};
+  if (ATT) at = attachments(a, c);
+  const Best r = clear_pairs<ATT>(sc, p0, p1, candidate(a, c), scratch(a, c), a.distmax, a.tol, a.max_iters, at);
   if (a.chunks > 1) {
     const size_t nc = (size_t)a.NC;
     float* w = a.part + (size_t)chunk * RSIM_CLEAR_PART * nc + c;
@@ -81,6 +92,13 @@ __global__ __launch_bounds__(RSIM_CLEAR_LANES) void k_clear_dist(DClear a) {
     f[0] = r.p1.x; f[1] = r.p1.y; f[2] = r.p1.z; f[3] = r.p2.x; f[4] = r.p2.y; f[5] = r.p2.z;
   }
 }
+
+}  // namespace
+
+__global__ __launch_bounds__(RSIM_CLEAR_LANES) void k_clear_fk(DClear a) { clear_fk<false>(a); }
+__global__ __launch_bounds__(RSIM_CLEAR_LANES) void k_clear_fk_att(DClear a) { clear_fk<true>(a); }
+__global__ __launch_bounds__(RSIM_CLEAR_LANES) void k_clear_dist(DClear a) { clear_dist<false>(a); }
+__global__ __launch_bounds__(RSIM_CLEAR_LANES) void k_clear_dist_att(DClear a) { clear_dist<true>(a); }
 
 __global__ __launch_bounds__(RSIM_CLEAR_LANES) void k_clear_min(DClear a) {
   const int c = (int)blockIdx.x * RSIM_CLEAR_LANES + (int)threadIdx.x;
@@ -105,14 +123,14 @@ __global__ __launch_bounds__(RSIM_CLEAR_LANES) void k_clear_min(DClear a) {
 
 extern "C" int rsim_launch_clear_fk(const DClear* a, hipStream_t stream) {
   if (a->NC <= 0 || a->nel <= 0) return 0;
-  hipLaunchKernelGGL(k_clear_fk, dim3((a->NC + RSIM_CLEAR_LANES - 1) / RSIM_CLEAR_LANES), dim3(RSIM_CLEAR_LANES), 0, stream, *a);
+  hipLaunchKernelGGL(a->natt > 0 ? k_clear_fk_att : k_clear_fk, dim3((a->NC + RSIM_CLEAR_LANES - 1) / RSIM_CLEAR_LANES), dim3(RSIM_CLEAR_LANES), 0, stream, *a);
   return (int)hipGetLastError();
 }
 
 extern "C" int rsim_launch_clear_dist(const DClear* a, hipStream_t stream) {
   if (a->NC <= 0 || a->npair <= 0 || a->chunks <= 0) return 0;
   const int waves = (a->NC + RSIM_CLEAR_LANES - 1) / RSIM_CLEAR_LANES;
-  hipLaunchKernelGGL(k_clear_dist, dim3(a->chunks, waves), dim3(RSIM_CLEAR_LANES), 0, stream, *a);
+  hipLaunchKernelGGL(a->natt > 0 ? k_clear_dist_att : k_clear_dist, dim3(a->chunks, waves), dim3(RSIM_CLEAR_LANES), 0, stream, *a);
   int e = (int)hipGetLastError();
   if (e || a->chunks == 1) return e;
   hipLaunchKernelGGL(k_clear_min, dim3(waves), dim3(RSIM_CLEAR_LANES), 0, stream, *a);

@@ -10,6 +10,8 @@
 //             pair list), then the loop of samples -- FK at q(t) into the scratch, the whole pair list with the lane's running minimum as distmax, the step.
 //             A wavefront runs as long as its slowest lane: decided lanes are masked, the trip count max_steps is wave-uniform and the loop leaves early once
 //             every lane of the wavefront is decided.  Every inner loop is bounded by a table length, max_iters or a vertex count.
+//   k_sweep_att   the same body with the attachment branches of the cores compiled in (rsim_clear_core.h ATT): what a call with attachments runs.  k_sweep is
+//             the instantiation without them.
 // No LDS, no barrier, no atomics, no private array.
 #include <hip/hip_runtime.h>
 #include "../../include/rsim.h"
@@ -18,7 +20,9 @@
 
 using namespace rsim_sweep;
 
-__global__ __launch_bounds__(RSIM_CLEAR_LANES) void k_sweep(DSweep a) {
+namespace {
+template <bool ATT>
+__device__ __forceinline__ void sweep_body(const DSweep& a) {
   const DClear& d = a.c;
   const int c = (int)blockIdx.x * RSIM_CLEAR_LANES + (int)threadIdx.x;
   if (c >= d.NC) return;
@@ -38,7 +42,9 @@ __global__ __launch_bounds__(RSIM_CLEAR_LANES) void k_sweep(DSweep a) {
   sc.geom = d.geom; sc.pairs = d.pairs; sc.rec = RSIM_DIST_REC; sc.slot_of_body = d.slot_of_body; sc.mesh_vert = d.mesh_vert;
   sc.fo_size = d.fo_size; sc.fo_pos = d.fo_pos; sc.fo_quat = d.fo_quat;
 
-  const float L = motion_bound(d.tab, d.nel, sc, a.fo_rcenter, a.fo_rbound, d.npair, s, st);
+  Att at = {0u, nullptr, nullptr, nullptr};
+  if (ATT) at = att_of_env(d.natt, d.held, d.rel, d.body_sig, d.body_att, env);   // the env's held row, read once into a mask, and its rel rows
+  const float L = motion_bound<ATT>(d.tab, d.nel, sc, a.fo_rcenter, a.fo_rbound, d.npair, s, st, at);
   if (a.bound) { a.bound[c] = L; return; }
 
   Opts op;
@@ -47,10 +53,10 @@ __global__ __launch_bounds__(RSIM_CLEAR_LANES) void k_sweep(DSweep a) {
   float t = 0.f;
   bool done = false;
   for (int i = 0; i < a.max_steps; i++) {
-    if (!done) done = sweep_sample(d.tab, d.nel, sc, d.npair, s, st, op, L, t, o);
+    if (!done) done = sweep_sample<ATT>(d.tab, d.nel, sc, d.npair, s, st, op, L, t, o, at);
     if (__all(done)) break;
   }
-  a.c.status[c] = o.status; a.t[c] = o.t; a.tmin[c] = o.t_min;
+  d.status[c] = o.status; a.t[c] = o.t; a.tmin[c] = o.t_min;
   d.dist[c] = o.best.dist; d.pair[c] = o.best.pair;
   if (a.steps) a.steps[c] = o.steps;
   if (d.fromto) {
@@ -59,8 +65,13 @@ __global__ __launch_bounds__(RSIM_CLEAR_LANES) void k_sweep(DSweep a) {
   }
 }
 
+}  // namespace
+
+__global__ __launch_bounds__(RSIM_CLEAR_LANES) void k_sweep(DSweep a) { sweep_body<false>(a); }
+__global__ __launch_bounds__(RSIM_CLEAR_LANES) void k_sweep_att(DSweep a) { sweep_body<true>(a); }
+
 extern "C" int rsim_launch_sweep(const DSweep* a, hipStream_t stream) {
   if (a->c.NC <= 0 || a->c.nel <= 0 || a->c.npair <= 0) return 0;
-  hipLaunchKernelGGL(k_sweep, dim3((a->c.NC + RSIM_CLEAR_LANES - 1) / RSIM_CLEAR_LANES), dim3(RSIM_CLEAR_LANES), 0, stream, *a);
+  hipLaunchKernelGGL(a->c.natt > 0 ? k_sweep_att : k_sweep, dim3((a->c.NC + RSIM_CLEAR_LANES - 1) / RSIM_CLEAR_LANES), dim3(RSIM_CLEAR_LANES), 0, stream, *a);
   return (int)hipGetLastError();
 }

@@ -13,6 +13,9 @@
 //    env that overrides geom_size alone is still covered by the first).  A geom of a body that is not moved has speed 0.  The distance of two convex solids is
 //    1-Lipschitz in the displacement of either, so a pair's bound is the sum of its two geoms' and L the maximum over the list, times 1 + 2^-16 for the
 //    roundings of this very sum (some thirty fp32 operations, 2^-24 each).
+//  * ATTACHMENTS (rsim_clear_core.h): a held body has Omega = Omega(carrier) and V = V(carrier) + Omega(carrier) |p_rel| -- the FK step p = p_c + R_c p_rel
+//    with p_rel constant -- and its subtree follows by the rules above; one that is not held stands still, Omega = V = 0, and so does its subtree (its joints
+//    are held).  L is the maximum over the pairs the lane's env evaluates.  ATT = false compiles all of it away.
 //  * Omega and V of a slot live in the first two words of that slot's pose in the scratch until the first FK walk overwrites them: no array in registers.
 //  * the loop (sweep): sample c(t) = clear_pairs at the poses of q(t); c <= margin + slack: HIT; t == 1: FREE; else t <- min(1, t + (c - margin) / L), where a
 //    far sample reads c = distmax.  Between two samples t_i < t_j the clearance is at least c(t_i) - L (t - t_i) > margin up to the step's end, and past a step
@@ -45,14 +48,15 @@ RSIM_HD float norm3(V3 a) { return sqrtf(dot(a, a)); }
 
 // ---- the motion bound ---------------------------------------------------------------------------------------------------------------------------------
 // leaves (Omega, V) of every moved body in words 0 and 1 of its slot
-RSIM_HD void bound_walk(const int* tab, int nel, const Seg& s, const PoseStore& st) {
+template <bool ATT>
+RSIM_HD void bound_walk(const int* tab, int nel, const Seg& s, const PoseStore& st, const Att& at) {
   float om = 0.f, v = 0.f, lom = 0.f, lv = 0.f;
   int cur_slot = -1, last_slot = -1;
   const float* ft = s.env.ft;
   for (int e = 0; e <= nel; e++) {
     const int* el = tab + (size_t)RSIM_CLEAR_REC * (e < nel ? e : 0);
     const int kind = e < nel ? RSIM_CLEAR_U(el[CLE_KIND]) : CL_BODY;
-    if (kind == CL_BODY) {
+    if (kind == CL_BODY || (ATT && kind == CL_ATTACH)) {
       if (cur_slot >= 0) {
         float* w = st.pos + (size_t)cur_slot * st.pe;
         w[0] = om; w[st.ps] = v;
@@ -66,7 +70,15 @@ RSIM_HD void bound_walk(const int* tab, int nel, const Seg& s, const PoseStore& 
         else { const float* w = st.pos + (size_t)pslot * st.pe; pom = w[0]; pv = w[st.ps]; }
       }
       om = pom;
-      v = pv + pom * norm3(ld3(ft + RSIM_CLEAR_U(el[CLE_O1])));
+      if (ATT && kind == CL_ATTACH) {
+        const int i = RSIM_CLEAR_U(el[CLE_O3]);
+        const bool held = (at.held >> i) & 1u;
+        const float arm = norm3(attach_rel(at, i, s.env, RSIM_CLEAR_U(el[CLE_ID]), RSIM_CLEAR_U(el[CLE_PBODY])).p);
+        om = held ? pom : 0.f;
+        v = held ? pv + pom * arm : 0.f;   // (not held: at rest, and its subtree with it -- every joint below is held)
+      } else {
+        v = pv + pom * norm3(ld3(ft + RSIM_CLEAR_U(el[CLE_O1])));
+      }
       cur_slot = RSIM_CLEAR_U(el[CLE_SLOT]);
     } else {
       const int col = RSIM_CLEAR_U(el[CLE_COL]), qadr = RSIM_CLEAR_U(el[CLE_ID]);
@@ -82,6 +94,10 @@ RSIM_HD void bound_walk(const int* tab, int nel, const Seg& s, const PoseStore& 
       }
     }
   }
+}
+RSIM_HD void bound_walk(const int* tab, int nel, const Seg& s, const PoseStore& st) {
+  const Att none = {0u, nullptr, nullptr, nullptr};
+  bound_walk<false>(tab, nel, s, st, none);
 }
 
 // a radius about the geom's own origin that contains the solid: by type and size, and by the model's bounding sphere (rbound about rcenter); a plane has none
@@ -108,24 +124,32 @@ RSIM_HD float geom_speed(const Scene<GeomRec>& sc, int fo_rcenter, int fo_rbound
   return w[st.ps] + w[0] * (norm3(lp) + geom_radius(RSIM_CLEAR_U(s.type), size, rc, rb));
 }
 
-template <class GeomRec>
-RSIM_HD float motion_bound(const int* tab, int nel, const Scene<GeomRec>& sc, int fo_rcenter, int fo_rbound, int npair, const Seg& s, const PoseStore& st) {
-  bound_walk(tab, nel, s, st);
+template <bool ATT, class GeomRec>
+RSIM_HD float motion_bound(const int* tab, int nel, const Scene<GeomRec>& sc, int fo_rcenter, int fo_rbound, int npair, const Seg& s, const PoseStore& st, const Att& at) {
+  bound_walk<ATT>(tab, nel, s, st, at);
   float L = 0.f;
   for (int p = 0; p < npair; p++) {
     const int* rec = sc.pairs + (size_t)p * sc.rec;
-    L = fmaxf(L, geom_speed(sc, fo_rcenter, fo_rbound, RSIM_CLEAR_U(rec[0]), s.env.ft, st) + geom_speed(sc, fo_rcenter, fo_rbound, RSIM_CLEAR_U(rec[1]), s.env.ft, st));
+    const int g1 = RSIM_CLEAR_U(rec[0]), g2 = RSIM_CLEAR_U(rec[1]);
+    if (ATT && !pair_active(at, RSIM_CLEAR_U(sc.geom[g1].body), RSIM_CLEAR_U(sc.geom[g2].body))) continue;
+    L = fmaxf(L, geom_speed(sc, fo_rcenter, fo_rbound, g1, s.env.ft, st) + geom_speed(sc, fo_rcenter, fo_rbound, g2, s.env.ft, st));
   }
   return L * (1.f + 1.52587890625e-05f);
+}
+template <class GeomRec>
+RSIM_HD float motion_bound(const int* tab, int nel, const Scene<GeomRec>& sc, int fo_rcenter, int fo_rbound, int npair, const Seg& s, const PoseStore& st) {
+  const Att none = {0u, nullptr, nullptr, nullptr};
+  return motion_bound<false>(tab, nel, sc, fo_rcenter, fo_rbound, npair, s, st, none);
 }
 
 // ---- the advancement loop --------------------------------------------------------------------------------------------------------------------------------
 // One sample: FK at q(t) and the pair loop; folds it into o and decides.  Returns true when the segment is decided.
-template <class GeomRec>
-RSIM_HD bool sweep_sample(const int* tab, int nel, const Scene<GeomRec>& sc, int npair, const Seg& s, const PoseStore& st, const Opts& op, float L, float& t, Out& o) {
+template <bool ATT, class GeomRec>
+RSIM_HD bool sweep_sample(const int* tab, int nel, const Scene<GeomRec>& sc, int npair, const Seg& s, const PoseStore& st, const Opts& op, float L, float& t, Out& o,
+                          const Att& at) {
   const SegQ qv = {s.q0, s.q1, t};
-  fk_walk(tab, nel, s.env, st, qv);
-  const Best r = clear_pairs(sc, 0, npair, s.env, st, op.distmax, op.tol, op.max_iters);
+  fk_walk<ATT>(tab, nel, s.env, st, qv, at);
+  const Best r = clear_pairs<ATT>(sc, 0, npair, s.env, st, op.distmax, op.tol, op.max_iters, at);
   o.steps++;
   o.t = t;
   o.status |= r.status & DIST_CAP;
@@ -147,12 +171,17 @@ RSIM_HD Out sweep_begin(float distmax) {
 }
 
 // the whole segment, serially (the host's form; the kernel runs the same samples under a wave-uniform loop, rsim_sweep.hip)
-template <class GeomRec>
-RSIM_HD Out sweep(const int* tab, int nel, const Scene<GeomRec>& sc, int npair, const Seg& s, const PoseStore& st, const Opts& op, float L) {
+template <bool ATT, class GeomRec>
+RSIM_HD Out sweep(const int* tab, int nel, const Scene<GeomRec>& sc, int npair, const Seg& s, const PoseStore& st, const Opts& op, float L, const Att& at) {
   Out o = sweep_begin(op.distmax);
   float t = 0.f;
   for (int i = 0; i < op.max_steps; i++)
-    if (sweep_sample(tab, nel, sc, npair, s, st, op, L, t, o)) break;
+    if (sweep_sample<ATT>(tab, nel, sc, npair, s, st, op, L, t, o, at)) break;
   return o;
+}
+template <class GeomRec>
+RSIM_HD Out sweep(const int* tab, int nel, const Scene<GeomRec>& sc, int npair, const Seg& s, const PoseStore& st, const Opts& op, float L) {
+  const Att none = {0u, nullptr, nullptr, nullptr};
+  return sweep<false>(tab, nel, sc, npair, s, st, op, L, none);
 }
 }  // namespace rsim_sweep

@@ -16,8 +16,15 @@ a radius about the geom's origin that contains it; a geom of a body that is not 
 over the list of the sum of a pair's two bounds, times 1 + 2^-16 (the device's allowance for its fp32 roundings, kept here so that both state one bound).
 
 The loop: t = 0; sample c(t); c <= margin + slack: HIT; t == 1: FREE; else t <- min(1, t + (c - margin) / L), a far sample reading c = distmax; max_steps
-samples without a decision: UNDECIDED.  The motion is certified to have clearance > margin on [0, t).  NOT HANDLED: a grasped object does not move with the
-motion; free and ball joints as controlled dofs; interpolation other than linear in joint space."""
+samples without a decision: UNDECIDED.  The motion is certified to have clearance > margin on [0, t).
+
+Carried objects (clearance.py: attach, one env's held row, its rel rows).  A held body has Omega = Omega(carrier) and V = V(carrier) + Omega(carrier) |p_rel|,
+and its subtree follows by the rules above; one that is not held stands still.  L is the maximum over the pairs the env evaluates (clearance.active_pairs; an
+explicit list: all of them).  The certificate is unchanged: the held body's origin is p_c(t) + R_c(t) p_rel with p_rel constant, so it moves at most
+V(carrier) + Omega(carrier) |p_rel| per unit t and turns at most Omega(carrier) -- the body step's bound with p_rel in place of body_pos; and which pairs the
+env evaluates does not depend on t, so c(t) is L-Lipschitz as before.  A plane on an attached body is refused, as on any moved body.
+
+NOT HANDLED: free and ball joints as controlled dofs; interpolation other than linear in joint space; per-pair bounds."""
 from __future__ import annotations
 
 import numpy as np
@@ -56,9 +63,10 @@ def geom_radius(gtype, size, rcenter, rbound):
     return 0.0 if gtype == mjcf.GEOM_PLANE else max(r, float(np.linalg.norm(rcenter)) + float(rbound))
 
 
-def body_rates(flat, qpos, dofs, q0, q1, overrides=None):
+def body_rates(flat, qpos, dofs, q0, q1, overrides=None, attach=None, held=None, rel=None):
     """(Omega [nbody], V [nbody]) of the segment, on the FK tables rounded to fp32 (ik.rounded); zero for a body that is not moved"""
-    sig = clearance.signatures(flat, dofs)
+    sig = clearance._signatures(flat, dofs)
+    att = clearance._attachments(flat, dofs, attach, sig)
     col = clearance._columns(flat, dofs)
     t = ik.rounded(flat, overrides)
     I = clearance._I
@@ -86,12 +94,26 @@ def body_rates(flat, qpos, dofs, q0, q1, overrides=None):
                 if jtype[j] == mjcf.JNT_HINGE and c >= 0:
                     om[b] += abs(q1[c] - q0[c])
                 v[b] += om[b] * arm
+    if att:
+        r = clearance.relative_poses(flat, qpos, att, rel, overrides)
+        for (body, carrier), h, ri in zip(att, clearance._held_row(att, held), r):
+            if not h:
+                continue
+            om[body], v[body] = om[carrier], v[carrier] + om[carrier] * np.linalg.norm(ri[:3])
+            for b in clearance.subtree(flat, body)[1:]:      # (their joints are held: dx = 0, no |dq|)
+                p = parent[b]
+                om[b], v[b] = om[p], v[p] + om[p] * np.linalg.norm(t["body_pos"][b])
+                for j in range(jadr[b], jadr[b] + jnum[b]):
+                    if jtype[j] == mjcf.JNT_SLIDE:
+                        v[b] += np.linalg.norm(t["jnt_axis"][j]) * om[b] * abs(qpos[qa[j]] - t["qpos0"][qa[j]])
+                    else:
+                        v[b] += 2 * om[b] * np.linalg.norm(t["jnt_pos"][j])
     return om, v
 
 
-def _pairs(flat, dofs, pairs):
-    p = clearance.default_pairs(flat, dofs) if pairs is None else distance.check_pairs(flat, pairs)
-    sig = clearance.signatures(flat, dofs)
+def _pairs(flat, dofs, pairs, attach=None):
+    p = clearance.default_pairs(flat, dofs, attach) if pairs is None else distance.check_pairs(flat, pairs)
+    sig = clearance.signatures(flat, dofs, attach)      # (all held: an attached body counts as moved whatever the env's row)
     gtype, gbody = clearance._I(flat, "geom_type"), clearance._I(flat, "geom_bodyid")
     for k, pr in enumerate(p):
         for g in pr:
@@ -101,13 +123,13 @@ def _pairs(flat, dofs, pairs):
     return p
 
 
-def geom_speeds(flat, qpos, dofs, q0, q1, geoms, overrides=None, params=None):
+def geom_speeds(flat, qpos, dofs, q0, q1, geoms, overrides=None, params=None, attach=None, held=None, rel=None):
     """{geom id: bound on the speed of any of its points per unit t}; params: the env's own geom arrays (geom_size, geom_pos, geom_rbound, geom_rcenter)"""
-    om, v = body_rates(flat, qpos, dofs, q0, q1, overrides)
+    om, v = body_rates(flat, qpos, dofs, q0, q1, overrides, attach, held, rel)
     A = lambda name, w: np.asarray((params or {}).get(name, flat.arrays[name]), dtype=np.float64).astype(np.float32).astype(np.float64).reshape(-1, w)   # noqa: E731
     gsize, gpos, rc, rb = A("geom_size", 3), A("geom_pos", 3), A("geom_rcenter", 3), A("geom_rbound", 1)
     gtype, gbody = clearance._I(flat, "geom_type"), clearance._I(flat, "geom_bodyid")
-    sig = clearance.signatures(flat, dofs)
+    sig = clearance.signatures(flat, dofs, attach, held)
     out = {}
     for g in sorted(set(int(x) for x in geoms)):
         b = gbody[g]
@@ -115,26 +137,29 @@ def geom_speeds(flat, qpos, dofs, q0, q1, geoms, overrides=None, params=None):
     return out
 
 
-def motion_bound(flat, qpos, dofs, q0, q1, pairs=None, overrides=None, params=None):
-    """L of one segment: the distance of every listed pair changes by at most L |dt|"""
-    p = _pairs(flat, dofs, pairs)
-    s = geom_speeds(flat, qpos, dofs, q0, q1, p.ravel(), overrides, params)
-    return max(s[int(a)] + s[int(b)] for a, b in p) * INFLATE
+def motion_bound(flat, qpos, dofs, q0, q1, pairs=None, overrides=None, params=None, attach=None, held=None, rel=None):
+    """L of one segment: the distance of every pair the env evaluates changes by at most L |dt|"""
+    p = _pairs(flat, dofs, pairs, attach)
+    s = geom_speeds(flat, qpos, dofs, q0, q1, p.ravel(), overrides, params, attach, held, rel)
+    on = clearance.active_pairs(flat, dofs, p, attach, held) if pairs is None and attach is not None and len(attach) else np.ones(len(p), dtype=bool)
+    return max([s[int(a)] + s[int(b)] for (a, b), k in zip(p, on) if k], default=0.0) * INFLATE
 
 
 def sweep(flat, qpos, dofs, q0, q1, pairs=None, distmax=1.0, margin=DEFAULTS["margin"], slack=DEFAULTS["slack"], max_steps=DEFAULTS["max_steps"],
-          tol=distance.DEFAULTS["tol"], max_iters=distance.DEFAULTS["max_iters"], params=None, overrides=None):
+          tol=distance.DEFAULTS["tol"], max_iters=distance.DEFAULTS["max_iters"], params=None, overrides=None, attach=None, held=None, rel=None):
     """One segment: -> (status, t, dist, t_min, pair, fromto [6], steps); bit 8 of status (distance.CAP) is set if any sample's iteration was capped"""
     o = options(distmax, margin, slack, max_steps)
-    p = _pairs(flat, dofs, pairs)
+    p = _pairs(flat, dofs, pairs, attach)
     q0, q1 = np.asarray(q0, dtype=np.float64).ravel(), np.asarray(q1, dtype=np.float64).ravel()
-    L = motion_bound(flat, qpos, dofs, q0, q1, p, overrides, params)
+    L = motion_bound(flat, qpos, dofs, q0, q1, pairs, overrides, params, attach, held, rel)
     m32 = clearance._model32(flat, overrides)
     gparams = None if params is None else {k: v for k, v in params.items() if k in ("geom_size", "geom_pos", "geom_quat")}
     best, t_min, cap, t, steps = (o["distmax"], -1, np.zeros(6)), 0.0, 0, 0.0, 0
     while steps < o["max_steps"]:
         q = q0 + t * (q1 - q0)
-        d, k, ft, st = clearance.clearance(flat, qpos, dofs, q, p, o["distmax"], tol, max_iters, gparams, poses=clearance.fk(flat, qpos, dofs, q, model32=m32))
+        poses = clearance.fk(flat, qpos, dofs, q, model32=m32, attach=attach, held=held, rel=rel)
+        d, k, ft, st = clearance.clearance(flat, qpos, dofs, q, pairs if attach is not None and len(attach) else p, o["distmax"], tol, max_iters, gparams, poses=poses,
+                                           attach=attach, held=held)
         steps += 1
         cap |= st & distance.CAP
         if k >= 0 and d < best[0]:

@@ -227,49 +227,90 @@ class VecEnv:
             return second if arm == 1 else first + second
         raise ValueError(f"{who}: the controller description has no arm {arm!r}")
 
-    def config_fk(self, q, arm=0):
+    def _attach_ids(self, who, attach, arm):
+        """attach = [(body, carrier), ...], names or model body ids; carrier None: the body of the arm's `eef_site` -> [(body id, carrier id), ...] or None"""
+        from .backend import ctrl_desc
+
+        if attach is None:
+            return None
+        flat = self.env.model.flat
+        names = flat.names["body"]
+
+        def one(b):
+            if isinstance(b, str):
+                if b not in names:
+                    raise KeyError(f"no body named {b!r}")
+                return names.index(b)
+            return int(b)
+
+        out = []
+        for pr in attach:
+            if len(pr) != 2:
+                raise ValueError(f"{who}: an attachment is (body, carrier), got {pr!r}")
+            body, carrier = pr
+            if carrier is None:
+                d = ctrl_desc(self.env.cfg)
+                if arm not in (0, 1) or (arm == 1 and d.narm != 2):
+                    raise ValueError(f"{who}: carrier=None needs one arm's eef_site, got arm {arm!r}")
+                site = int(d.eef_site) if arm == 0 else int(d.eef_site2)
+                carrier = int(np.asarray(flat.arrays["site_bodyid"]).ravel()[site])
+            out.append((one(body), one(carrier)))
+        return out
+
+    def config_fk(self, q, arm=0, attach=None, held=None, rel=None):
         """Body poses at candidate arm joint vectors, away from the state: q [n_envs, K, n] (2-D for K = 1) device tensor of the arm's joint positions ->
         (xpos [n_envs, K, nbody, 3], xquat [n_envs, K, nbody, 4]) of all bodies (HipBatch.config_fk).  The dofs are the arm's `dof_idx` of the env's
-        controller description; arm=1: the second arm of a two-arm description, arm="both": the two concatenated."""
-        return self.env.batch.config_fk(self._arm_dofs("config_fk", arm), q)
+        controller description; arm=1: the second arm of a two-arm description, arm="both": the two concatenated.  attach / held / rel: carried objects, as
+        config_clearance."""
+        return self.env.batch.config_fk(self._arm_dofs("config_fk", arm), q, attach=self._attach_ids("config_fk", attach, arm), held=held, rel=rel)
 
-    def config_clearance(self, q, arm=0, pairs=None, distmax=1.0, **opts):
+    def config_clearance(self, q, arm=0, pairs=None, distmax=1.0, attach=None, held=None, rel=None, **opts):
         """Is this arm configuration free, and by how much?  q [n_envs, K, n] (2-D for K = 1) candidate joint positions of the arm -> (dist, pair, fromto,
         status) per candidate: the smallest distance over `pairs`, the index into the list of the pair that attains it, its nearest points and its status
         (HipBatch.config_clearance: the status codes, the convex-hull and overlap rules).  pairs: a list of (geom, geom), names or model geom ids; None: the
         model's collision pairs the arm's joints can change (HipBatch.config_pairs).  Every joint that is not the arm's -- fingers, objects, the other arm --
-        is held where it is, and A GRASPED OBJECT DOES NOT MOVE WITH THE CANDIDATE.  The simulation state is not touched.  arm: as config_fk.  With solve_ik:
+        is held where it is.  The simulation state is not touched.  arm: as config_fk.  With solve_ik:
 
             q, err, it, ok = env.solve_ik(pos, quat)
             d, pair, ft, st = env.config_clearance(q)
             free = ok & (d > margin)
+
+        A GRASPED OBJECT MOVES WITH THE CANDIDATE ONLY IF THE CALL SAYS SO: attach = [(body, carrier), ...], names or model body ids, carrier None meaning the
+        body of the arm's `eef_site`; held = bool tensor [n_envs] or [n_envs, n] (None: held in every env -- the caller decides what is grasped); rel =
+        [n_envs, n, 7] pose of the body in the carrier's frame (None: as it sits now).  Then the object rides on the carrier in the envs that hold it, drops out
+        against the fingers that hold it and comes in against the table, the bin and the other arm (HipBatch.config_clearance):
+
+            d, pair, ft, st = env.config_clearance(q, attach=[("cube_main", None)], held=grasped)
         """
         ids = None if pairs is None else self._geom_ids(pairs)
-        return self.env.batch.config_clearance(self._arm_dofs("config_clearance", arm), q, pairs=ids, distmax=distmax, **opts)
+        return self.env.batch.config_clearance(self._arm_dofs("config_clearance", arm), q, pairs=ids, distmax=distmax,
+                                               attach=self._attach_ids("config_clearance", attach, arm), held=held, rel=rel, **opts)
 
-    def config_sweep(self, q0, q1, arm=0, pairs=None, distmax=1.0, **opts):
+    def config_sweep(self, q0, q1, arm=0, pairs=None, distmax=1.0, attach=None, held=None, rel=None, **opts):
         """Is the arm motion from q0 to q1 free?  q0, q1 [n_envs, K, n] (2-D for K = 1) ends of K joint-space segments per env, interpolated linearly ->
         (status, t, dist, t_min, pair, fromto, steps) per segment (HipBatch.config_sweep: 0 FREE, 1 HIT, 2 UNDECIDED; the motion is certified to keep more
         than `margin` of clearance on [0, t)).  arm, pairs: as config_clearance; opts: margin, slack, max_steps, fromto, tol, max_iters.  Every joint that is
-        not the arm's is held where it is, and A GRASPED OBJECT DOES NOT MOVE WITH THE MOTION.  The simulation state is not touched.  One motion bound serves the
+        not the arm's is held where it is; a grasped object moves with the motion only if the call says so (attach / held / rel, as config_clearance: the
+        motion bound then covers the carried bodies).  The simulation state is not touched.  One motion bound serves the
         whole list: a listed pair that stays within margin + slack whatever the arm does (the Panda's link0 / link1 geoms, 1.0 mm apart) decides every segment
         at its first sample -- pass `pairs` without it."""
         ids = None if pairs is None else self._geom_ids(pairs)
-        return self.env.batch.config_sweep(self._arm_dofs("config_sweep", arm), q0, q1, pairs=ids, distmax=distmax, **opts)
+        return self.env.batch.config_sweep(self._arm_dofs("config_sweep", arm), q0, q1, pairs=ids, distmax=distmax,
+                                           attach=self._attach_ids("config_sweep", attach, arm), held=held, rel=rel, **opts)
 
-    def path_clearance(self, waypoints, arm=0, pairs=None, distmax=1.0, **opts):
+    def path_clearance(self, waypoints, arm=0, pairs=None, distmax=1.0, attach=None, held=None, rel=None, **opts):
         """Is this joint-space path free?  waypoints [n_envs, K, W, n]: K paths per env of W >= 2 arm joint vectors, joined by straight joint-space segments
         -> (free bool [n_envs, K], first_segment int64, t, dist float32, pair int32).  One config_sweep call over the K (W - 1) segments, reduced in torch: a
         path is free only if EVERY segment is FREE; otherwise first_segment is the first segment that is not (HIT or UNDECIDED) and t, dist, pair are that
         segment's (the path is certified up to parameter t of it).  A free path reads first_segment -1, t 1 and the smallest dist over its segments with that
-        segment's pair.  arm, pairs, opts: as config_sweep."""
+        segment's pair.  arm, pairs, attach, held, rel, opts: as config_sweep."""
         import torch
 
         if not (isinstance(waypoints, torch.Tensor) and waypoints.dim() == 4 and waypoints.shape[2] >= 2):
             raise ValueError(f"path_clearance: waypoints must be a tensor [n_envs, K, W, n] with W >= 2, got {tuple(getattr(waypoints, 'shape', ()))}")
         B, K, W, n = waypoints.shape
         q0, q1 = waypoints[:, :, :-1].reshape(B, K * (W - 1), n), waypoints[:, :, 1:].reshape(B, K * (W - 1), n)
-        st, t, dist, _, pair, _, _ = self.config_sweep(q0, q1, arm=arm, pairs=pairs, distmax=distmax, **dict(opts, fromto=False))
+        st, t, dist, _, pair, _, _ = self.config_sweep(q0, q1, arm=arm, pairs=pairs, distmax=distmax, attach=attach, held=held, rel=rel, **dict(opts, fromto=False))
         st, t, dist, pair = (x.reshape(B, K, W - 1) for x in (st, t, dist, pair))
         bad = (st & 3) != 0
         free = ~bad.any(dim=2)
