@@ -712,6 +712,48 @@ int rsim_config_motion_bound_attached(rsim_batch* b, int ndof, const int32_t* do
  * it exists so that "a batch that never names an attachment builds no new table" can be checked from outside (tests/test_attach.py); no result depends on it. */
 int rsim_config_tables(const rsim_batch* b);
 
+/* Clearance gradients and a collision cost: which way does a candidate move away from the scene?  (rsim_grad.hip; robosuite_amd/clearance.py clearance_grad /
+ * collision_cost is the fp64 host mirror; DESIGN.md 5.3 has the derivation.)
+ *   rsim_config_clearance_grad (_attached) is rsim_config_clearance (_attached) with one more output, grad_dev [B][k][ndof].  dist, pair, fromto and status are
+ *               bit for bit what that entry returns for the same arguments: the same kernels, the same chunking.  fromto_dev and status_dev are needed here (the
+ *               gradient is formed from them) and may not be NULL.
+ *   grad        for the pair that attains the minimum, with nearest points p1, p2 (fromto), distance d (dist, signed or not) and n = (p2 - p1) / d:
+ *                   dd/dq_c = n . (s2_c v_c(p2) - s1_c v_c(p1)),   v_c(p) = a_c x (p - anchor_c) for a hinge, a_c for a slide.
+ *               a_c and anchor_c are the world axis and anchor of controlled column c AT THE CANDIDATE, taken in the FK walk at the moment the joint is applied
+ *               (axis = R_cur a, anchor = p_cur + R_cur jnt_pos: several joints on one body are right), on the env's own float table.  s_i_c is bit c of the dof
+ *               signature of the pair's body i; a held carried body has its carrier's.  No derivative of the witness points enters.  A pair whose two bodies
+ *               share a signature needs no special case: its terms cancel.  Negative exact distances (plane, sphere, capsule) take the same formula.
+ *   zeros       grad is all zeros where pair < 0 (far), where status has RSIM_DIST_OVERLAP (distance 0, one common point, no direction) and where
+ *               |dist| < RSIM_GRAD_MIN_DIST (no usable direction in fp32).
+ *   limits      THE DIRECTION IS READ FROM fromto, so its accuracy falls as ulp(coordinate) / |dist| below about a millimetre; and the gradient is ONE-SIDED where
+ *               the witnesses are not unique (parallel faces) or the nearest pair ties: it is the derivative of the returned pair at the returned points.
+ *   rsim_config_collision_cost (_attached): a smooth cost over ALL near pairs, C1 where the nearest pair switches.  Every listed pair the env evaluates is queried
+ *               with distmax = d_safe (no running-minimum pruning).  A pair with d < d_safe adds 1/2 (d_safe - d)^2 to cost_dev [B][k] and -(d_safe - d) grad d,
+ *               under the zero rules above, to grad_dev [B][k][ndof]; an overlapping pair (RSIM_DIST_OVERLAP) adds 1/2 d_safe^2 and no gradient and is counted
+ *               in noverlap_dev.  nnear_dev counts the contributing pairs.  Either count may be NULL.  Pair lists (default, explicit), attachments, per-env
+ *               skipping and refusals are those of rsim_config_clearance (_attached); in addition d_safe <= 0 is refused by name.  With several pair chunks the
+ *               partial sums are added in chunk order, without atomics: a repeat call is bit-identical (another chunk count rounds differently).
+ * Pure queries, asynchronous on the batch's stream.  They run behind the unchanged clearance kernels (k_clear_fk, k_clear_dist, k_clear_min): k_clear_joints leaves
+ * axis and anchor of every controlled column in a store beside the pose scratch, k_clear_grad (_att) writes the gradient of each candidate's own result,
+ * k_clear_cost (_att) and k_clear_cost_sum the cost.  The signature table of a dof list and the joint store are built by the first call that asks: a batch that
+ * never asks allocates and launches nothing new (rsim_config_grad_tables, a diagnostic like rsim_config_tables, counts the signature tables).
+ * NOT HANDLED: a gradient term inside rsim_ik_site or the fused step; penetration depth and gradients for general convex overlaps; per-pair outputs (all near
+ * pairs with their own gradients); second derivatives; gradients of rsim_config_sweep; free or ball joints as controlled dofs. */
+#define RSIM_GRAD_MIN_DIST 1e-7f
+int rsim_config_clearance_grad(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, int npair, const int32_t* pairs, float distmax,
+                               const rsim_clear_opts* opts, float* dist_dev, int32_t* pair_dev, float* fromto_dev, int32_t* status_dev,
+                               float* grad_dev /* [B][k][ndof] */);
+int rsim_config_clearance_grad_attached(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, int npair, const int32_t* pairs, float distmax,
+                                        const rsim_clear_opts* opts, float* dist_dev, int32_t* pair_dev, float* fromto_dev, int32_t* status_dev, float* grad_dev,
+                                        const rsim_attach* att);
+int rsim_config_collision_cost(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, int npair, const int32_t* pairs, float d_safe,
+                               const rsim_clear_opts* opts, float* cost_dev /* [B][k] */, float* grad_dev /* [B][k][ndof] */,
+                               int32_t* nnear_dev /* [B][k] or NULL */, int32_t* noverlap_dev /* [B][k] or NULL */);
+int rsim_config_collision_cost_attached(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, int npair, const int32_t* pairs, float d_safe,
+                                        const rsim_clear_opts* opts, float* cost_dev, float* grad_dev, int32_t* nnear_dev, int32_t* noverlap_dev,
+                                        const rsim_attach* att);
+int rsim_config_grad_tables(const rsim_batch* b);
+
 #ifdef __cplusplus
 }
 #endif

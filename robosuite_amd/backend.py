@@ -288,6 +288,13 @@ def lib():
                 getattr(L, f + "_attached").argtypes = list(getattr(L, f).argtypes) + [C.POINTER(Attach)]
             L.rsim_config_pairs_attached.argtypes = list(L.rsim_config_pairs.argtypes) + [C.c_int, C.POINTER(C.c_int32)]
             L.rsim_config_tables.argtypes = [vp]
+        if hasattr(L, "rsim_config_clearance_grad"):       # (as above: absent from an earlier build named by RSIM_LIB)
+            cl = list(L.rsim_config_clearance.argtypes)
+            L.rsim_config_clearance_grad.argtypes = cl + [vp]
+            L.rsim_config_clearance_grad_attached.argtypes = cl + [vp, C.POINTER(Attach)]
+            L.rsim_config_collision_cost.argtypes = cl[:9] + [vp, vp, vp, vp]
+            L.rsim_config_collision_cost_attached.argtypes = cl[:9] + [vp, vp, vp, vp, C.POINTER(Attach)]
+            L.rsim_config_grad_tables.argtypes = [vp]
         L.rsim_comm_unique_id.argtypes = [vp, C.c_size_t]
         L.rsim_comm_create.argtypes = [vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
         L.rsim_allreduce_stats.argtypes = [vp, vp, C.c_int, C.c_int]
@@ -1053,6 +1060,76 @@ class HipBatch:
         if flat2:
             return dist[:, 0], pid[:, 0], (ft[:, 0] if fromto else None), st[:, 0]
         return dist, pid, ft, st
+
+    # ---- clearance gradient and collision cost (include/rsim.h rsim_config_clearance_grad / rsim_config_collision_cost, csrc/rsim_grad.hip) -----------
+    def _config_call(self, who, dofs, q, pairs, tol, max_iters, chunks, attach, held, rel):
+        """what config_clearance's relatives share: the checks and the leading C arguments -> (args up to the pair list, ClearOpts, qc, K, 2-D?, keep)"""
+        from . import distance as _dist
+
+        if not hasattr(self._L, "rsim_config_clearance_grad"):
+            raise RsimError(f"{who}: the loaded library has no rsim_{who}")
+        try:
+            o = _dist.options(**{k: v for k, v in (("tol", tol), ("max_iters", max_iters)) if v is not None})
+        except (TypeError, ValueError) as e:
+            raise RsimError(str(e).replace("geom_distance", who)) from None
+        dofs, qc, K, flat2 = self._config_q(who, dofs, q)
+        att, keep = self._attach(who, attach, held, rel)
+        if pairs is None:
+            n, parg, p = 0, None, None
+        else:
+            p = np.ascontiguousarray(np.asarray(pairs), dtype=np.int32)
+            if p.ndim != 2 or p.shape[1] != 2 or p.shape[0] < 1:
+                raise RsimError(f"{who}: npair < 1 or pairs not of shape [P, 2] (got shape {tuple(p.shape)})")
+            n, parg = int(p.shape[0]), p.ctypes.data_as(C.POINTER(C.c_int32))
+        co = ClearOpts(o["tol"], o["max_iters"], int(chunks))
+        head = (self.ptr, len(dofs), (C.c_int32 * len(dofs))(*dofs), K, C.c_void_p(qc.data_ptr()), n, parg)
+        return head, co, att, qc, K, flat2, len(dofs), (keep, p)
+
+    def config_grad_tables(self):
+        """how many signature tables the gradient / cost queries have uploaded so far: 0 for a batch that never asked.  A diagnostic (include/rsim.h)."""
+        return int(self._L.rsim_config_grad_tables(self.ptr)) if hasattr(self._L, "rsim_config_grad_tables") else 0
+
+    def config_clearance_grad(self, dofs, q, pairs=None, distmax=1.0, tol=None, max_iters=None, chunks=0, attach=None, held=None, rel=None):
+        """config_clearance with the derivative of dist with respect to the controlled dofs: -> (dist, pair, fromto, status, grad float32 [B, K, n]); the first
+        four are bit for bit config_clearance's.  grad = n . (s2 v(p2) - s1 v(p1)) for the pair that attains the minimum, n = (p2 - p1) / dist from fromto,
+        v_c(p) = a_c x (p - anchor_c) for a hinge and a_c for a slide at the candidate, s_i the dof signatures of the pair's bodies (a held carried body has its
+        carrier's).  All zeros where pair < 0, where status has OVERLAP (2) and where |dist| < 1e-7.  The direction is read from fromto: its accuracy falls
+        as ulp / |dist| below about a millimetre; where witnesses are not unique (parallel faces) or the nearest pair ties the gradient is one-sided.  2-D q
+        gives [B] / [B, 6] / [B, n].  A pure query on the batch's stream; robosuite_amd/clearance.py clearance_grad is the fp64 host mirror."""
+        import torch
+
+        head, co, att, qc, K, flat2, n, _keep = self._config_call("config_clearance_grad", dofs, q, pairs, tol, max_iters, chunks, attach, held, rel)
+        dev = qc.device
+        dist = torch.empty((self.B, K), dtype=torch.float32, device=dev)
+        pid = torch.empty((self.B, K), dtype=torch.int32, device=dev)
+        ft = torch.empty((self.B, K, 6), dtype=torch.float32, device=dev)
+        st = torch.empty((self.B, K), dtype=torch.int32, device=dev)
+        grad = torch.empty((self.B, K, n), dtype=torch.float32, device=dev)
+        self._ray_fence_in()
+        args = head + (float(distmax), C.byref(co)) + tuple(C.c_void_p(t.data_ptr()) for t in (dist, pid, ft, st, grad))
+        _chk(self._L.rsim_config_clearance_grad(*args) if att is None else self._L.rsim_config_clearance_grad_attached(*args, C.byref(att)))
+        self._ray_fence_out()
+        return tuple(t[:, 0] for t in (dist, pid, ft, st, grad)) if flat2 else (dist, pid, ft, st, grad)
+
+    def config_collision_cost(self, dofs, q, pairs=None, d_safe=0.05, tol=None, max_iters=None, chunks=0, attach=None, held=None, rel=None):
+        """A smooth collision cost over ALL near pairs, and its gradient: -> (cost float32 [B, K], grad float32 [B, K, n], nnear int32 [B, K], noverlap int32
+        [B, K]).  Every listed pair the env evaluates (pairs, attach / held / rel: as config_clearance) is queried with distmax = d_safe; one with d < d_safe
+        adds 1/2 (d_safe - d)^2 to cost and -(d_safe - d) grad d to grad (config_clearance_grad's formula and zero rules); an overlapping pair (status 2) adds
+        1/2 d_safe^2 and no gradient and is counted in noverlap; nnear counts the contributing pairs.  C1 where the nearest pair switches, which the minimum's
+        gradient is not.  No atomics: a repeat call is bit-identical.  robosuite_amd/clearance.py collision_cost is the fp64 host mirror."""
+        import torch
+
+        head, co, att, qc, K, flat2, n, _keep = self._config_call("config_collision_cost", dofs, q, pairs, tol, max_iters, chunks, attach, held, rel)
+        dev = qc.device
+        cost = torch.empty((self.B, K), dtype=torch.float32, device=dev)
+        grad = torch.empty((self.B, K, n), dtype=torch.float32, device=dev)
+        nnear = torch.empty((self.B, K), dtype=torch.int32, device=dev)
+        nover = torch.empty((self.B, K), dtype=torch.int32, device=dev)
+        self._ray_fence_in()
+        args = head + (float(d_safe), C.byref(co)) + tuple(C.c_void_p(t.data_ptr()) for t in (cost, grad, nnear, nover))
+        _chk(self._L.rsim_config_collision_cost(*args) if att is None else self._L.rsim_config_collision_cost_attached(*args, C.byref(att)))
+        self._ray_fence_out()
+        return tuple(t[:, 0] for t in (cost, grad, nnear, nover)) if flat2 else (cost, grad, nnear, nover)
 
     # ---- swept clearance (include/rsim.h rsim_config_sweep / rsim_config_motion_bound, csrc/rsim_sweep.hip) ------------------------------------------
     def _sweep_q(self, who, dofs, q0, q1, pairs):

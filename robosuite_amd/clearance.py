@@ -26,6 +26,17 @@ as given, every pair in every env.  Without attach every function here is what i
 
     active_pairs(flat, dofs, pairs, attach, held) -> bool [P]: which pairs of the default list an env with that held row evaluates
 
+Gradients and the collision cost (include/rsim.h rsim_config_clearance_grad / rsim_config_collision_cost, csrc/rsim_grad.hip).
+
+    joint_frames(flat, qpos, dofs, q, overrides=None, model32=None) -> (axis [n, 3], anchor [n, 3], slide bool [n]): world axis and anchor of every controlled
+                                     column at the candidate, from mjcf.kinematics_np's walk on the fp32-rounded model
+    pair_grad(frames, s1, s2, p1, p2, d) -> [n]: n . (s2_c v_c(p2) - s1_c v_c(p1)), n = (p2 - p1) / d, v_c(p) = a_c x (p - anchor_c) for a hinge, a_c for a slide
+    reduce_grad / reduce_cost        the two below from per-pair results (distance.geom_distance's), for a caller that has them already
+    clearance_grad(...)  -> clearance(...)'s four and grad [n]: pair_grad of the pair that attains the minimum; zeros for a far result, an OVERLAP status
+                                     and |dist| < GRAD_MIN_DIST
+    collision_cost(flat, qpos, dofs, q, pairs=None, d_safe=0.05, ...) -> (cost, grad [n], nnear, noverlap): every pair the env evaluates with distmax = d_safe; a
+                                     pair with d < d_safe adds 1/2 (d_safe - d)^2 and -(d_safe - d) grad d (the zero rules), an overlapping one 1/2 d_safe^2 only
+
 NOT HANDLED: deciding whether an object is grasped (the caller says so); an object attached to an attached object; per-env skipping for explicit lists."""
 from __future__ import annotations
 
@@ -37,6 +48,7 @@ from . import distance, ik, mjcf
 
 MAX_DOFS = 16      # RSIM_JNT_MAX
 ATTACH_MAX = 4     # RSIM_ATTACH_MAX
+GRAD_MIN_DIST = 1e-7      # RSIM_GRAD_MIN_DIST
 
 
 class ClearanceError(ValueError):
@@ -285,3 +297,93 @@ def clearance(flat, qpos, dofs, q, pairs=None, distmax=1.0, tol=distance.DEFAULT
     if not rd < distmax:
         return float(distmax), -1, np.zeros(6), distance.FAR
     return float(rd), int(rk), rf, int(st[rk])
+
+
+# ---- gradients and the collision cost ------------------------------------------------------------------------------------------------------------------------
+def joint_frames(flat, qpos, dofs, q, overrides=None, model32=None):
+    """(axis [n, 3], anchor [n, 3], slide bool [n]) of the controlled columns at the candidate: what mjcf.kinematics_np's walk forms at the moment each joint is
+    applied (axis = R_cur a, anchor = p_cur + R_cur jnt_pos), on the parameters rounded to fp32"""
+    col = _columns(flat, dofs)
+    m = model32 if model32 is not None else _model32(flat, overrides)
+    xanchor, xaxis = mjcf.kinematics_np(m, candidate_qpos(flat, qpos, dofs, q))[5:7]
+    jtype = _I(flat, "jnt_type")
+    axis, anchor, slide = np.zeros((len(col), 3)), np.zeros((len(col), 3)), np.zeros(len(col), dtype=bool)
+    for j, c in col.items():
+        axis[c], anchor[c], slide[c] = xaxis[j], xanchor[j], jtype[j] == mjcf.JNT_SLIDE
+    return axis, anchor, slide
+
+
+def pair_grad(frames, s1, s2, p1, p2, d):
+    """[n]: the derivative of the distance d between nearest points p1 (on a body with signature s1) and p2 (s2) with respect to every controlled column"""
+    axis, anchor, slide = frames
+    p1, p2 = np.asarray(p1, dtype=np.float64), np.asarray(p2, dtype=np.float64)
+    nrm = (p2 - p1) / d
+    out = np.zeros(len(axis))
+    for c in range(len(axis)):
+        f1, f2 = float((int(s1) >> c) & 1), float((int(s2) >> c) & 1)
+        v = axis[c] * (f2 - f1) if slide[c] else np.cross(axis[c], (p2 - anchor[c]) * f2 - (p1 - anchor[c]) * f1)
+        out[c] = nrm @ v
+    return out
+
+
+def _has_dir(d, status):
+    return (int(status) & (distance.FAR | distance.OVERLAP)) == 0 and abs(d) >= GRAD_MIN_DIST
+
+
+def _pair_distances(flat, qpos, dofs, q, pairs, distmax, tol, max_iters, params, overrides, poses, attach, held, rel, check_options):
+    """the listed pairs' (list, dist, fromto, status) at the candidate, a pair the env does not evaluate reading far; and the bodies' signatures under its row"""
+    p = default_pairs(flat, dofs, attach) if pairs is None else distance.check_pairs(flat, pairs)
+    xpos, xquat = fk(flat, qpos, dofs, q, overrides, attach=attach, held=held, rel=rel) if poses is None else poses
+    d, ft, st = distance.geom_distance(flat, xpos, xquat, p, distmax, tol, max_iters, params, check_options=check_options)
+    if pairs is None and attach is not None and len(attach):
+        st = np.where(active_pairs(flat, dofs, p, attach, held), st, st | distance.FAR)
+    return p, d, ft, st, signatures(flat, dofs, attach, held)
+
+
+def reduce_grad(flat, p, d, ft, st, sig, frames, distmax):
+    """the minimum and its gradient from per-pair results (d, ft, st of distance.geom_distance over list p, at any distmax >= this one): -> clearance_grad's five"""
+    n = len(frames[0])
+    rd, rf, rk = distance.reduce_min(np.where(((st & distance.FAR) == 0) & (d < distmax), d, np.inf), ft)
+    if not rd < distmax:
+        return float(distmax), -1, np.zeros(6), distance.FAR, np.zeros(n)
+    grad = np.zeros(n)
+    if _has_dir(rd, st[rk]):
+        gb = _I(flat, "geom_bodyid")
+        grad = pair_grad(frames, sig[gb[p[rk][0]]], sig[gb[p[rk][1]]], rf[:3], rf[3:], rd)
+    return float(rd), int(rk), rf, int(st[rk]), grad
+
+
+def reduce_cost(flat, p, d, ft, st, sig, frames, d_safe):
+    """the collision cost from per-pair results (as reduce_grad): -> collision_cost's four"""
+    gb = _I(flat, "geom_bodyid")
+    cost, grad, nnear, nover = 0.0, np.zeros(len(frames[0])), 0, 0
+    for k in range(len(p)):
+        if (st[k] & distance.FAR) or not d[k] < d_safe:
+            continue
+        w = d_safe - d[k]
+        cost += 0.5 * w * w
+        nnear += 1
+        nover += 1 if st[k] & distance.OVERLAP else 0
+        if _has_dir(d[k], st[k]):
+            grad -= w * pair_grad(frames, sig[gb[p[k][0]]], sig[gb[p[k][1]]], ft[k, :3], ft[k, 3:], d[k])
+    return float(cost), grad, nnear, nover
+
+
+def clearance_grad(flat, qpos, dofs, q, pairs=None, distmax=1.0, tol=distance.DEFAULTS["tol"], max_iters=distance.DEFAULTS["max_iters"], params=None,
+                   overrides=None, poses=None, attach=None, held=None, rel=None, frames=None, check_options=True):
+    """One candidate: -> (dist, pair, fromto [6], status, grad [n]): clearance()'s result and the derivative of dist with respect to the controlled columns.
+    frames: joint_frames() of the candidate, to save the walk; check_options=False lets the distance be iterated past the query's own limits (a reference)."""
+    p, d, ft, st, sig = _pair_distances(flat, qpos, dofs, q, pairs, distmax, tol, max_iters, params, overrides, poses, attach, held, rel, check_options)
+    fr = frames if frames is not None else joint_frames(flat, qpos, dofs, q, overrides)
+    return reduce_grad(flat, p, d, ft, st, sig, fr, distmax)
+
+
+def collision_cost(flat, qpos, dofs, q, pairs=None, d_safe=0.05, tol=distance.DEFAULTS["tol"], max_iters=distance.DEFAULTS["max_iters"], params=None,
+                   overrides=None, poses=None, attach=None, held=None, rel=None, frames=None, check_options=True):
+    """One candidate: -> (cost, grad [n], nnear, noverlap): the sum of 1/2 (d_safe - d)^2 over the pairs the env evaluates that are closer than d_safe, its
+    derivative with respect to the controlled columns, and how many pairs contribute / overlap."""
+    if not d_safe > 0:
+        raise ClearanceError(f"clearance: d_safe {d_safe} is not > 0")
+    p, d, ft, st, sig = _pair_distances(flat, qpos, dofs, q, pairs, d_safe, tol, max_iters, params, overrides, poses, attach, held, rel, check_options)
+    fr = frames if frames is not None else joint_frames(flat, qpos, dofs, q, overrides)
+    return reduce_cost(flat, p, d, ft, st, sig, fr, d_safe)

@@ -98,6 +98,15 @@ class BatchState:
         carried objects attach / held / rel (HipBatch._attach), handed through as they are."""
         return self.batch.config_clearance(dofs, q, pairs=pairs, distmax=distmax, **opts)
 
+    def config_clearance_grad(self, dofs, q, pairs=None, distmax=1.0, **opts):
+        """config_clearance with the derivative of dist with respect to `dofs` (HipBatch.config_clearance_grad): -> (dist, pair, fromto, status, grad).  opts: tol,
+        max_iters, chunks, attach / held / rel."""
+        return self.batch.config_clearance_grad(dofs, q, pairs=pairs, distmax=distmax, **opts)
+
+    def config_collision_cost(self, dofs, q, pairs=None, d_safe=0.05, **opts):
+        """The smooth collision cost over the pairs closer than d_safe and its gradient (HipBatch.config_collision_cost): -> (cost, grad, nnear, noverlap)."""
+        return self.batch.config_collision_cost(dofs, q, pairs=pairs, d_safe=d_safe, **opts)
+
     def config_sweep(self, dofs, q0, q1, pairs=None, distmax=1.0, **opts):
         """Is the motion from q0 to q1 of `dofs` free?  A certified check away from the state (HipBatch.config_sweep): -> (status, t, dist, t_min, pair, fromto,
         steps).  Valid between step1 and step2.  opts: margin, slack, max_steps, fromto, tol, max_iters, and the carried objects attach / held / rel

@@ -89,6 +89,7 @@ extern "C" int rsim_launch_randomize(const DModel* m, const DBatch* b, const DDr
 #include "rsim_ik.h"
 #include "rsim_clear.h"
 #include "rsim_clear_core.h"
+#include "rsim_grad.h"
 #include "rsim_sweep.h"
 #include "rsim_hull.h"
 
@@ -149,7 +150,12 @@ struct rsim_model {
 enum { TIER_NONE, TIER_FUSED, TIER_LIST };   // rsim_batch.tier
 
 // configuration clearance (rsim_clear.hip): what the batch keeps per dof list -- the body table and the slot of every body on the device, and the default pair list
-struct ClearTab { int *d_tab, *d_slot, *d_att; int nel, nslot, natt; std::vector<int> def_pairs, slot; };   // (slot: the host copy of d_slot, for the swept query's refusals)
+struct ClearTab {
+  int *d_tab, *d_slot, *d_att; int nel, nslot, natt; std::vector<int> def_pairs, slot;   // (slot: the host copy of d_slot, for the swept query's refusals)
+  // the gradient and cost queries (rsim_grad.hip): every body's signature word on the host, on the device (d_sig) once one of them has asked; bit c of
+  // slide_mask: controlled column c is a slide joint
+  std::vector<int> sig_words; int* d_sig; unsigned slide_mask;
+};
 
 struct rsim_batch {
   rsim_model* m;
@@ -242,6 +248,10 @@ struct rsim_batch {
   std::map<std::vector<int>, ClearTab> clear_tabs;
   float *d_clear_scr, *d_clear_part;
   size_t clear_scr_n, clear_part_n;   // floats held
+  // clearance gradient / collision cost (rsim_grad.hip): the joint store and the cost's partial results, grown on demand by the first call that asks
+  float *d_grad_jscr, *d_grad_part;
+  size_t grad_jscr_n, grad_part_n;
+  int grad_tabs;                      // signature tables uploaded (rsim_config_grad_tables)
   float* d_sens_f;       // [nsensor][3] touch-site sizes; then [B][nq + nv + nu]: qpos / qvel / ctrl as they were ahead of a debug launch that integrates
   int ended_outside;     // rsim_end_episodes left needs_reset flags for the next rsim_control_step (fresh controllers); rsim_step2_last, which runs no in-kernel controller, drops them first
   // stream groups: control steps of env block g run on gstream[g]; `forked` = the group streams hold work the main stream has not waited for
@@ -1127,7 +1137,9 @@ extern "C" void rsim_batch_free(rsim_batch* b) {
   if (b->d_ray_rf) hipFree(b->d_ray_rf);
   for (auto& kv : b->ik_chains) hipFree(kv.second.first);
   for (auto& kv : b->dist_tables) hipFree(kv.second);
-  for (auto& kv : b->clear_tabs) { hipFree(kv.second.d_tab); hipFree(kv.second.d_slot); if (kv.second.d_att) hipFree(kv.second.d_att); }
+  for (auto& kv : b->clear_tabs) { hipFree(kv.second.d_tab); hipFree(kv.second.d_slot); if (kv.second.d_att) hipFree(kv.second.d_att); if (kv.second.d_sig) hipFree(kv.second.d_sig); }
+  if (b->d_grad_jscr) hipFree(b->d_grad_jscr);
+  if (b->d_grad_part) hipFree(b->d_grad_part);
   if (b->d_clear_scr) hipFree(b->d_clear_scr);
   if (b->d_clear_part) hipFree(b->d_clear_part);
   if (b->db.mprc) hipFree(b->db.mprc);
@@ -2302,6 +2314,7 @@ struct ClearPlan {
   std::vector<unsigned> sig;   // [nbody] bit c set: controlled column c is on the body's path to the world
   std::vector<int> tab, slot;  // the body table; [nbody] slot of a moved body or -1
   int nel, nslot;
+  unsigned slide_mask;         // bit c: controlled column c is a slide joint
   // attachments (include/rsim.h rsim_attach): [nbody] the signature with the body's attachment held (sig: not held), and the index of the attachment a body
   // belongs to -- itself or above it --, -1 for none
   int natt;
@@ -2316,6 +2329,7 @@ static int clear_plan(const rsim_model* m, const char* who, int ndof, const int3
   if (ndof < 1 || ndof > RSIM_JNT_MAX) return fail("%s: ndof %d outside 1..%d", who, ndof, RSIM_JNT_MAX);
   if (!dofs) return fail("%s: dof_ids is NULL", who);
   std::vector<int> col_of_jnt((size_t)m->njnt, -1);
+  unsigned slide = 0u;
   for (int c = 0; c < ndof; c++) {
     if (dof_check(who, m, dofs, c)) return 1;
     int j = -1;
@@ -2327,7 +2341,9 @@ static int clear_plan(const rsim_model* m, const char* who, int ndof, const int3
     if (jtype[j] != rsim_clear::CL_HINGE && jtype[j] != rsim_clear::CL_SLIDE)
       return fail("%s: controlled dof %d belongs to %s, a %s joint (hinge and slide joints only)", who, dofs[c], ik_joint_name(m, j).c_str(), jtype[j] == 0 ? "free" : "ball");
     col_of_jnt[j] = c;
+    if (jtype[j] == rsim_clear::CL_SLIDE) slide |= 1u << c;
   }
+  out->slide_mask = slide;
   out->sig.assign((size_t)m->nbody, 0u);
   out->slot.assign((size_t)m->nbody, -1);
   out->tab.clear();
@@ -2465,6 +2481,9 @@ static int clear_table(rsim_batch* b, const char* who, int ndof, const int32_t* 
     if (clear_plan(b->m, who, ndof, dofs, natt, natt > 0 ? att->bodies : nullptr, &plan)) return 1;
     ClearTab t;
     t.d_tab = t.d_slot = t.d_att = nullptr; t.nel = plan.nel; t.nslot = plan.nslot; t.slot = plan.slot; t.natt = plan.natt;
+    t.d_sig = nullptr; t.slide_mask = plan.slide_mask;
+    t.sig_words.resize((size_t)b->m->nbody);
+    for (int i = 0; i < b->m->nbody; i++) t.sig_words[i] = (int)((plan.sig[i] & 0xffffu) | (plan.sig_held[i] << 16));
     std::vector<int> h;   // what the pair loop's skip rule reads: [nbody] both signatures in one word, [nbody] the attachment a body belongs to
     if (plan.natt > 0) {
       h.resize(2 * (size_t)b->m->nbody);
@@ -2552,10 +2571,35 @@ extern "C" int rsim_config_fk_attached(rsim_batch* b, int ndof, const int32_t* d
                                        const rsim_attach* att) {
   return config_fk(att && att->n ? "rsim_config_fk_attached" : "rsim_config_fk", b, ndof, dof_ids, k, q_dev, xpos_dev, xquat_dev, att);
 }
+// what the gradient and cost entries add to a clearance call's argument: the signature table of the dof list (uploaded by the first call that asks) and the joint
+// store, grown on demand like the pose scratch
+static int grad_args(rsim_batch* b, const ClearTab* tab, const DClear& c, DGrad* g) {
+  memset(g, 0, sizeof(*g));
+  g->c = c;
+  if (!tab->d_sig) {
+    int* d = nullptr;
+    if (dalloc(&d, tab->sig_words.size())) return 1;
+    if (hipMemcpy(d, tab->sig_words.data(), tab->sig_words.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); return fail("hipMemcpy of the signature table failed"); }
+    const_cast<ClearTab*>(tab)->d_sig = d;   // (the table lives in the batch's map; the clearance entries never read this field)
+    b->grad_tabs++;
+  }
+  g->sig = tab->d_sig; g->slide_mask = tab->slide_mask;
+  if (clear_grow(b, &b->d_grad_jscr, &b->grad_jscr_n, (size_t)c.n * 6 * c.NC)) return 1;
+  g->jscr = b->d_grad_jscr;
+  return 0;
+}
+extern "C" int rsim_config_grad_tables(const rsim_batch* b) { return b ? b->grad_tabs : 0; }
+// cost: NOT the minimum but the collision cost (rsim_config_collision_cost): distmax is d_safe, dist_dev is cost_dev, pair_dev / status_dev are the two counts
 static int config_clearance(const char* who, rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, int npair, const int32_t* pairs, float distmax,
-                            const rsim_clear_opts* opts, float* dist_dev, int32_t* pair_dev, float* fromto_dev, int32_t* status_dev, const rsim_attach* att) {
+                            const rsim_clear_opts* opts, float* dist_dev, int32_t* pair_dev, float* fromto_dev, int32_t* status_dev, const rsim_attach* att,
+                            bool want_grad = false, float* grad_dev = nullptr, bool cost = false) {
   if (!b) return fail("%s: batch is NULL", who);
-  if (!dist_dev || !pair_dev) return fail("%s: %s is NULL", who, !dist_dev ? "dist_dev" : "pair_dev");
+  if (cost) {
+    if (!dist_dev || !grad_dev) return fail("%s: %s is NULL", who, !dist_dev ? "cost_dev" : "grad_dev");
+    if (!(distmax > 0.f)) return fail("%s: d_safe %g is not > 0", who, (double)distmax);
+  } else if (!dist_dev || !pair_dev) return fail("%s: %s is NULL", who, !dist_dev ? "dist_dev" : "pair_dev");
+  if (want_grad && (!grad_dev || !fromto_dev || !status_dev))
+    return fail("%s: %s is NULL (the gradient is formed from fromto and status)", who, !grad_dev ? "grad_dev" : !fromto_dev ? "fromto_dev" : "status_dev");
   if (!(distmax >= 0.f)) return fail("%s: distmax %g is not >= 0", who, (double)distmax);
   if (pairs_check(who, npair, pairs)) return 1;
   const rsim_clear_opts def = {1e-6f, 64, 0};
@@ -2580,15 +2624,32 @@ static int config_clearance(const char* who, rsim_batch* b, int ndof, const int3
   const int per = (npair + chunks - 1) / chunks;
   chunks = (npair + per - 1) / per;   // (no empty chunk)
   if (clear_grow(b, &b->d_clear_scr, &b->clear_scr_n, (size_t)a.nslot * 7 * a.NC)) return 1;
-  if (chunks > 1 && clear_grow(b, &b->d_clear_part, &b->clear_part_n, (size_t)chunks * RSIM_CLEAR_PART * a.NC)) return 1;
+  if (!cost && chunks > 1 && clear_grow(b, &b->d_clear_part, &b->clear_part_n, (size_t)chunks * RSIM_CLEAR_PART * a.NC)) return 1;
+  if (cost && chunks > 1 && clear_grow(b, &b->d_grad_part, &b->grad_part_n, (size_t)chunks * (RSIM_GRAD_PART + a.n) * a.NC)) return 1;
   a.scr = b->d_clear_scr; a.part = b->d_clear_part;
   a.npair = npair; a.chunks = chunks;
   a.fo_size = m->fo[FO_cg_size]; a.fo_pos = m->fo[FO_cg_pos]; a.fo_quat = m->fo[FO_cg_quat];
   a.geom = b->d_ray_geom; a.mesh_vert = b->d_mesh;
   a.distmax = distmax; a.tol = o.tol; a.max_iters = o.max_iters;
+  if (cost) {
+    DGrad g;
+    if (grad_args(b, tab, a, &g)) return 1;
+    g.d_safe = distmax; g.cost = dist_dev; g.grad = grad_dev; g.nnear = pair_dev; g.nover = status_dev; g.cpart = b->d_grad_part;
+    int e = rsim_launch_clear_fk(&a, b->stream);
+    if (!e) e = rsim_launch_clear_joints(&g, b->stream);
+    if (!e) e = rsim_launch_clear_cost(&g, b->stream);
+    return launched(who, e);
+  }
   a.dist = dist_dev; a.pair = pair_dev; a.fromto = fromto_dev; a.status = status_dev;
+  DGrad g;
+  if (want_grad) {
+    if (grad_args(b, tab, a, &g)) return 1;
+    g.grad = grad_dev;
+  }
   int e = rsim_launch_clear_fk(&a, b->stream);
   if (!e) e = rsim_launch_clear_dist(&a, b->stream);
+  if (want_grad && !e) e = rsim_launch_clear_joints(&g, b->stream);
+  if (want_grad && !e) e = rsim_launch_clear_grad(&g, b->stream);
   return launched(who, e);
 }
 extern "C" int rsim_config_clearance(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, int npair, const int32_t* pairs, float distmax,
@@ -2600,6 +2661,30 @@ extern "C" int rsim_config_clearance_attached(rsim_batch* b, int ndof, const int
                                               int32_t* status_dev, const rsim_attach* att) {
   return config_clearance(att && att->n ? "rsim_config_clearance_attached" : "rsim_config_clearance", b, ndof, dof_ids, k, q_dev, npair, pairs, distmax, opts,
                           dist_dev, pair_dev, fromto_dev, status_dev, att);
+}
+// ---- clearance gradient and collision cost (rsim_grad.hip, include/rsim.h rsim_config_clearance_grad / rsim_config_collision_cost): the clearance call above, with
+// its plan, tables, scratch and chunking, and the new kernels behind it
+extern "C" int rsim_config_clearance_grad(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, int npair, const int32_t* pairs, float distmax,
+                                          const rsim_clear_opts* opts, float* dist_dev, int32_t* pair_dev, float* fromto_dev, int32_t* status_dev, float* grad_dev) {
+  return config_clearance("rsim_config_clearance_grad", b, ndof, dof_ids, k, q_dev, npair, pairs, distmax, opts, dist_dev, pair_dev, fromto_dev, status_dev, nullptr,
+                          true, grad_dev);
+}
+extern "C" int rsim_config_clearance_grad_attached(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, int npair, const int32_t* pairs,
+                                                   float distmax, const rsim_clear_opts* opts, float* dist_dev, int32_t* pair_dev, float* fromto_dev,
+                                                   int32_t* status_dev, float* grad_dev, const rsim_attach* att) {
+  return config_clearance(att && att->n ? "rsim_config_clearance_grad_attached" : "rsim_config_clearance_grad", b, ndof, dof_ids, k, q_dev, npair, pairs, distmax, opts,
+                          dist_dev, pair_dev, fromto_dev, status_dev, att, true, grad_dev);
+}
+extern "C" int rsim_config_collision_cost(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, int npair, const int32_t* pairs, float d_safe,
+                                          const rsim_clear_opts* opts, float* cost_dev, float* grad_dev, int32_t* nnear_dev, int32_t* noverlap_dev) {
+  return config_clearance("rsim_config_collision_cost", b, ndof, dof_ids, k, q_dev, npair, pairs, d_safe, opts, cost_dev, nnear_dev, nullptr, noverlap_dev, nullptr,
+                          false, grad_dev, true);
+}
+extern "C" int rsim_config_collision_cost_attached(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, int npair, const int32_t* pairs,
+                                                   float d_safe, const rsim_clear_opts* opts, float* cost_dev, float* grad_dev, int32_t* nnear_dev,
+                                                   int32_t* noverlap_dev, const rsim_attach* att) {
+  return config_clearance(att && att->n ? "rsim_config_collision_cost_attached" : "rsim_config_collision_cost", b, ndof, dof_ids, k, q_dev, npair, pairs, d_safe, opts,
+                          cost_dev, nnear_dev, nullptr, noverlap_dev, att, false, grad_dev, true);
 }
 
 // ---- swept clearance (rsim_sweep.hip, include/rsim.h rsim_config_sweep / rsim_config_motion_bound) -----------------------------------------------------------

@@ -286,6 +286,31 @@ class VecEnv:
         return self.env.batch.config_clearance(self._arm_dofs("config_clearance", arm), q, pairs=ids, distmax=distmax,
                                                attach=self._attach_ids("config_clearance", attach, arm), held=held, rel=rel, **opts)
 
+    def config_clearance_grad(self, q, arm=0, pairs=None, distmax=1.0, attach=None, held=None, rel=None, **opts):
+        """Which way does this arm configuration move away from the scene?  config_clearance with one more result: -> (dist, pair, fromto, status, grad), grad
+        [n_envs, K, n] the derivative of dist with respect to the arm's joints for the pair that attains the minimum (HipBatch.config_clearance_grad: the
+        formula, the zero rules -- far, overlap, |dist| < 1e-7 -- and the two limits).  arm, pairs, attach / held / rel: as config_clearance.  A step of
+        q + step * grad raises the clearance of that pair; the gradient jumps where the nearest pair switches -- collision_cost does not."""
+        ids = None if pairs is None else self._geom_ids(pairs)
+        return self.env.batch.config_clearance_grad(self._arm_dofs("config_clearance_grad", arm), q, pairs=ids, distmax=distmax,
+                                                    attach=self._attach_ids("config_clearance_grad", attach, arm), held=held, rel=rel, **opts)
+
+    def config_collision_cost(self, q, d_safe=0.05, arm=0, pairs=None, attach=None, held=None, rel=None, **opts):
+        """The smooth collision cost of arm configurations and its gradient: -> (cost, grad, nnear, noverlap) (HipBatch.config_collision_cost): the sum of
+        1/2 (d_safe - d)^2 over the listed pairs closer than d_safe.  arm, pairs, attach / held / rel: as config_clearance."""
+        ids = None if pairs is None else self._geom_ids(pairs)
+        return self.env.batch.config_collision_cost(self._arm_dofs("config_collision_cost", arm), q, pairs=ids, d_safe=d_safe,
+                                                    attach=self._attach_ids("config_collision_cost", attach, arm), held=held, rel=rel, **opts)
+
+    def collision_cost(self, q, d_safe=0.05, arm=0, **opts):
+        """config_collision_cost's cost as a DIFFERENTIABLE torch value: backward is grad_out[..., None] * grad, the device's analytic gradient --
+
+            q.requires_grad_(True)
+            env.collision_cost(q, 0.05).sum().backward()      # q.grad is filled
+
+        First order only (no second derivatives); the cost is C1, so a first-order optimiser on [n_envs, K, n] tensors sees a continuous gradient."""
+        return _collision_cost_fn().apply(q, self, float(d_safe), arm, opts)
+
     def config_sweep(self, q0, q1, arm=0, pairs=None, distmax=1.0, attach=None, held=None, rel=None, **opts):
         """Is the arm motion from q0 to q1 free?  q0, q1 [n_envs, K, n] (2-D for K = 1) ends of K joint-space segments per env, interpolated linearly ->
         (status, t, dist, t_min, pair, fromto, steps) per segment (HipBatch.config_sweep: 0 FREE, 1 HIT, 2 UNDECIDED; the motion is certified to keep more
@@ -356,6 +381,31 @@ class VecEnv:
 
         keys = self._object_keys + self._proprio_keys if keys is None else keys
         return torch.cat([obs[:, self.obs_slices[k]] for k in keys], dim=1)
+
+
+_COST_FN = None
+
+
+def _collision_cost_fn():
+    """the torch.autograd.Function behind VecEnv.collision_cost (built on first use: this module does not import torch)"""
+    global _COST_FN
+    if _COST_FN is None:
+        import torch
+
+        class CollisionCost(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, q, env, d_safe, arm, opts):
+                cost, grad, _, _ = env.config_collision_cost(q.detach(), d_safe, arm=arm, **opts)
+                ctx.save_for_backward(grad)
+                return cost
+
+            @staticmethod
+            def backward(ctx, grad_out):
+                (grad,) = ctx.saved_tensors
+                return grad_out[..., None] * grad, None, None, None, None
+
+        _COST_FN = CollisionCost
+    return _COST_FN
 
 
 def gym_flags(end_reason):
