@@ -737,7 +737,8 @@ int rsim_config_tables(const rsim_batch* b);
  * axis and anchor of every controlled column in a store beside the pose scratch, k_clear_grad (_att) writes the gradient of each candidate's own result,
  * k_clear_cost (_att) and k_clear_cost_sum the cost.  The signature table of a dof list and the joint store are built by the first call that asks: a batch that
  * never asks allocates and launches nothing new (rsim_config_grad_tables, a diagnostic like rsim_config_tables, counts the signature tables).
- * NOT HANDLED: a gradient term inside rsim_ik_site or the fused step; penetration depth and gradients for general convex overlaps; per-pair outputs (all near
+ * The gradient term inside IK is rsim_ik_site_avoid below, which instantiates cost_pairs once more in a code object of its own.
+ * NOT HANDLED: a gradient term inside the fused step; penetration depth and gradients for general convex overlaps; per-pair outputs (all near
  * pairs with their own gradients); second derivatives; gradients of rsim_config_sweep; free or ball joints as controlled dofs. */
 #define RSIM_GRAD_MIN_DIST 1e-7f
 int rsim_config_clearance_grad(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, int npair, const int32_t* pairs, float distmax,
@@ -753,6 +754,58 @@ int rsim_config_collision_cost_attached(rsim_batch* b, int ndof, const int32_t* 
                                         const rsim_clear_opts* opts, float* cost_dev, float* grad_dev, int32_t* nnear_dev, int32_t* noverlap_dev,
                                         const rsim_attach* att);
 int rsim_config_grad_tables(const rsim_batch* b);
+
+/* Collision-aware inverse kinematics: rsim_ik_site with the collision cost's gradient as a SECONDARY TASK in the null space of the pose task, K problems per env,
+ * for the whole batch, on the device (csrc/rsim_ik_avoid.hip; robosuite_amd/ik_avoid.py is the fp64 host mirror and the definition).  The arm's
+ * redundancy leaves the obstacle while the site still reaches the target: what repairs a grazing IK solution, as one call.
+ *   iteration   per problem q <- clamp(q_init), q_rest = q; then repeat: e, J = the site error and Jacobian exactly as rsim_ik_site defines them (a position-only
+ *               target zeroes the angular rows); cost, g, nnear, nover = rsim_config_collision_cost (_attached) at q with the call's pair list, d_safe and
+ *               attachments; conv = rsim_ik_site's convergence test, finished = conv and cost <= cost_tol; STOP if finished or after max_iters updates; else
+ *               A = J J^T + damping I, v = posture_gain (q_rest - q) - avoid_gain g, dq = J^T A^-1 e + v - J^T A^-1 (J v), scaled so that max |dq| <= max_dq,
+ *               q <- clamp(q + dq).  The chain runs max_iters + 1 evaluations; the last one never updates.
+ *   cost_tol    every term of the cost is at most the cost, so cost <= 1/2 (d_safe - d_free)^2 proves every listed pair at least d_free apart.  The default
+ *               1/2 (d_safe / 2)^2 proves d_free = d_safe / 2 and excludes an overlapping pair (which adds 1/2 d_safe^2).  +inf: never wait for the cost.
+ *               (Stopping on nnear == 0 instead would be wrong: the quadratic hinge approaches d_safe asymptotically.)
+ *   frozen      a problem that has stopped is frozen: later evaluations of the chain leave every one of its outputs untouched, and its lane leaves the cost
+ *               kernel before the pair loop.
+ *   outputs     q_out; err, cost and the counts AT q_out; iters = updates made, bit 30 = converged, bit 29 = finished.  q_out of a problem that did not finish
+ *               is the last iterate: finite and, with clamp_range, inside the ranges.
+ *   check_every c > 0: the host reads one "any problem still running" word after every c evaluations and ends the chain early -- the call then SYNCHRONISES the
+ *               stream.  The kernel sets that word with a plain vector store of 1 from every lane that updated; no atomics.  0: fully asynchronous, max_iters + 1
+ *               evaluations.  Finished problems are frozen, so both settings return identical bits.
+ * Pair lists (pairs HOST [npair][2]; NULL with npair 0, or npair < 0: the default list), attachments (att NULL or n == 0: none), per-env skipping and refusals
+ * are rsim_config_collision_cost's; path rules are rsim_ik_site's: a controlled dof that is not on the path to the site is refused by name, so is a ball joint, a
+ * free joint or a mocap body on it, and a joint on the path that is not controlled is held at the env's qpos.  Also refused by name: d_safe <= 0,
+ * avoid_gain < 0, cost_tol < 0, check_every < 0.
+ * A PURE QUERY on each env's own model parameters, on the batch's stream.  Two launches per evaluation (k_ika_cost over (pair chunks, wavefronts), then k_ika_step:
+ * the chunk sum, the step and both walks at the new q) behind k_ika_init; rsim_grad.hip, rsim_clear.hip and rsim_ik.hip are untouched.  A batch that never asks
+ * allocates and launches nothing new (rsim_ik_avoid_tables, a diagnostic like rsim_config_grad_tables, counts the (site, dofs) keys asked for; the first call of
+ * a dof list also uploads that list's signature table, which rsim_config_grad_tables counts).
+ * LIMITS: a pair that STARTS in a general convex overlap (status 2) adds cost and no push -- hand in several start vectors, K > 1; a listed pair that stays inside
+ * d_safe whatever the arm does (the Panda's link0 / link1 geoms, 1 mm apart) never lets a problem finish -- hand in the list without parent / child pairs, as for
+ * rsim_config_sweep; a 6-dof arm with a pose target has no null space to use.
+ * NOT HANDLED: avoidance as a weighted primary task; per-pair active sets between iterations; a sweep or avoidance term inside the fused step; free or ball joints
+ * as controlled dofs; compaction of unfinished problems. */
+#define RSIM_IK_AVOID_GAIN 100.0f  /* chosen from the fp64 mirror alone on the test scenes: profiles/ik_avoid_parity.txt */
+typedef struct rsim_ik_avoid_opts {
+  float damping, max_dq, pos_tol, rot_tol, posture_gain; int32_t max_iters, clamp_range;   /* rsim_ik_opts' fields, in its order */
+  float d_safe, avoid_gain, cost_tol; int32_t check_every;
+} rsim_ik_avoid_opts;
+/* defaults (opts == NULL): rsim_ik_opts' (damping 1e-4, max_dq 0.5, pos_tol 1e-4 m, rot_tol 1e-3 rad, posture_gain 0, max_iters 50, clamp_range 1), d_safe 0.05,
+ * avoid_gain RSIM_IK_AVOID_GAIN, cost_tol 1/2 (d_safe / 2)^2, check_every 0 */
+int rsim_ik_site_avoid(rsim_batch* b, int site, int ndof, const int32_t* dof_ids, int k,
+                       const float* target_pos_dev   /* [B][k][3] */,
+                       const float* target_quat_dev  /* [B][k][4] wxyz, or NULL: position only */,
+                       const float* q_init_dev       /* [B][k][ndof], or NULL: the env's current qpos */,
+                       int npair, const int32_t* pairs /* HOST [npair][2]; NULL with npair 0, or npair < 0: the default list */,
+                       const rsim_ik_avoid_opts* opts /* NULL: defaults */, const rsim_clear_opts* clear_opts /* NULL: defaults */,
+                       const rsim_attach* att        /* or NULL */,
+                       float* q_out_dev              /* [B][k][ndof] */,
+                       float* err_dev                /* [B][k][2]: |err_pos|, |omega| at q_out */,
+                       int32_t* iters_dev            /* [B][k]: updates made; bit 30 = converged, bit 29 = finished */,
+                       float* cost_dev               /* [B][k]: the collision cost at q_out */,
+                       int32_t* nnear_dev            /* [B][k] or NULL */, int32_t* noverlap_dev /* [B][k] or NULL */);
+int rsim_ik_avoid_tables(const rsim_batch* b);
 
 #ifdef __cplusplus
 }

@@ -295,6 +295,10 @@ def lib():
             L.rsim_config_collision_cost.argtypes = cl[:9] + [vp, vp, vp, vp]
             L.rsim_config_collision_cost_attached.argtypes = cl[:9] + [vp, vp, vp, vp, C.POINTER(Attach)]
             L.rsim_config_grad_tables.argtypes = [vp]
+        if hasattr(L, "rsim_ik_site_avoid"):               # (as above)
+            L.rsim_ik_site_avoid.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, vp, vp, vp, C.c_int, C.POINTER(C.c_int32), C.POINTER(IkAvoidOpts),
+                                             C.POINTER(ClearOpts), C.POINTER(Attach), vp, vp, vp, vp, vp, vp]
+            L.rsim_ik_avoid_tables.argtypes = [vp]
         L.rsim_comm_unique_id.argtypes = [vp, C.c_size_t]
         L.rsim_comm_create.argtypes = [vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
         L.rsim_allreduce_stats.argtypes = [vp, vp, C.c_int, C.c_int]
@@ -494,6 +498,10 @@ class IkOpts(C.Structure):       # include/rsim.h rsim_ik_opts
 
 class DistOpts(C.Structure):     # include/rsim.h rsim_dist_opts
     _fields_ = [("tol", C.c_float), ("max_iters", C.c_int32)]
+
+
+class IkAvoidOpts(C.Structure):  # include/rsim.h rsim_ik_avoid_opts
+    _fields_ = list(IkOpts._fields_) + [("d_safe", C.c_float), ("avoid_gain", C.c_float), ("cost_tol", C.c_float), ("check_every", C.c_int32)]
 
 
 class ClearOpts(C.Structure):    # include/rsim.h rsim_clear_opts
@@ -1130,6 +1138,81 @@ class HipBatch:
         _chk(self._L.rsim_config_collision_cost(*args) if att is None else self._L.rsim_config_collision_cost_attached(*args, C.byref(att)))
         self._ray_fence_out()
         return tuple(t[:, 0] for t in (cost, grad, nnear, nover)) if flat2 else (cost, grad, nnear, nover)
+
+    # ---- collision-aware inverse kinematics (include/rsim.h rsim_ik_site_avoid, csrc/rsim_ik_avoid.hip) ---------------------------------------------------
+    def ik_avoid_tables(self):
+        """how many (site, dofs) keys solve_ik_avoid has been asked for: 0 for a batch that never asked.  A diagnostic (include/rsim.h)."""
+        return int(self._L.rsim_ik_avoid_tables(self.ptr)) if hasattr(self._L, "rsim_ik_avoid_tables") else 0
+
+    def solve_ik_avoid(self, site, dofs, pos, quat=None, q_init=None, pairs=None, d_safe=0.05, avoid_gain=None, cost_tol=None, check_every=0, tol=None,
+                       dist_max_iters=None, chunks=0, attach=None, held=None, rel=None, **opts):
+        """solve_ik that leaves the obstacles: the gradient of config_collision_cost as a secondary task in the null space of the pose task, K problems per env, on
+        the device.  site, dofs, pos, quat, q_init and opts (damping, max_dq, max_iters, pos_tol, rot_tol, posture_gain, clamp_range): as solve_ik.  pairs, attach
+        / held / rel, tol, dist_max_iters (the distance iteration's cap) and chunks: as config_collision_cost.  Per iteration v = posture_gain (q_rest - q) -
+        avoid_gain grad cost, dq = J^T A^-1 e + v - J^T A^-1 (J v); a problem is FINISHED when it has converged and cost <= cost_tol (None: 1/2 (d_safe / 2)^2,
+        which proves every listed pair at least d_safe / 2 apart; inf: never wait for the cost), and is then frozen.  avoid_gain None: ik_avoid.AVOID_GAIN.
+        check_every = c > 0: the host looks after every c evaluations whether any problem still runs and ends the chain early (the call then synchronises the
+        stream; the results are bit for bit those of 0).
+        -> (q [B, K, n], err [B, K, 2], iters int32 [B, K], converged bool [B, K], finished bool [B, K], cost [B, K], nnear int32 [B, K], noverlap int32 [B, K]),
+        err / cost / counts AT q; 2-D inputs mean K = 1 and give 2-D results.  A pair that starts in a general convex overlap adds cost and no push (use K > 1
+        starts); a listed pair that can never leave d_safe (the Panda's link0 / link1 geoms) never lets a problem finish (hand in the list without parent / child
+        pairs); a 6-dof arm with a pose target has no null space.  robosuite_amd/ik_avoid.py is the fp64 host mirror and the definition."""
+        import torch
+
+        from . import distance as _dist
+        from . import ik_avoid as _ia
+
+        who = "solve_ik_avoid"
+        if not hasattr(self._L, "rsim_ik_site_avoid"):
+            raise RsimError(f"{who}: the loaded library has no rsim_ik_site_avoid")
+        try:
+            o = _ia.options(d_safe=d_safe, cost_tol=cost_tol, check_every=check_every, **({} if avoid_gain is None else {"avoid_gain": avoid_gain}), **opts)
+            do = _dist.options(**{k: v for k, v in (("tol", tol), ("max_iters", dist_max_iters)) if v is not None})
+        except (TypeError, ValueError) as e:
+            raise RsimError(f"{who}: {e}") from None
+        dofs = [int(d) for d in np.asarray(dofs).ravel()]
+        n = len(dofs)
+        given = [("pos", pos, 3)] + ([("quat", quat, 4)] if quat is not None else []) + ([("q_init", q_init, n)] if q_init is not None else [])
+        for name, t, w in given:
+            if not (isinstance(t, torch.Tensor) and t.is_cuda):
+                raise RsimError(f"{who}: {name} must be a CUDA tensor")
+            if t.device.index != self.device:      # (the kernel is handed raw pointers: memory of another GPU is not its to read)
+                raise RsimError(f"{who}: {name} lives on {t.device}, the batch on cuda:{self.device}")
+        flat2 = pos.dim() == 2
+        K = 1 if flat2 else (int(pos.shape[1]) if pos.dim() == 3 else 0)
+        for name, t, w in given:
+            want = (self.B, w) if flat2 else (self.B, K, w)
+            if K < 1 or tuple(t.shape) != want:
+                raise RsimError(f"{who}: {name} must have shape ({self.B}, K, {w}) (or ({self.B}, {w}) for K = 1), got {tuple(t.shape)}")
+        att, _keep = self._attach(who, attach, held, rel)
+        if pairs is None:
+            npair, parg = 0, None
+        else:
+            pl = np.ascontiguousarray(np.asarray(pairs), dtype=np.int32)
+            if pl.ndim != 2 or pl.shape[1] != 2 or pl.shape[0] < 1:
+                raise RsimError(f"{who}: npair < 1 or pairs not of shape [P, 2] (got shape {tuple(pl.shape)})")
+            npair, parg = int(pl.shape[0]), pl.ctypes.data_as(C.POINTER(C.c_int32))
+        f = lambda t: None if t is None else t.contiguous().float()      # noqa: E731
+        p, qt, qi = f(pos), f(quat), f(q_init)
+        dev = p.device
+        q = torch.empty((self.B, K, n), dtype=torch.float32, device=dev)
+        err = torch.empty((self.B, K, 2), dtype=torch.float32, device=dev)
+        it = torch.empty((self.B, K), dtype=torch.int32, device=dev)
+        cost = torch.empty((self.B, K), dtype=torch.float32, device=dev)
+        nnear = torch.empty((self.B, K), dtype=torch.int32, device=dev)
+        nover = torch.empty((self.B, K), dtype=torch.int32, device=dev)
+        io = IkAvoidOpts(o["damping"], o["max_dq"], o["pos_tol"], o["rot_tol"], o["posture_gain"], int(o["max_iters"]), int(bool(o["clamp_range"])), o["d_safe"],
+                         o["avoid_gain"], o["cost_tol"], int(o["check_every"]))
+        co = ClearOpts(do["tol"], do["max_iters"], int(chunks))
+        P = lambda t: None if t is None else C.c_void_p(t.data_ptr())      # noqa: E731
+        self._ray_fence_in()
+        _chk(self._L.rsim_ik_site_avoid(self.ptr, int(site), n, (C.c_int32 * max(n, 1))(*dofs), K, P(p), P(qt), P(qi), npair, parg, C.byref(io), C.byref(co),
+                                        C.byref(att) if att is not None else None, P(q), P(err), P(it), P(cost), P(nnear), P(nover)))
+        self._ray_fence_out()
+        conv, fin = (it & (1 << 30)) != 0, (it & (1 << 29)) != 0
+        it = it & ((1 << 29) - 1)
+        out = (q, err, it, conv, fin, cost, nnear, nover)
+        return tuple(t[:, 0] for t in out) if flat2 else out
 
     # ---- swept clearance (include/rsim.h rsim_config_sweep / rsim_config_motion_bound, csrc/rsim_sweep.hip) ------------------------------------------
     def _sweep_q(self, who, dofs, q0, q1, pairs):

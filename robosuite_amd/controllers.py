@@ -84,6 +84,12 @@ class BatchState:
         """Inverse kinematics of `site` over `dofs` for every env, away from the state (HipBatch.solve_ik): -> (q, err, iters, converged)."""
         return self.batch.solve_ik(site, dofs, pos, quat=quat, q_init=q_init, **opts)
 
+    def solve_ik_avoid(self, site, dofs, pos, quat=None, q_init=None, **opts):
+        """solve_ik with the collision cost's gradient in the null space of the pose task (HipBatch.solve_ik_avoid): -> (q, err, iters, converged, finished,
+        cost, nnear, noverlap).  Unmoved bodies are at the poses as they stand: valid between step1 and step2, like the other views.  opts: pairs, d_safe,
+        avoid_gain, cost_tol, check_every, the solver's and the distance query's options, attach / held / rel."""
+        return self.batch.solve_ik_avoid(site, dofs, pos, quat=quat, q_init=q_init, **opts)
+
     def config_fk(self, dofs, q, attach=None, held=None, rel=None):
         """Body poses at candidate joint vectors of `dofs`, away from the state (HipBatch.config_fk): -> (xpos, xquat).  Valid between step1 and step2."""
         return self.batch.config_fk(dofs, q, attach=attach, held=held, rel=rel)

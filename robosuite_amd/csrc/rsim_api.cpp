@@ -90,6 +90,7 @@ extern "C" int rsim_launch_randomize(const DModel* m, const DBatch* b, const DDr
 #include "rsim_clear.h"
 #include "rsim_clear_core.h"
 #include "rsim_grad.h"
+#include "rsim_ik_avoid.h"
 #include "rsim_sweep.h"
 #include "rsim_hull.h"
 
@@ -252,6 +253,10 @@ struct rsim_batch {
   float *d_grad_jscr, *d_grad_part;
   size_t grad_jscr_n, grad_part_n;
   int grad_tabs;                      // signature tables uploaded (rsim_config_grad_tables)
+  // collision-aware IK (rsim_ik_avoid.hip): the problems' state (clamped start vectors, done flags, the `any` word), grown on demand by the first call that asks
+  float* d_ika_work;
+  size_t ika_work_n;
+  std::map<std::vector<int>, int> ika_keys;   // (site, dof ids) -> calls: the keys rsim_ik_site_avoid has been asked for (rsim_ik_avoid_tables)
   float* d_sens_f;       // [nsensor][3] touch-site sizes; then [B][nq + nv + nu]: qpos / qvel / ctrl as they were ahead of a debug launch that integrates
   int ended_outside;     // rsim_end_episodes left needs_reset flags for the next rsim_control_step (fresh controllers); rsim_step2_last, which runs no in-kernel controller, drops them first
   // stream groups: control steps of env block g run on gstream[g]; `forked` = the group streams hold work the main stream has not waited for
@@ -1140,6 +1145,7 @@ extern "C" void rsim_batch_free(rsim_batch* b) {
   for (auto& kv : b->clear_tabs) { hipFree(kv.second.d_tab); hipFree(kv.second.d_slot); if (kv.second.d_att) hipFree(kv.second.d_att); if (kv.second.d_sig) hipFree(kv.second.d_sig); }
   if (b->d_grad_jscr) hipFree(b->d_grad_jscr);
   if (b->d_grad_part) hipFree(b->d_grad_part);
+  if (b->d_ika_work) hipFree(b->d_ika_work);
   if (b->d_clear_scr) hipFree(b->d_clear_scr);
   if (b->d_clear_part) hipFree(b->d_clear_part);
   if (b->db.mprc) hipFree(b->db.mprc);
@@ -2589,6 +2595,14 @@ static int grad_args(rsim_batch* b, const ClearTab* tab, const DClear& c, DGrad*
   return 0;
 }
 extern "C" int rsim_config_grad_tables(const rsim_batch* b) { return b ? b->grad_tabs : 0; }
+// into how many chunks a call cuts its pair list: what it asks for, or the automatic count (the comment in config_clearance); never an empty chunk
+static int clear_chunks(int asked, int waves, int npair) {
+  const int fill = RSIM_CLEAR_FULL / waves;
+  int chunks = asked > 0 ? asked : std::max(1, fill * fill);
+  chunks = std::max(1, std::min(std::min(chunks, npair), RSIM_CLEAR_MAX_CHUNKS));
+  const int per = (npair + chunks - 1) / chunks;
+  return (npair + per - 1) / per;
+}
 // cost: NOT the minimum but the collision cost (rsim_config_collision_cost): distmax is d_safe, dist_dev is cost_dev, pair_dev / status_dev are the two counts
 static int config_clearance(const char* who, rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, int npair, const int32_t* pairs, float distmax,
                             const rsim_clear_opts* opts, float* dist_dev, int32_t* pair_dev, float* fromto_dev, int32_t* status_dev, const rsim_attach* att,
@@ -2618,11 +2632,7 @@ static int config_clearance(const char* who, rsim_batch* b, int ndof, const int3
   // and once each SIMD of the part has a wavefront (256 CUs x 4 = RSIM_CLEAR_FULL candidate blocks) that is all a cut does: K = 16 and 64 are fastest with ONE
   // chunk (15 ms against 43 ms with 8).  Far below that the part stands empty behind a few wavefronts that walk the whole list: K = 1 (64 blocks) is fastest with
   // one pair per chunk (3.7 ms against 12.6 ms).  Between the two measured ends the count falls with the square of the fill: r = FULL / blocks, chunks = r * r.
-  const int fill = RSIM_CLEAR_FULL / waves;
-  int chunks = o.chunks > 0 ? o.chunks : std::max(1, fill * fill);
-  chunks = std::max(1, std::min(std::min(chunks, npair), RSIM_CLEAR_MAX_CHUNKS));
-  const int per = (npair + chunks - 1) / chunks;
-  chunks = (npair + per - 1) / per;   // (no empty chunk)
+  const int chunks = clear_chunks(o.chunks, waves, npair);
   if (clear_grow(b, &b->d_clear_scr, &b->clear_scr_n, (size_t)a.nslot * 7 * a.NC)) return 1;
   if (!cost && chunks > 1 && clear_grow(b, &b->d_clear_part, &b->clear_part_n, (size_t)chunks * RSIM_CLEAR_PART * a.NC)) return 1;
   if (cost && chunks > 1 && clear_grow(b, &b->d_grad_part, &b->grad_part_n, (size_t)chunks * (RSIM_GRAD_PART + a.n) * a.NC)) return 1;
@@ -2685,6 +2695,104 @@ extern "C" int rsim_config_collision_cost_attached(rsim_batch* b, int ndof, cons
                                                    int32_t* noverlap_dev, const rsim_attach* att) {
   return config_clearance(att && att->n ? "rsim_config_collision_cost_attached" : "rsim_config_collision_cost", b, ndof, dof_ids, k, q_dev, npair, pairs, d_safe, opts,
                           cost_dev, nnear_dev, nullptr, noverlap_dev, att, false, grad_dev, true);
+}
+
+// ---- collision-aware inverse kinematics (rsim_ik_avoid.hip, include/rsim.h rsim_ik_site_avoid): rsim_ik_site's path rules and chain head, the collision cost's plan,
+// tables, scratch and chunking, and a chain of two launches per evaluation
+static int ika_path(rsim_batch* b, int site, int ndof, const int32_t* dofs, const int** head) {
+  int nel = 0;
+  if (!ik_chain(b, site, ndof, dofs, head, &nel)) return 0;
+  const char from[] = "rsim_ik_site:";   // the path rules are rsim_ik_site's, and so are their words: only the entry's name differs
+  if (!strncmp(g_err, from, sizeof(from) - 1)) {
+    const std::string rest(g_err + sizeof(from) - 1);
+    snprintf(g_err, sizeof(g_err), "rsim_ik_site_avoid:%s", rest.c_str());
+  }
+  return 1;
+}
+extern "C" int rsim_ik_avoid_tables(const rsim_batch* b) { return b ? (int)b->ika_keys.size() : 0; }
+extern "C" int rsim_ik_site_avoid(rsim_batch* b, int site, int ndof, const int32_t* dof_ids, int k, const float* target_pos_dev, const float* target_quat_dev,
+                                  const float* q_init_dev, int npair, const int32_t* pairs, const rsim_ik_avoid_opts* opts, const rsim_clear_opts* copts,
+                                  const rsim_attach* att, float* q_out_dev, float* err_dev, int32_t* iters_dev, float* cost_dev, int32_t* nnear_dev,
+                                  int32_t* noverlap_dev) {
+  const char* who = "rsim_ik_site_avoid";
+  if (!b) return fail("%s: batch is NULL", who);
+  if (ndof < 1 || ndof > RSIM_JNT_MAX) return fail("%s: ndof %d outside 1..%d", who, ndof, RSIM_JNT_MAX);
+  if (!dof_ids) return fail("%s: dof_ids is NULL", who);
+  if (k < 1) return fail("%s: k %d < 1", who, k);
+  if (!target_pos_dev) return fail("%s: target_pos_dev is NULL", who);
+  if (!q_out_dev || !err_dev || !iters_dev || !cost_dev)
+    return fail("%s: %s is NULL", who, !q_out_dev ? "q_out_dev" : !err_dev ? "err_dev" : !iters_dev ? "iters_dev" : "cost_dev");
+  if (site < 0 || site >= b->m->nsite) return fail("%s: site %d out of range (%d sites)", who, site, b->m->nsite);
+  const float d_def = 0.05f;
+  const rsim_ik_avoid_opts def = {1e-4f, 0.5f, 1e-4f, 1e-3f, 0.f, 50, 1, d_def, RSIM_IK_AVOID_GAIN, 0.5f * (0.5f * d_def) * (0.5f * d_def), 0};
+  const rsim_ik_avoid_opts o = opts ? *opts : def;
+  if (!(o.damping >= 0.f) || !(o.max_dq > 0.f) || !(o.pos_tol >= 0.f) || !(o.rot_tol >= 0.f) || !(o.posture_gain >= 0.f) || o.max_iters < 0 || o.max_iters >= (1 << 29))
+    return fail("%s: option out of range (damping %g, max_dq %g, pos_tol %g, rot_tol %g, posture_gain %g, max_iters %d)", who, (double)o.damping, (double)o.max_dq,
+                (double)o.pos_tol, (double)o.rot_tol, (double)o.posture_gain, o.max_iters);
+  if (!(o.d_safe > 0.f)) return fail("%s: d_safe %g is not > 0", who, (double)o.d_safe);
+  if (!(o.avoid_gain >= 0.f)) return fail("%s: avoid_gain %g is not >= 0", who, (double)o.avoid_gain);
+  if (!(o.cost_tol >= 0.f)) return fail("%s: cost_tol %g is not >= 0", who, (double)o.cost_tol);
+  if (o.check_every < 0) return fail("%s: check_every %d is not >= 0", who, o.check_every);
+  if (npair < 0) { npair = 0; pairs = nullptr; }   // the default list
+  if (pairs_check(who, npair, pairs)) return 1;
+  const rsim_clear_opts cdef = {1e-6f, 64, 0};
+  const rsim_clear_opts co = copts ? *copts : cdef;
+  if (!(co.tol >= 0.f) || co.max_iters < 1 || co.max_iters > RSIM_DIST_MAX_ITERS || co.chunks < 0)
+    return fail("%s: option out of range (tol %g, max_iters %d: 1..%d, chunks %d: >= 0)", who, (double)co.tol, co.max_iters, RSIM_DIST_MAX_ITERS, co.chunks);
+  if (join_groups(b)) return 1;
+  HIPCHK(hipSetDevice(b->device));
+  DIkAvoid a;
+  memset(&a, 0, sizeof(a));
+  if (ika_path(b, site, ndof, dof_ids, &a.head)) return 1;   // (refusals come before anything is launched)
+  DClear c;
+  const ClearTab* tab;
+  if (clear_args(b, who, ndof, dof_ids, k, q_out_dev, att, &c, &tab)) return 1;   // Cand::q IS q_out
+  if (c.natt > 0 && !pairs) c.body_sig = tab->d_att;
+  if (pairs_resolve(b, who, tab, &npair, &pairs, &c.pairs)) return 1;
+  if (refresh_derived(b, RSIM_XPOS) || ray_scene(b)) return 1;
+  const rsim_model* m = b->m;
+  const int body = m->I("site_bodyid")[site];
+  if (body < 0 || body >= m->nbody || tab->slot[body] < 0) return fail("%s: the body of site %d is not moved by the controlled dofs", who, site);
+  const int waves = (c.NC + RSIM_CLEAR_LANES - 1) / RSIM_CLEAR_LANES;
+  const int chunks = clear_chunks(co.chunks, waves, npair);
+  const size_t nc = (size_t)c.NC;
+  if (clear_grow(b, &b->d_clear_scr, &b->clear_scr_n, (size_t)c.nslot * 7 * nc)) return 1;
+  if (clear_grow(b, &b->d_grad_part, &b->grad_part_n, (size_t)chunks * (RSIM_GRAD_PART + c.n) * nc)) return 1;
+  if (clear_grow(b, &b->d_ika_work, &b->ika_work_n, (size_t)(c.n + 1) * nc + 1)) return 1;
+  c.scr = b->d_clear_scr;
+  c.npair = npair; c.chunks = chunks;
+  c.fo_size = m->fo[FO_cg_size]; c.fo_pos = m->fo[FO_cg_pos]; c.fo_quat = m->fo[FO_cg_quat];
+  c.geom = b->d_ray_geom; c.mesh_vert = b->d_mesh;
+  c.distmax = o.d_safe; c.tol = co.tol; c.max_iters = co.max_iters;
+  if (grad_args(b, tab, c, &a.g)) return 1;
+  a.g.d_safe = o.d_safe; a.g.cost = cost_dev; a.g.nnear = nnear_dev; a.g.nover = noverlap_dev; a.g.cpart = b->d_grad_part;
+  a.q = q_out_dev;
+  a.rows = target_quat_dev ? 6 : 3;
+  a.site_slot = tab->slot[body]; a.o_site_pos = m->fo[FO_site_pos] + 3 * site; a.o_site_quat = m->fo[FO_site_quat] + 4 * site;
+  a.site_sig = (unsigned)tab->sig_words[body] & 0xffffu;
+  a.tpos = target_pos_dev; a.tquat = target_quat_dev; a.q_init = q_init_dev;
+  a.damping = o.damping; a.max_dq = o.max_dq; a.pos_tol = o.pos_tol; a.rot_tol = o.rot_tol; a.posture_gain = o.posture_gain; a.avoid_gain = o.avoid_gain;
+  a.cost_tol = o.cost_tol; a.max_iters = o.max_iters; a.clamp_range = o.clamp_range ? 1 : 0;
+  a.q_rest = b->d_ika_work; a.done = (int*)(b->d_ika_work + (size_t)c.n * nc); a.any = a.done + nc;
+  a.err = err_dev; a.iters = iters_dev;
+  std::vector<int> key(1, site);
+  key.insert(key.end(), dof_ids, dof_ids + ndof);
+  b->ika_keys[key]++;
+  int e = rsim_launch_ika_init(&a, b->stream);
+  // max_iters + 1 evaluations, the last of which never updates; check_every = c > 0: after every c of them one word says whether any problem still runs
+  for (int done = 0; !e && done <= o.max_iters;) {
+    const int block = o.check_every > 0 ? std::min(o.check_every, o.max_iters + 1 - done) : o.max_iters + 1;
+    if (o.check_every > 0) HIPCHK(hipMemsetAsync(a.any, 0, sizeof(int), b->stream));
+    for (int i = 0; i < block && !e; i++) e = rsim_launch_ika_iter(&a, b->stream);
+    done += block;
+    if (!e && o.check_every > 0 && done <= o.max_iters) {
+      int any = 0;
+      HIPCHK(hipMemcpyAsync(&any, a.any, sizeof(int), hipMemcpyDeviceToHost, b->stream));
+      HIPCHK(hipStreamSynchronize(b->stream));
+      if (!any) break;   // every problem has stopped: the evaluations left would pass every lane over
+    }
+  }
+  return launched(who, e);
 }
 
 // ---- swept clearance (rsim_sweep.hip, include/rsim.h rsim_config_sweep / rsim_config_motion_bound) -----------------------------------------------------------

@@ -215,6 +215,28 @@ class VecEnv:
             raise ValueError(f"solve_ik: the controller description has no arm {arm}")
         return self.env.batch.solve_ik(site, dofs, pos, quat=quat, q_init=q_init, **opts)
 
+    def solve_ik_avoid(self, pos, quat=None, arm=0, q_init=None, pairs=None, d_safe=0.05, attach=None, held=None, rel=None, **opts):
+        """Which arm joint positions put the gripper site at this pose AND stand clear of the scene?  solve_ik with the gradient of config_collision_cost as a
+        secondary task in the null space of the pose task -> (q, err, iters, converged, finished, cost, nnear, noverlap) (HipBatch.solve_ik_avoid).  finished =
+        converged and cost <= cost_tol, by default 1/2 (d_safe / 2)^2: every listed pair is then at least d_safe / 2 apart.  Site and dofs: as solve_ik; pairs,
+        attach / held / rel: as config_clearance; opts: avoid_gain, cost_tol, check_every, chunks and solve_ik's.  What repairs a grazing IK solution:
+
+            pairs = [p for p in env.batch.config_pairs(dofs) if not parent_child(p)]      # a pair that can never leave d_safe never lets a problem finish
+            q, err, it, ok, free, cost, nnear, nover = env.solve_ik_avoid(pos, quat, pairs=pairs, q_init=starts)      # K > 1 starts: an overlap gives no push
+        """
+        from .backend import ctrl_desc
+
+        d = ctrl_desc(self.env.cfg)
+        if arm == 0:
+            site, dofs = int(d.eef_site), [int(d.dof_idx[i]) for i in range(d.ndof) if d.part_of[i] == 0]
+        elif arm == 1 and d.narm == 2:
+            site, dofs = int(d.eef_site2), [int(d.dof_idx[8 + i]) for i in range(d.ndof2)]
+        else:
+            raise ValueError(f"solve_ik_avoid: the controller description has no arm {arm}")
+        ids = None if pairs is None else self._geom_ids(pairs)
+        return self.env.batch.solve_ik_avoid(site, dofs, pos, quat=quat, q_init=q_init, pairs=ids, d_safe=d_safe,
+                                             attach=self._attach_ids("solve_ik_avoid", attach, arm), held=held, rel=rel, **opts)
+
     def _arm_dofs(self, who, arm):
         from .backend import ctrl_desc
 
