@@ -538,8 +538,8 @@ int rsim_ik_site(rsim_batch* b, int site, int ndof, const int32_t* dof_ids, int 
  *            fromto holds the deepest points.
  *            RSIM_DIST_FAR (1): beyond distmax: dist = distmax and fromto is zero (MuJoCo's convention).
  *            RSIM_DIST_OVERLAP (2): any other overlapping pair (box, cylinder, ellipsoid and mesh combinations, and a sphere or capsule against one of them):
- *            dist = 0 and fromto is one common point, twice.  THE PENETRATION DEPTH OF GENERAL CONVEX SOLIDS IS NOT COMPUTED HERE; rsim_contacts reports the
- *            depth the simulator itself uses.
+ *            dist = 0 and fromto is one common point, twice.  This entry stops at the surface: rsim_geom_distance_signed below returns depth, normal and
+ *            witnesses for these pairs, and leaves every other result as it is here; rsim_contacts reports the depth the simulator itself uses.
  *            RSIM_DIST_CAP (bit 8, or-ed in): the iteration stopped at max_iters before its bounds were within tol; dist and fromto are the best iterate,
  *            still a valid upper bound of the distance.
  * Algorithm: GJK on the Minkowski difference of the two cores (a sphere is a point, a capsule a segment; the radii come off at the end); each iteration has an
@@ -569,6 +569,33 @@ int rsim_geom_distance(rsim_batch* b, int npair, const int32_t* pairs /* HOST [n
                        float* dist_dev            /* [B][npair] */,
                        float* fromto_dev          /* [B][npair][6], or NULL */,
                        int32_t* status_dev        /* [B][npair], or NULL */);
+
+/* rsim_geom_distance with EVERY overlap signed (csrc/rsim_pen.hip k_dist_signed, the per-pair code csrc/rsim_pen_core.h; robosuite_amd/penetration.py is the fp64
+ * host mirror and the definition).  A pair rsim_geom_distance does not send to RSIM_DIST_OVERLAP comes back bit for bit as that call returns it.  For the others:
+ *   dist     minus the penetration depth: with delta(n) = h_A(n) + h_B(-n), how far geom2 must move along unit n to come free, the depth is a minimum of delta over
+ *            the directions and n, the minimiser, the contact normal from geom1 to geom2.
+ *   fromto   p1 on geom1's surface in its support set along +n, p2 = p1 + dist n on geom2's supporting plane along -n (MuJoCo's convention for a negative
+ *            mj_geomDistance, the one the plane and sphere / capsule pairs follow).  n = (p2 - p1) / dist.
+ *   status   RSIM_DIST_OK, or RSIM_DIST_PEN_CAP (bit 9): the descent made pen_iters projections without coming to rest.  The result is then still a valid
+ *            DIRECTIONAL depth: dist = -delta(n) for the returned n, an upper bound of the depth.  RSIM_DIST_OVERLAP is never set.
+ * Algorithm: a sphere or capsule whose core is apart from the other shape is exact without descent (dist = d_core - r).  Otherwise a descent on the cores: from
+ * the direction of least delta among 13 candidates (the centre line, the axes of both geoms), tilted by 1e-3 rad, each step moves geom2 by (delta(n) + offset) n
+ * -- outside the Minkowski difference by at least offset -- and runs the GJK of rsim_geom_distance once: the witnesses' direction is the next n, accepted only if
+ * delta decreases.  It ends when delta decreases by no more than pen_tol, or not at all, or after pen_iters projections (1 .. RSIM_PEN_MAX_ITERS).
+ * LIMITS: what comes out is a LOCAL minimum of the separating translation, never less than the true depth (each face of the Minkowski difference that holds the
+ * origin's foot is one; penetration.multistart_depth is the global reference).  Where faces are parallel the witnesses are one point of a face each.  The normal
+ * is as good as fp32 resolves a direction over `offset`: depths are within some 1e-4 m of the fp64 mirror, 99 % of them within 1.5e-5 m (profiles/penetration_parity.txt).
+ * Refusals, the pair table cache, asynchrony and the pure-query rule are rsim_geom_distance's; in addition a penetration option out of range is refused by name. */
+#define RSIM_DIST_PEN_CAP 512
+#define RSIM_PEN_MAX_ITERS 128
+typedef struct rsim_pen_opts { float pen_tol; int32_t pen_iters; float offset; } rsim_pen_opts;
+/* defaults (pen == NULL): pen_tol 1e-7 m, pen_iters 64, offset 4e-3 m (DESIGN.md 5.3 records the choice) */
+int rsim_geom_distance_signed(rsim_batch* b, int npair, const int32_t* pairs /* HOST [npair][2] */, float distmax,
+                              const rsim_dist_opts* opts /* NULL: defaults */, const rsim_pen_opts* pen /* NULL: defaults */,
+                              float* dist_dev            /* [B][npair] */,
+                              float* fromto_dev          /* [B][npair][6], or NULL */,
+                              int32_t* status_dev        /* [B][npair], or NULL */,
+                              int32_t* steps_dev         /* [B][npair] projections made, 0 for a pair that did not descend; or NULL */);
 
 /* Configuration clearance for the whole batch, on the device (csrc/rsim_clear.hip): "is this joint configuration free, and by how much?" for k candidate joint
  * vectors per env -- the body poses at each candidate (rsim_config_fk) and the smallest distance between what the candidate moves and everything it can hit
@@ -738,7 +765,8 @@ int rsim_config_tables(const rsim_batch* b);
  * k_clear_cost (_att) and k_clear_cost_sum the cost.  The signature table of a dof list and the joint store are built by the first call that asks: a batch that
  * never asks allocates and launches nothing new (rsim_config_grad_tables, a diagnostic like rsim_config_tables, counts the signature tables).
  * The gradient term inside IK is rsim_ik_site_avoid below, which instantiates cost_pairs once more in a code object of its own.
- * NOT HANDLED: a gradient term inside the fused step; penetration depth and gradients for general convex overlaps; per-pair outputs (all near
+ * NOT HANDLED: a gradient term inside the fused step; penetration depth and gradients for general convex overlaps in THESE entries (the _signed cost below has
+ * them); per-pair outputs (all near
  * pairs with their own gradients); second derivatives; gradients of rsim_config_sweep; free or ball joints as controlled dofs. */
 #define RSIM_GRAD_MIN_DIST 1e-7f
 int rsim_config_clearance_grad(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, int npair, const int32_t* pairs, float distmax,
@@ -754,6 +782,17 @@ int rsim_config_collision_cost_attached(rsim_batch* b, int ndof, const int32_t* 
                                         const rsim_clear_opts* opts, float* cost_dev, float* grad_dev, int32_t* nnear_dev, int32_t* noverlap_dev,
                                         const rsim_attach* att);
 int rsim_config_grad_tables(const rsim_batch* b);
+/* rsim_config_collision_cost (_attached) with rsim_geom_distance_signed as the pair routine (csrc/rsim_pen.hip k_clear_cost_signed (_att), behind the unchanged
+ * k_clear_fk / k_clear_joints and in front of the unchanged k_clear_cost_sum).  An overlapping pair has a direction: it adds 1/2 (d_safe - d)^2 with d < 0 and
+ * -(d_safe - d) grad d, by the gradient formula above, and is counted in nnear_dev and in noverlap_dev, which here counts dist < 0.  A candidate without an
+ * overlap gets cost, counts and gradient bit for bit as rsim_config_collision_cost returns them (with the same chunk count).  Everything else is that call's.
+ * NOT CARRIED: signed distances in rsim_config_clearance, rsim_config_sweep, rsim_config_clearance_grad and rsim_ik_site_avoid. */
+int rsim_config_collision_cost_signed(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, int npair, const int32_t* pairs, float d_safe,
+                                      const rsim_clear_opts* opts, const rsim_pen_opts* pen /* NULL: defaults */, float* cost_dev, float* grad_dev,
+                                      int32_t* nnear_dev, int32_t* noverlap_dev);
+int rsim_config_collision_cost_signed_attached(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, int npair, const int32_t* pairs,
+                                               float d_safe, const rsim_clear_opts* opts, const rsim_pen_opts* pen, float* cost_dev, float* grad_dev,
+                                               int32_t* nnear_dev, int32_t* noverlap_dev, const rsim_attach* att);
 
 /* Collision-aware inverse kinematics: rsim_ik_site with the collision cost's gradient as a SECONDARY TASK in the null space of the pose task, K problems per env,
  * for the whole batch, on the device (csrc/rsim_ik_avoid.hip; robosuite_amd/ik_avoid.py is the fp64 host mirror and the definition).  The arm's

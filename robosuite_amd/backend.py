@@ -275,6 +275,8 @@ def lib():
             L.rsim_ik_site.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, vp, vp, vp, C.POINTER(IkOpts), vp, vp, vp]
         if hasattr(L, "rsim_geom_distance"):
             L.rsim_geom_distance.argtypes = [vp, C.c_int, C.POINTER(C.c_int32), C.c_float, C.POINTER(DistOpts), vp, vp, vp]
+        if hasattr(L, "rsim_geom_distance_signed"):        # (as above: absent from an earlier build named by RSIM_LIB)
+            L.rsim_geom_distance_signed.argtypes = [vp, C.c_int, C.POINTER(C.c_int32), C.c_float, C.POINTER(DistOpts), C.POINTER(PenOpts), vp, vp, vp, vp]
         if hasattr(L, "rsim_config_clearance"):
             L.rsim_config_fk.argtypes = [vp, C.c_int, C.POINTER(C.c_int32), C.c_int, vp, vp, vp]
             L.rsim_config_pairs.argtypes = [vp, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32)]
@@ -295,6 +297,10 @@ def lib():
             L.rsim_config_collision_cost.argtypes = cl[:9] + [vp, vp, vp, vp]
             L.rsim_config_collision_cost_attached.argtypes = cl[:9] + [vp, vp, vp, vp, C.POINTER(Attach)]
             L.rsim_config_grad_tables.argtypes = [vp]
+        if hasattr(L, "rsim_config_collision_cost_signed"):
+            cc = list(L.rsim_config_collision_cost.argtypes)
+            L.rsim_config_collision_cost_signed.argtypes = cc[:9] + [C.POINTER(PenOpts)] + cc[9:]
+            L.rsim_config_collision_cost_signed_attached.argtypes = cc[:9] + [C.POINTER(PenOpts)] + cc[9:] + [C.POINTER(Attach)]
         if hasattr(L, "rsim_ik_site_avoid"):               # (as above)
             L.rsim_ik_site_avoid.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, vp, vp, vp, C.c_int, C.POINTER(C.c_int32), C.POINTER(IkAvoidOpts),
                                              C.POINTER(ClearOpts), C.POINTER(Attach), vp, vp, vp, vp, vp, vp]
@@ -498,6 +504,10 @@ class IkOpts(C.Structure):       # include/rsim.h rsim_ik_opts
 
 class DistOpts(C.Structure):     # include/rsim.h rsim_dist_opts
     _fields_ = [("tol", C.c_float), ("max_iters", C.c_int32)]
+
+
+class PenOpts(C.Structure):      # include/rsim.h rsim_pen_opts
+    _fields_ = [("pen_tol", C.c_float), ("pen_iters", C.c_int32), ("offset", C.c_float)]
 
 
 class IkAvoidOpts(C.Structure):  # include/rsim.h rsim_ik_avoid_opts
@@ -907,14 +917,31 @@ class HipBatch:
         return q, err, it, conv
 
     # ---- geom distance (include/rsim.h rsim_geom_distance, csrc/rsim_dist.hip) ------------------------
-    def geom_distance(self, pairs, distmax=1.0, fromto=True, tol=None, max_iters=None):
+    def _pen_opts(self, who, entry, pen):
+        """the penetration options of a signed=True call as the C structure; RsimError for what the library would refuse, or for a library without the entry"""
+        from . import penetration as _pen
+
+        if not hasattr(self._L, entry):
+            raise RsimError(f"{who}: the loaded library has no {entry}")
+        try:
+            o = _pen.options(pen)
+        except (TypeError, ValueError) as e:
+            raise RsimError(str(e).replace("geom_distance", who)) from None
+        return PenOpts(o["pen_tol"], o["pen_iters"], o["offset"])
+
+    def geom_distance(self, pairs, distmax=1.0, fromto=True, tol=None, max_iters=None, signed=False, pen=None, steps=False):
         """mj_geomDistance for every env and every listed pair: pairs is an int array [P, 2] of MODEL geom ids (host).  -> (dist float32 [B, P], fromto
         float32 [B, P, 6] -- the nearest point on geom1, then on geom2, world frame -- or None with fromto=False, status int32 [B, P]).  status 0: disjoint
         and closer than distmax, or an overlap whose signed distance is exact (a plane pair; spheres / capsules among themselves): dist < 0 is then minus the
         penetration depth; 1: beyond distmax (dist = distmax, fromto zero); 2: any other overlapping pair (dist = 0, fromto one common point twice: the depth
         of general convex overlaps is not computed -- `contacts` reports the one the simulator uses); bit 8 (256): the iteration stopped at max_iters.  A mesh
         geom is its convex hull.  tol (1e-6 m): the gap between the iteration's bounds at which it stops; max_iters (64).  A pure query of the state, on the
-        batch's stream; robosuite_amd/distance.py is the fp64 host mirror (and names the status codes)."""
+        batch's stream; robosuite_amd/distance.py is the fp64 host mirror (and names the status codes).
+        signed=True (rsim_geom_distance_signed, csrc/rsim_pen.hip): every status-2 pair comes back signed instead -- dist = minus the penetration depth, fromto p1
+        on geom1's surface and p2 = p1 + dist n on geom2's supporting plane, n the contact normal from geom1 to geom2, status 0 -- and every other pair bit for
+        bit as without it.  The depth is a LOCAL minimum of the separating translation, never less than the true depth; bit 9 (512): the descent stopped at
+        pen_iters, dist is then the depth along the returned normal.  pen: {"pen_tol": 1e-7, "pen_iters": 64, "offset": 4e-3} (robosuite_amd/penetration.py,
+        the fp64 mirror and the definition).  steps=True (signed only) appends the projections made per pair, int32 [B, P], 0 where a pair did not descend."""
         import torch
 
         from . import distance as _dist
@@ -923,6 +950,9 @@ class HipBatch:
             o = _dist.options(**{k: v for k, v in (("tol", tol), ("max_iters", max_iters)) if v is not None})
         except (TypeError, ValueError) as e:
             raise RsimError(str(e)) from None
+        if (pen is not None or steps) and not signed:
+            raise RsimError("geom_distance: pen and steps go with signed=True")
+        po = self._pen_opts("geom_distance", "rsim_geom_distance_signed", pen) if signed else None
         p = np.ascontiguousarray(np.asarray(pairs), dtype=np.int32)
         if p.ndim != 2 or p.shape[1] != 2 or p.shape[0] < 1:
             raise RsimError(f"geom_distance: npair < 1 or pairs not of shape [P, 2] (got shape {tuple(p.shape)})")
@@ -933,6 +963,13 @@ class HipBatch:
         st = torch.empty((self.B, n), dtype=torch.int32, device=dev)
         co = DistOpts(o["tol"], o["max_iters"])
         self._ray_fence_in()
+        if signed:
+            ns = torch.empty((self.B, n), dtype=torch.int32, device=dev) if steps else None
+            _chk(self._L.rsim_geom_distance_signed(self.ptr, n, p.ctypes.data_as(C.POINTER(C.c_int32)), float(distmax), C.byref(co), C.byref(po),
+                                                   C.c_void_p(dist.data_ptr()), C.c_void_p(ft.data_ptr()) if fromto else None, C.c_void_p(st.data_ptr()),
+                                                   C.c_void_p(ns.data_ptr()) if steps else None))
+            self._ray_fence_out()
+            return (dist, ft, st, ns) if steps else (dist, ft, st)
         _chk(self._L.rsim_geom_distance(self.ptr, n, p.ctypes.data_as(C.POINTER(C.c_int32)), float(distmax), C.byref(co), C.c_void_p(dist.data_ptr()),
                                         C.c_void_p(ft.data_ptr()) if fromto else None, C.c_void_p(st.data_ptr())))
         self._ray_fence_out()
@@ -1119,14 +1156,20 @@ class HipBatch:
         self._ray_fence_out()
         return tuple(t[:, 0] for t in (dist, pid, ft, st, grad)) if flat2 else (dist, pid, ft, st, grad)
 
-    def config_collision_cost(self, dofs, q, pairs=None, d_safe=0.05, tol=None, max_iters=None, chunks=0, attach=None, held=None, rel=None):
+    def config_collision_cost(self, dofs, q, pairs=None, d_safe=0.05, tol=None, max_iters=None, chunks=0, attach=None, held=None, rel=None, signed=False,
+                              pen=None):
         """A smooth collision cost over ALL near pairs, and its gradient: -> (cost float32 [B, K], grad float32 [B, K, n], nnear int32 [B, K], noverlap int32
         [B, K]).  Every listed pair the env evaluates (pairs, attach / held / rel: as config_clearance) is queried with distmax = d_safe; one with d < d_safe
         adds 1/2 (d_safe - d)^2 to cost and -(d_safe - d) grad d to grad (config_clearance_grad's formula and zero rules); an overlapping pair (status 2) adds
         1/2 d_safe^2 and no gradient and is counted in noverlap; nnear counts the contributing pairs.  C1 where the nearest pair switches, which the minimum's
-        gradient is not.  No atomics: a repeat call is bit-identical.  robosuite_amd/clearance.py collision_cost is the fp64 host mirror."""
+        gradient is not.  No atomics: a repeat call is bit-identical.  robosuite_amd/clearance.py collision_cost is the fp64 host mirror.
+        signed=True (rsim_config_collision_cost_signed): the pair routine is geom_distance(signed=True)'s, so an overlapping pair adds 1/2 (d_safe - d)^2 with
+        d < 0 and pushes; noverlap then counts dist < 0.  A candidate without an overlap is bit for bit as without it.  pen: as geom_distance."""
         import torch
 
+        if pen is not None and not signed:
+            raise RsimError("config_collision_cost: pen goes with signed=True")
+        po = self._pen_opts("config_collision_cost", "rsim_config_collision_cost_signed", pen) if signed else None
         head, co, att, qc, K, flat2, n, _keep = self._config_call("config_collision_cost", dofs, q, pairs, tol, max_iters, chunks, attach, held, rel)
         dev = qc.device
         cost = torch.empty((self.B, K), dtype=torch.float32, device=dev)
@@ -1134,8 +1177,11 @@ class HipBatch:
         nnear = torch.empty((self.B, K), dtype=torch.int32, device=dev)
         nover = torch.empty((self.B, K), dtype=torch.int32, device=dev)
         self._ray_fence_in()
-        args = head + (float(d_safe), C.byref(co)) + tuple(C.c_void_p(t.data_ptr()) for t in (cost, grad, nnear, nover))
-        _chk(self._L.rsim_config_collision_cost(*args) if att is None else self._L.rsim_config_collision_cost_attached(*args, C.byref(att)))
+        args = head + (float(d_safe), C.byref(co)) + ((C.byref(po),) if signed else ()) + tuple(C.c_void_p(t.data_ptr()) for t in (cost, grad, nnear, nover))
+        if signed:
+            _chk(self._L.rsim_config_collision_cost_signed(*args) if att is None else self._L.rsim_config_collision_cost_signed_attached(*args, C.byref(att)))
+        else:
+            _chk(self._L.rsim_config_collision_cost(*args) if att is None else self._L.rsim_config_collision_cost_attached(*args, C.byref(att)))
         self._ray_fence_out()
         return tuple(t[:, 0] for t in (cost, grad, nnear, nover)) if flat2 else (cost, grad, nnear, nover)
 

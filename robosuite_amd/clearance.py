@@ -330,11 +330,21 @@ def _has_dir(d, status):
     return (int(status) & (distance.FAR | distance.OVERLAP)) == 0 and abs(d) >= GRAD_MIN_DIST
 
 
-def _pair_distances(flat, qpos, dofs, q, pairs, distmax, tol, max_iters, params, overrides, poses, attach, held, rel, check_options):
-    """the listed pairs' (list, dist, fromto, status) at the candidate, a pair the env does not evaluate reading far; and the bodies' signatures under its row"""
+def _pair_distances(flat, qpos, dofs, q, pairs, distmax, tol, max_iters, params, overrides, poses, attach, held, rel, check_options, signed=False, pen=None):
+    """the listed pairs' (list, dist, fromto, status) at the candidate, a pair the env does not evaluate reading far; and the bodies' signatures under its row.
+    signed: every overlap with its negative distance and witnesses (penetration.pair_signed)"""
     p = default_pairs(flat, dofs, attach) if pairs is None else distance.check_pairs(flat, pairs)
     xpos, xquat = fk(flat, qpos, dofs, q, overrides, attach=attach, held=held, rel=rel) if poses is None else poses
-    d, ft, st = distance.geom_distance(flat, xpos, xquat, p, distmax, tol, max_iters, params, check_options=check_options)
+    if signed:
+        from . import penetration
+
+        o = penetration.options(pen)
+        G = distance.world_geoms(flat, xpos, xquat, p.ravel(), params)
+        d, ft, st = np.zeros(len(p)), np.zeros((len(p), 6)), np.zeros(len(p), dtype=np.int32)
+        for k, (g1, g2) in enumerate(p):
+            d[k], ft[k], st[k] = penetration.pair_signed(G[int(g1)], G[int(g2)], distmax, tol, max_iters, **o)
+    else:
+        d, ft, st = distance.geom_distance(flat, xpos, xquat, p, distmax, tol, max_iters, params, check_options=check_options)
     if pairs is None and attach is not None and len(attach):
         st = np.where(active_pairs(flat, dofs, p, attach, held), st, st | distance.FAR)
     return p, d, ft, st, signatures(flat, dofs, attach, held)
@@ -353,8 +363,9 @@ def reduce_grad(flat, p, d, ft, st, sig, frames, distmax):
     return float(rd), int(rk), rf, int(st[rk]), grad
 
 
-def reduce_cost(flat, p, d, ft, st, sig, frames, d_safe):
-    """the collision cost from per-pair results (as reduce_grad): -> collision_cost's four"""
+def reduce_cost(flat, p, d, ft, st, sig, frames, d_safe, signed=False):
+    """the collision cost from per-pair results (as reduce_grad): -> collision_cost's four.  signed: the results are penetration.pair_signed's, noverlap counts
+    dist < 0"""
     gb = _I(flat, "geom_bodyid")
     cost, grad, nnear, nover = 0.0, np.zeros(len(frames[0])), 0, 0
     for k in range(len(p)):
@@ -363,7 +374,7 @@ def reduce_cost(flat, p, d, ft, st, sig, frames, d_safe):
         w = d_safe - d[k]
         cost += 0.5 * w * w
         nnear += 1
-        nover += 1 if st[k] & distance.OVERLAP else 0
+        nover += 1 if (d[k] < 0 if signed else st[k] & distance.OVERLAP) else 0
         if _has_dir(d[k], st[k]):
             grad -= w * pair_grad(frames, sig[gb[p[k][0]]], sig[gb[p[k][1]]], ft[k, :3], ft[k, 3:], d[k])
     return float(cost), grad, nnear, nover
@@ -379,11 +390,12 @@ def clearance_grad(flat, qpos, dofs, q, pairs=None, distmax=1.0, tol=distance.DE
 
 
 def collision_cost(flat, qpos, dofs, q, pairs=None, d_safe=0.05, tol=distance.DEFAULTS["tol"], max_iters=distance.DEFAULTS["max_iters"], params=None,
-                   overrides=None, poses=None, attach=None, held=None, rel=None, frames=None, check_options=True):
+                   overrides=None, poses=None, attach=None, held=None, rel=None, frames=None, check_options=True, signed=False, pen=None):
     """One candidate: -> (cost, grad [n], nnear, noverlap): the sum of 1/2 (d_safe - d)^2 over the pairs the env evaluates that are closer than d_safe, its
-    derivative with respect to the controlled columns, and how many pairs contribute / overlap."""
+    derivative with respect to the controlled columns, and how many pairs contribute / overlap.  signed=True: an overlapping pair enters with its negative
+    distance (penetration.pair_signed; pen: its options) and its gradient, and noverlap counts dist < 0."""
     if not d_safe > 0:
         raise ClearanceError(f"clearance: d_safe {d_safe} is not > 0")
-    p, d, ft, st, sig = _pair_distances(flat, qpos, dofs, q, pairs, d_safe, tol, max_iters, params, overrides, poses, attach, held, rel, check_options)
+    p, d, ft, st, sig = _pair_distances(flat, qpos, dofs, q, pairs, d_safe, tol, max_iters, params, overrides, poses, attach, held, rel, check_options, signed, pen)
     fr = frames if frames is not None else joint_frames(flat, qpos, dofs, q, overrides)
-    return reduce_cost(flat, p, d, ft, st, sig, fr, d_safe)
+    return reduce_cost(flat, p, d, ft, st, sig, fr, d_safe, signed)

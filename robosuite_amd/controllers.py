@@ -75,10 +75,10 @@ class BatchState:
         """Depth (and `element` segmentation) image of every env on the body poses as they stand (HipBatch.render_depth)."""
         return self.batch.render_depth(camera, height, width, segmentation=segmentation, **opts)
 
-    def geom_distance(self, pairs, distmax=1.0, **opts):
+    def geom_distance(self, pairs, distmax=1.0, signed=False, pen=None, **opts):
         """mj_geomDistance for every env and every listed geom pair on the body poses as they stand: valid between step1 and step2, like the other views
         (HipBatch.geom_distance): -> (dist, fromto, status)."""
-        return self.batch.geom_distance(pairs, distmax=distmax, **opts)
+        return self.batch.geom_distance(pairs, distmax=distmax, **(dict(opts, signed=True, pen=pen) if signed else opts))
 
     def solve_ik(self, site, dofs, pos, quat=None, q_init=None, **opts):
         """Inverse kinematics of `site` over `dofs` for every env, away from the state (HipBatch.solve_ik): -> (q, err, iters, converged)."""

@@ -86,6 +86,7 @@ extern "C" int rsim_launch_randomize(const DModel* m, const DBatch* b, const DDr
 #include "rsim_sensors.h"
 #include "rsim_ray.h"
 #include "rsim_dist.h"
+#include "rsim_pen.h"
 #include "rsim_ik.h"
 #include "rsim_clear.h"
 #include "rsim_clear_core.h"
@@ -2285,8 +2286,28 @@ static int dist_pairs(rsim_batch* b, int npair, const int32_t* pairs, const int*
   *d_tab = it->second;
   return 0;
 }
+// the penetration options of a signed call: defaults, range
+static int pen_options(const char* who, const rsim_pen_opts* pen, rsim_pen_opts* out) {
+  const rsim_pen_opts def = {1e-7f, 64, 4e-3f};
+  *out = pen ? *pen : def;
+  if (!(out->pen_tol >= 0.f) || !(out->offset > 0.f) || !std::isfinite(out->offset) || out->pen_iters < 1 || out->pen_iters > RSIM_PEN_MAX_ITERS)
+    return fail("%s: penetration option out of range (pen_tol %g, offset %g, pen_iters %d: 1..%d)", who, (double)out->pen_tol, (double)out->offset, out->pen_iters,
+                RSIM_PEN_MAX_ITERS);
+  return 0;
+}
+static int geom_distance(rsim_batch* b, int npair, const int32_t* pairs, float distmax, const rsim_dist_opts* opts, float* dist_dev, float* fromto_dev,
+                         int32_t* status_dev, bool is_signed, const rsim_pen_opts* pen, int32_t* steps_dev);
 extern "C" int rsim_geom_distance(rsim_batch* b, int npair, const int32_t* pairs, float distmax, const rsim_dist_opts* opts, float* dist_dev, float* fromto_dev,
                                   int32_t* status_dev) {
+  return geom_distance(b, npair, pairs, distmax, opts, dist_dev, fromto_dev, status_dev, false, nullptr, nullptr);
+}
+extern "C" int rsim_geom_distance_signed(rsim_batch* b, int npair, const int32_t* pairs, float distmax, const rsim_dist_opts* opts, const rsim_pen_opts* pen,
+                                         float* dist_dev, float* fromto_dev, int32_t* status_dev, int32_t* steps_dev) {
+  return geom_distance(b, npair, pairs, distmax, opts, dist_dev, fromto_dev, status_dev, true, pen, steps_dev);
+}
+// (the refusals keep rsim_geom_distance's words for both entries, as the attached clearance entries keep rsim_config_clearance's)
+static int geom_distance(rsim_batch* b, int npair, const int32_t* pairs, float distmax, const rsim_dist_opts* opts, float* dist_dev, float* fromto_dev,
+                         int32_t* status_dev, bool is_signed, const rsim_pen_opts* pen, int32_t* steps_dev) {
   if (!b) return fail("rsim_geom_distance: batch is NULL");
   if (npair < 1) return fail("rsim_geom_distance: npair %d < 1", npair);
   if (!pairs) return fail("rsim_geom_distance: pairs is NULL");
@@ -2298,6 +2319,8 @@ extern "C" int rsim_geom_distance(rsim_batch* b, int npair, const int32_t* pairs
   const rsim_dist_opts o = opts ? *opts : def;
   if (!(o.tol >= 0.f) || o.max_iters < 1 || o.max_iters > RSIM_DIST_MAX_ITERS)
     return fail("rsim_geom_distance: option out of range (tol %g, max_iters %d: 1..%d)", (double)o.tol, o.max_iters, RSIM_DIST_MAX_ITERS);
+  rsim_pen_opts po;
+  if (is_signed && pen_options("rsim_geom_distance_signed", pen, &po)) return 1;
   if (join_groups(b)) return 1;
   HIPCHK(hipSetDevice(b->device));
   DDist a;
@@ -2310,6 +2333,11 @@ extern "C" int rsim_geom_distance(rsim_batch* b, int npair, const int32_t* pairs
   a.geom = b->d_ray_geom; a.mesh_vert = b->d_mesh; a.ft = b->d_ft; a.xpos = b->db.xpos; a.xquat = b->db.xquat;
   a.distmax = distmax; a.tol = o.tol; a.max_iters = o.max_iters;
   a.dist = dist_dev; a.fromto = fromto_dev; a.status = status_dev;
+  if (is_signed) {
+    DPenDist ap;
+    ap.d = a; ap.pen_tol = po.pen_tol; ap.offset = po.offset; ap.pen_iters = po.pen_iters; ap.steps = steps_dev;
+    return launched("rsim_geom_distance_signed", rsim_launch_dist_signed(&ap, b->stream));
+  }
   return launched("rsim_geom_distance", rsim_launch_dist(&a, b->stream));
 }
 
@@ -2606,8 +2634,10 @@ static int clear_chunks(int asked, int waves, int npair) {
 // cost: NOT the minimum but the collision cost (rsim_config_collision_cost): distmax is d_safe, dist_dev is cost_dev, pair_dev / status_dev are the two counts
 static int config_clearance(const char* who, rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, int npair, const int32_t* pairs, float distmax,
                             const rsim_clear_opts* opts, float* dist_dev, int32_t* pair_dev, float* fromto_dev, int32_t* status_dev, const rsim_attach* att,
-                            bool want_grad = false, float* grad_dev = nullptr, bool cost = false) {
+                            bool want_grad = false, float* grad_dev = nullptr, bool cost = false, bool is_signed = false, const rsim_pen_opts* pen = nullptr) {
   if (!b) return fail("%s: batch is NULL", who);
+  rsim_pen_opts po;
+  if (is_signed && pen_options(who, pen, &po)) return 1;
   if (cost) {
     if (!dist_dev || !grad_dev) return fail("%s: %s is NULL", who, !dist_dev ? "cost_dev" : "grad_dev");
     if (!(distmax > 0.f)) return fail("%s: d_safe %g is not > 0", who, (double)distmax);
@@ -2647,7 +2677,12 @@ static int config_clearance(const char* who, rsim_batch* b, int ndof, const int3
     g.d_safe = distmax; g.cost = dist_dev; g.grad = grad_dev; g.nnear = pair_dev; g.nover = status_dev; g.cpart = b->d_grad_part;
     int e = rsim_launch_clear_fk(&a, b->stream);
     if (!e) e = rsim_launch_clear_joints(&g, b->stream);
-    if (!e) e = rsim_launch_clear_cost(&g, b->stream);
+    if (is_signed) {   // the pair loop of rsim_pen.hip between the same two kernels
+      DPenCost gp;
+      gp.g = g; gp.pen_tol = po.pen_tol; gp.offset = po.offset; gp.pen_iters = po.pen_iters;
+      if (!e) e = rsim_launch_clear_cost_signed(&gp, b->stream);
+      if (!e) e = rsim_launch_clear_cost_sum(&g, b->stream);
+    } else if (!e) e = rsim_launch_clear_cost(&g, b->stream);
     return launched(who, e);
   }
   a.dist = dist_dev; a.pair = pair_dev; a.fromto = fromto_dev; a.status = status_dev;
@@ -2695,6 +2730,18 @@ extern "C" int rsim_config_collision_cost_attached(rsim_batch* b, int ndof, cons
                                                    int32_t* noverlap_dev, const rsim_attach* att) {
   return config_clearance(att && att->n ? "rsim_config_collision_cost_attached" : "rsim_config_collision_cost", b, ndof, dof_ids, k, q_dev, npair, pairs, d_safe, opts,
                           cost_dev, nnear_dev, nullptr, noverlap_dev, att, false, grad_dev, true);
+}
+extern "C" int rsim_config_collision_cost_signed(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, int npair, const int32_t* pairs,
+                                                 float d_safe, const rsim_clear_opts* opts, const rsim_pen_opts* pen, float* cost_dev, float* grad_dev,
+                                                 int32_t* nnear_dev, int32_t* noverlap_dev) {
+  return config_clearance("rsim_config_collision_cost_signed", b, ndof, dof_ids, k, q_dev, npair, pairs, d_safe, opts, cost_dev, nnear_dev, nullptr, noverlap_dev,
+                          nullptr, false, grad_dev, true, true, pen);
+}
+extern "C" int rsim_config_collision_cost_signed_attached(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, int npair, const int32_t* pairs,
+                                                          float d_safe, const rsim_clear_opts* opts, const rsim_pen_opts* pen, float* cost_dev, float* grad_dev,
+                                                          int32_t* nnear_dev, int32_t* noverlap_dev, const rsim_attach* att) {
+  return config_clearance(att && att->n ? "rsim_config_collision_cost_signed_attached" : "rsim_config_collision_cost_signed", b, ndof, dof_ids, k, q_dev, npair, pairs,
+                          d_safe, opts, cost_dev, nnear_dev, nullptr, noverlap_dev, att, false, grad_dev, true, true, pen);
 }
 
 // ---- collision-aware inverse kinematics (rsim_ik_avoid.hip, include/rsim.h rsim_ik_site_avoid): rsim_ik_site's path rules and chain head, the collision cost's plan,

@@ -22,3 +22,5 @@ struct DGrad {
 extern "C" int rsim_launch_clear_joints(const DGrad* a, hipStream_t stream);
 extern "C" int rsim_launch_clear_grad(const DGrad* a, hipStream_t stream);
 extern "C" int rsim_launch_clear_cost(const DGrad* a, hipStream_t stream);
+// k_clear_cost_sum alone, behind a pair loop that another code object ran (rsim_pen.hip k_clear_cost_signed); nothing with g.c.chunks <= 1
+extern "C" int rsim_launch_clear_cost_sum(const DGrad* a, hipStream_t stream);

@@ -146,3 +146,9 @@ extern "C" int rsim_launch_clear_cost(const DGrad* a, hipStream_t stream) {
   hipLaunchKernelGGL(k_clear_cost_sum, dim3(waves), dim3(RSIM_CLEAR_LANES), 0, stream, *a);
   return (int)hipGetLastError();
 }
+
+extern "C" int rsim_launch_clear_cost_sum(const DGrad* a, hipStream_t stream) {
+  if (a->c.NC <= 0 || a->c.npair <= 0 || a->c.chunks <= 1) return 0;
+  hipLaunchKernelGGL(k_clear_cost_sum, dim3((a->c.NC + RSIM_CLEAR_LANES - 1) / RSIM_CLEAR_LANES), dim3(RSIM_CLEAR_LANES), 0, stream, *a);
+  return (int)hipGetLastError();
+}

@@ -1,0 +1,171 @@
+// rsim_pen.hip -- the signed distance of overlapping convex pairs on the device: rsim_geom_distance_signed and rsim_config_collision_cost_signed (include/rsim.h).
+// The per-pair algorithm -- a descent on the support width, each step one call of the unchanged GJK core on a moved geom2 -- is rsim_pen_core.h, shared with the
+// host rehearsal (tests/san/pen_core_driver.cpp); robosuite_amd/penetration.py is the fp64 mirror and the definition.
+//
+// A code object of its own: rsim_dist.o and rsim_grad.o compile to what they compiled to, and a batch that never passes signed launches nothing from here.
+//   k_dist_signed             k_dist's grid and lane mapping (lane = env, one 64-lane workgroup is one pair for 64 consecutive envs), pair_signed as the pair
+//                             routine.  A lane whose pair does not overlap leaves pair_signed with pair_distance's result, bit for bit, and then waits for the
+//                             lanes of its wavefront that descend.
+//   k_clear_cost_signed       k_clear_cost's grid, lane mapping and partial results (rsim_grad.hip), run behind the unchanged k_clear_fk / k_clear_joints and in
+//   (_att)                    front of the unchanged k_clear_cost_sum.  The cost loop of rsim_grad_core.h with pair_signed as the pair routine: an overlapping
+//                             pair has a direction, so it passes grad_dir, adds 1/2 (d_safe - d)^2 with d < 0 and pushes.  noverlap counts dist < 0.
+// Every loop is bounded by pen_iters x max_iters, a table length, a vertex count or RSIM_JNT_MAX.  No LDS, no barrier, no private segment.
+#include <hip/hip_runtime.h>
+#include "../../include/rsim.h"
+#include "rsim_pen.h"
+#include "rsim_pen_core.h"
+#include "rsim_grad_core.h"
+
+using namespace rsim_grad;
+static_assert(DIST_PEN_CAP == RSIM_DIST_PEN_CAP, "rsim_pen_core.h DIST_PEN_CAP is include/rsim.h RSIM_DIST_PEN_CAP");
+static_assert(RSIM_PEN_ITERS_LIMIT == RSIM_PEN_MAX_ITERS, "rsim_pen.h RSIM_PEN_ITERS_LIMIT is include/rsim.h RSIM_PEN_MAX_ITERS");
+
+namespace {
+// world pose of geom g in this lane's env (k_dist's load_geom)
+__device__ __forceinline__ Geom dist_geom(const DDist& a, int g, const float* ft, const float* xpos, const float* xquat, int vadr, int vnum) {
+  const DRayGeom& s = a.geom[g];
+  V3 size = ld3(s.size), lp = ld3(s.pos);
+  Q4 lq = ldq(s.quat);
+  if (s.cg >= 0) { size = ld3(ft + a.fo_size + 3 * s.cg); lp = ld3(ft + a.fo_pos + 3 * s.cg); lq = ldq(ft + a.fo_quat + 4 * s.cg); }
+  const Q4 bq = ldq(xquat + 4 * s.body);
+  return make_geom(s.type, size, ld3(xpos + 3 * s.body) + qrot(bq, lp), qunit(qmul(bq, lq)), a.mesh_vert + 3 * (size_t)vadr, vnum);
+}
+
+// the three helpers of rsim_grad.hip's kernels, on the same argument
+__device__ __forceinline__ Cand candidate(const DClear& a, int c) {
+  const int env = c / a.K;
+  Cand r;
+  r.ft = a.ft + (size_t)env * a.fstride;
+  r.qpos = a.qpos + (size_t)env * a.nq;
+  r.q = a.q + (size_t)c * a.n;
+  r.xpos = a.xpos + (size_t)env * a.nbody * 3;
+  r.xquat = a.xquat + (size_t)env * a.nbody * 4;
+  return r;
+}
+__device__ __forceinline__ PoseStore scratch(const DClear& a, int c) {
+  const size_t nc = (size_t)a.NC;
+  PoseStore s;
+  s.pos = a.scr + c; s.quat = a.scr + 3 * nc + c;
+  s.pe = s.qe = 7 * nc; s.ps = s.qs = nc; s.by_body = 0;
+  return s;
+}
+__device__ __forceinline__ JointStore joints(const DGrad& a, int c) {
+  JointStore s;
+  s.a = a.jscr + c; s.ce = 6 * (size_t)a.c.NC; s.cs = (size_t)a.c.NC;
+  return s;
+}
+
+// rsim_grad_core.h cost_pairs with pair_signed as the pair routine; noverlap is dist < 0
+template <bool ATT, class GeomRec>
+__device__ __forceinline__ Cost cost_pairs_signed(const Scene<GeomRec>& sc, int p0, int p1, const Cand& c, const PoseStore& st, const JointStore& js, int n,
+                                                  unsigned slide_mask, float d_safe, float tol, int max_iters, const PenOpts& po, const Att& at, const int* sig,
+                                                  const int* body_att, const GradAcc& ga) {
+  Cost acc;
+  acc.cost = 0.f; acc.nnear = acc.nover = 0;
+  for (int col = 0; col < n; col++) ga.g[col * ga.gs] = 0.f;
+  for (int p = p0; p < p1; p++) {
+    const int* rec = sc.pairs + (size_t)p * sc.rec;
+    const int g1 = RSIM_CLEAR_U(rec[0]), g2 = RSIM_CLEAR_U(rec[1]);
+    const int b1 = RSIM_CLEAR_U(sc.geom[g1].body), b2 = RSIM_CLEAR_U(sc.geom[g2].body);
+    if (ATT && !pair_active(at, b1, b2)) continue;
+    Geom A = load_geom(sc, g1, c, st, RSIM_CLEAR_U(rec[2]), RSIM_CLEAR_U(rec[3]));
+    Geom Bg = load_geom(sc, g2, c, st, RSIM_CLEAR_U(rec[4]), RSIM_CLEAR_U(rec[5]));
+    const V3 org = A.p;
+    A.p = v3(0, 0, 0); Bg.p = Bg.p - org;
+    const Result r = pair_signed(A, Bg, d_safe, tol, max_iters, po);
+    if ((r.status & DIST_FAR) != 0 || !(r.dist < d_safe)) continue;
+    const float w = d_safe - r.dist;
+    acc.cost += 0.5f * w * w;
+    acc.nnear++;
+    acc.nover += r.dist < 0.f ? 1 : 0;
+    const V3 q1 = r.p1 + org, q2 = r.p2 + org;
+    V3 dir;
+    if (!grad_dir(r.dist, p, r.status, q1, q2, dir)) continue;
+    const unsigned w1 = (unsigned)RSIM_CLEAR_U(sig[b1]), w2 = (unsigned)RSIM_CLEAR_U(sig[b2]);
+    const unsigned s1 = sig_pick(w1, ATT && body_att ? RSIM_CLEAR_U(body_att[b1]) : -1, at.held);
+    const unsigned s2 = sig_pick(w2, ATT && body_att ? RSIM_CLEAR_U(body_att[b2]) : -1, at.held);
+    for (int col = 0; col < n; col++)
+      if (((s1 ^ s2) >> col) & 1u) ga.g[col * ga.gs] -= w * col_grad(js, col, (slide_mask >> col) & 1u, dir, q1, q2, s1, s2);
+  }
+  return acc;
+}
+
+template <bool ATT>
+__device__ __forceinline__ void cost_signed_lane(const DPenCost& ap) {
+  const DGrad& a = ap.g;
+  const int chunk = (int)blockIdx.x;
+  const int c = (int)blockIdx.y * RSIM_CLEAR_LANES + (int)threadIdx.x;
+  if (c >= a.c.NC) return;
+  const int n = a.c.n;
+  const int per = (a.c.npair + a.c.chunks - 1) / a.c.chunks;
+  const int p0 = chunk * per, p1 = min(a.c.npair, p0 + per);
+  Scene<DRayGeom> sc;
+  sc.geom = a.c.geom; sc.pairs = a.c.pairs; sc.rec = RSIM_DIST_REC; sc.slot_of_body = a.c.slot_of_body; sc.mesh_vert = a.c.mesh_vert;
+  sc.fo_size = a.c.fo_size; sc.fo_pos = a.c.fo_pos; sc.fo_quat = a.c.fo_quat;
+  Att at = {0u, nullptr, nullptr, nullptr};
+  if (ATT) at = att_of_env(a.c.natt, a.c.held, a.c.rel, a.c.body_sig, a.c.body_att, c / a.c.K);
+  const size_t nc = (size_t)a.c.NC;
+  float* w = a.c.chunks > 1 ? a.cpart + (size_t)chunk * (RSIM_GRAD_PART + n) * nc + c : nullptr;
+  GradAcc ga;   // the lane's own words: of the chunk's partial result, or of the output
+  ga.g = w ? w + RSIM_GRAD_PART * nc : a.grad + (size_t)c * n; ga.gs = w ? nc : 1;
+  PenOpts po;
+  po.pen_tol = ap.pen_tol; po.pen_iters = ap.pen_iters; po.offset = ap.offset;
+  const Cost r = cost_pairs_signed<ATT>(sc, p0, p1, candidate(a.c, c), scratch(a.c, c), joints(a, c), n, a.slide_mask, a.d_safe, a.c.tol, a.c.max_iters, po, at,
+                                        a.sig, a.c.body_att, ga);
+  if (w) {
+    w[0] = r.cost; w[nc] = __int_as_float(r.nnear); w[2 * nc] = __int_as_float(r.nover);
+    return;
+  }
+  a.cost[c] = r.cost;
+  if (a.nnear) a.nnear[c] = r.nnear;
+  if (a.nover) a.nover[c] = r.nover;
+}
+}  // namespace
+
+__global__ __launch_bounds__(RSIM_DIST_LANES) void k_dist_signed(DPenDist ap) {
+  const DDist& a = ap.d;
+  const int pair = (int)blockIdx.x;
+  const int env = (int)blockIdx.y * RSIM_DIST_LANES + (int)threadIdx.x;
+  const bool active = env < a.B;
+  const int e = active ? env : a.B - 1;   // an idle lane of the last block redoes the last env and writes nothing
+  const int* rec = a.pairs + (size_t)pair * RSIM_DIST_REC;
+  const int g1 = __builtin_amdgcn_readfirstlane(rec[0]), g2 = __builtin_amdgcn_readfirstlane(rec[1]);
+  const int adr1 = __builtin_amdgcn_readfirstlane(rec[2]), num1 = __builtin_amdgcn_readfirstlane(rec[3]);
+  const int adr2 = __builtin_amdgcn_readfirstlane(rec[4]), num2 = __builtin_amdgcn_readfirstlane(rec[5]);
+  const float* ft = a.ft + (size_t)e * a.fstride;
+  const float* xpos = a.xpos + (size_t)e * a.nbody * 3;
+  const float* xquat = a.xquat + (size_t)e * a.nbody * 4;
+  Geom A = dist_geom(a, g1, ft, xpos, xquat, adr1, num1), Bg = dist_geom(a, g2, ft, xpos, xquat, adr2, num2);
+  const V3 org = A.p;
+  A.p = v3(0, 0, 0); Bg.p = Bg.p - org;
+  PenOpts po;
+  po.pen_tol = ap.pen_tol; po.pen_iters = ap.pen_iters; po.offset = ap.offset;
+  int steps = 0;
+  const Result r = pair_signed(A, Bg, a.distmax, a.tol, a.max_iters, po, &steps);
+  if (!active) return;
+  const size_t o = (size_t)env * a.npair + pair;
+  const bool far = (r.status & DIST_FAR) != 0;
+  a.dist[o] = r.dist;
+  if (a.status) a.status[o] = r.status;
+  if (ap.steps) ap.steps[o] = steps;
+  if (a.fromto) {
+    const V3 p1 = far ? v3(0, 0, 0) : r.p1 + org, p2 = far ? v3(0, 0, 0) : r.p2 + org;
+    float* f = a.fromto + 6 * o;
+    f[0] = p1.x; f[1] = p1.y; f[2] = p1.z; f[3] = p2.x; f[4] = p2.y; f[5] = p2.z;
+  }
+}
+__global__ __launch_bounds__(RSIM_CLEAR_LANES) void k_clear_cost_signed(DPenCost a) { cost_signed_lane<false>(a); }
+__global__ __launch_bounds__(RSIM_CLEAR_LANES) void k_clear_cost_signed_att(DPenCost a) { cost_signed_lane<true>(a); }
+
+extern "C" int rsim_launch_dist_signed(const DPenDist* a, hipStream_t stream) {
+  if (a->d.B <= 0 || a->d.npair <= 0) return 0;
+  hipLaunchKernelGGL(k_dist_signed, dim3(a->d.npair, (a->d.B + RSIM_DIST_LANES - 1) / RSIM_DIST_LANES), dim3(RSIM_DIST_LANES), 0, stream, *a);
+  return (int)hipGetLastError();
+}
+
+extern "C" int rsim_launch_clear_cost_signed(const DPenCost* a, hipStream_t stream) {
+  if (a->g.c.NC <= 0 || a->g.c.npair <= 0 || a->g.c.chunks <= 0) return 0;
+  const int waves = (a->g.c.NC + RSIM_CLEAR_LANES - 1) / RSIM_CLEAR_LANES;
+  hipLaunchKernelGGL(a->g.c.natt > 0 ? k_clear_cost_signed_att : k_clear_cost_signed, dim3(a->g.c.chunks, waves), dim3(RSIM_CLEAR_LANES), 0, stream, *a);
+  return (int)hipGetLastError();
+}

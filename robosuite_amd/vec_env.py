@@ -169,17 +169,21 @@ class VecEnv:
             out.append(ids)
         return np.asarray(out, dtype=np.int32).reshape(-1, 2)
 
-    def geom_distance(self, pairs, distmax=1.0, fromto=True, **opts):
+    def geom_distance(self, pairs, distmax=1.0, fromto=True, signed=False, pen=None, **opts):
         """mj_geomDistance for every env: pairs is a list of (geom, geom), each a geom name or a model geom id -> (dist [n_envs, P], fromto [n_envs, P, 6] or
         None, status [n_envs, P]) device tensors (HipBatch.geom_distance: status codes, the convex-hull and overlap rules).  The first query after a fused
-        `step` runs one forward pass on the current state, as `raycast` does."""
-        return self.env.batch.geom_distance(self._geom_ids(pairs), distmax=distmax, fromto=fromto, **opts)
+        `step` runs one forward pass on the current state, as `raycast` does.  signed=True: overlapping boxes, cylinders, ellipsoids and meshes (and a
+        sphere or capsule in one of them) come back with dist = minus the penetration depth, witnesses and status 0 instead of (0, one point, status 2); pen:
+        the descent's options (HipBatch.geom_distance)."""
+        so = dict(opts, signed=True, pen=pen) if signed else opts
+        return self.env.batch.geom_distance(self._geom_ids(pairs), distmax=distmax, fromto=fromto, **so)
 
-    def body_distance(self, bodies_a, bodies_b, distmax=1.0, **opts):
+    def body_distance(self, bodies_a, bodies_b, distmax=1.0, signed=False, pen=None, **opts):
         """The smallest distance between two sets of bodies (names or ids) per env: all geom pairs (a geom of A, a geom of B) are queried and reduced with
         torch.min.  -> (min dist [n_envs], its fromto [n_envs, 6], its pair index [n_envs], the pair list int32 [P, 2]).  GEOMS THE QUERY REFUSES ARE
         SKIPPED: mesh geoms whose hull vertices the model does not hold (visual-only meshes), heightfields, a geom against itself, plane against plane
-        (distance.body_pairs).  With every pair beyond distmax the result is (distmax, zeros, 0)."""
+        (distance.body_pairs).  With every pair beyond distmax the result is (distmax, zeros, 0).  signed=True, pen: as geom_distance -- the minimum then is
+        the deepest overlap where bodies overlap, not 0."""
         import torch
 
         from . import distance as _dist
@@ -195,7 +199,7 @@ class VecEnv:
             return [bn.index(b) if isinstance(b, str) else int(b) for b in bodies]
 
         pairs = _dist.body_pairs(flat, ids(bodies_a), ids(bodies_b))
-        dist, ft, _ = self.env.batch.geom_distance(pairs, distmax=distmax, fromto=True, **opts)
+        dist, ft, _ = self.env.batch.geom_distance(pairs, distmax=distmax, fromto=True, **(dict(opts, signed=True, pen=pen) if signed else opts))
         d, k = torch.min(dist, dim=1)
         return d, ft[torch.arange(ft.shape[0], device=ft.device), k], k, pairs
 
@@ -317,20 +321,24 @@ class VecEnv:
         return self.env.batch.config_clearance_grad(self._arm_dofs("config_clearance_grad", arm), q, pairs=ids, distmax=distmax,
                                                     attach=self._attach_ids("config_clearance_grad", attach, arm), held=held, rel=rel, **opts)
 
-    def config_collision_cost(self, q, d_safe=0.05, arm=0, pairs=None, attach=None, held=None, rel=None, **opts):
+    def config_collision_cost(self, q, d_safe=0.05, arm=0, pairs=None, attach=None, held=None, rel=None, signed=False, pen=None, **opts):
         """The smooth collision cost of arm configurations and its gradient: -> (cost, grad, nnear, noverlap) (HipBatch.config_collision_cost): the sum of
-        1/2 (d_safe - d)^2 over the listed pairs closer than d_safe.  arm, pairs, attach / held / rel: as config_clearance."""
+        1/2 (d_safe - d)^2 over the listed pairs closer than d_safe.  arm, pairs, attach / held / rel: as config_clearance.  signed=True: an overlapping pair
+        enters with its negative distance and pushes (HipBatch.config_collision_cost); pen: the descent's options."""
         ids = None if pairs is None else self._geom_ids(pairs)
+        opts = dict(opts, signed=True, pen=pen) if signed else opts
         return self.env.batch.config_collision_cost(self._arm_dofs("config_collision_cost", arm), q, pairs=ids, d_safe=d_safe,
                                                     attach=self._attach_ids("config_collision_cost", attach, arm), held=held, rel=rel, **opts)
 
-    def collision_cost(self, q, d_safe=0.05, arm=0, **opts):
+    def collision_cost(self, q, d_safe=0.05, arm=0, signed=False, pen=None, **opts):
         """config_collision_cost's cost as a DIFFERENTIABLE torch value: backward is grad_out[..., None] * grad, the device's analytic gradient --
 
             q.requires_grad_(True)
             env.collision_cost(q, 0.05).sum().backward()      # q.grad is filled
 
-        First order only (no second derivatives); the cost is C1, so a first-order optimiser on [n_envs, K, n] tensors sees a continuous gradient."""
+        First order only (no second derivatives); the cost is C1, so a first-order optimiser on [n_envs, K, n] tensors sees a continuous gradient.
+        signed=True, pen: as config_collision_cost -- the gradient then leads out of an overlap instead of vanishing in it."""
+        opts = dict(opts, signed=True, pen=pen) if signed else opts
         return _collision_cost_fn().apply(q, self, float(d_safe), arm, opts)
 
     def config_sweep(self, q0, q1, arm=0, pairs=None, distmax=1.0, attach=None, held=None, rel=None, **opts):
