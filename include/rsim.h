@@ -765,8 +765,8 @@ int rsim_config_tables(const rsim_batch* b);
  * k_clear_cost (_att) and k_clear_cost_sum the cost.  The signature table of a dof list and the joint store are built by the first call that asks: a batch that
  * never asks allocates and launches nothing new (rsim_config_grad_tables, a diagnostic like rsim_config_tables, counts the signature tables).
  * The gradient term inside IK is rsim_ik_site_avoid below, which instantiates cost_pairs once more in a code object of its own.
- * NOT HANDLED: a gradient term inside the fused step; penetration depth and gradients for general convex overlaps in THESE entries (the _signed cost below has
- * them); per-pair outputs (all near
+ * NOT HANDLED: a gradient term inside the fused step; penetration depth and gradients for general convex overlaps in THESE entries (their _signed siblings
+ * below have them); per-pair outputs (all near
  * pairs with their own gradients); second derivatives; gradients of rsim_config_sweep; free or ball joints as controlled dofs. */
 #define RSIM_GRAD_MIN_DIST 1e-7f
 int rsim_config_clearance_grad(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, int npair, const int32_t* pairs, float distmax,
@@ -786,13 +786,35 @@ int rsim_config_grad_tables(const rsim_batch* b);
  * k_clear_fk / k_clear_joints and in front of the unchanged k_clear_cost_sum).  An overlapping pair has a direction: it adds 1/2 (d_safe - d)^2 with d < 0 and
  * -(d_safe - d) grad d, by the gradient formula above, and is counted in nnear_dev and in noverlap_dev, which here counts dist < 0.  A candidate without an
  * overlap gets cost, counts and gradient bit for bit as rsim_config_collision_cost returns them (with the same chunk count).  Everything else is that call's.
- * NOT CARRIED: signed distances in rsim_config_clearance, rsim_config_sweep, rsim_config_clearance_grad and rsim_ik_site_avoid. */
+ * NOT CARRIED: signed distances in rsim_config_sweep: a sweep ends in HIT at margin + slack whatever the sign, and its certificate does not change. */
 int rsim_config_collision_cost_signed(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, int npair, const int32_t* pairs, float d_safe,
                                       const rsim_clear_opts* opts, const rsim_pen_opts* pen /* NULL: defaults */, float* cost_dev, float* grad_dev,
                                       int32_t* nnear_dev, int32_t* noverlap_dev);
 int rsim_config_collision_cost_signed_attached(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, int npair, const int32_t* pairs,
                                                float d_safe, const rsim_clear_opts* opts, const rsim_pen_opts* pen, float* cost_dev, float* grad_dev,
                                                int32_t* nnear_dev, int32_t* noverlap_dev, const rsim_attach* att);
+/* rsim_config_clearance (_attached) and rsim_config_clearance_grad (_attached) with rsim_geom_distance_signed as the pair routine (csrc/rsim_pen_query.hip
+ * k_clear_dist_signed (_att), behind the unchanged k_clear_fk and in front of the unchanged k_clear_min; the gradient entries run the unchanged k_clear_joints /
+ * k_clear_grad behind it).  The minimum runs over the SIGNED per-pair values: a colliding candidate reports its deepest listed pair, dist < 0, with that pair's
+ * witnesses and status (RSIM_DIST_OK, or with RSIM_DIST_CAP / RSIM_DIST_PEN_CAP; RSIM_DIST_OVERLAP is never set), the lowest pair index on ties; the gradient is
+ * the formula above along n = (p2 - p1) / dist and is no longer zero there.  The running minimum is handed to the pair routine as max(minimum, 0), so that an
+ * overlapping pair is never taken for far once the minimum is negative; while it is >= 0 the calls are the unsigned entry's: a candidate with no overlapping
+ * pair is bit for bit what the unsigned entry returns (with the same chunk count).  Chunk counts agree in dist and pair.  Depths are local minima of the
+ * separating translation (rsim_geom_distance_signed's LIMITS).  Pair lists, attachments, per-env skipping, refusals, tables, asynchrony and the pure-query
+ * rule are the unsigned entries'; in addition a penetration option out of range is refused by name.  No new tables: rsim_config_tables and
+ * rsim_config_grad_tables count what they counted. */
+int rsim_config_clearance_signed(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, int npair, const int32_t* pairs, float distmax,
+                                 const rsim_clear_opts* opts, const rsim_pen_opts* pen /* NULL: defaults */, float* dist_dev, int32_t* pair_dev,
+                                 float* fromto_dev, int32_t* status_dev);
+int rsim_config_clearance_signed_attached(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, int npair, const int32_t* pairs,
+                                          float distmax, const rsim_clear_opts* opts, const rsim_pen_opts* pen, float* dist_dev, int32_t* pair_dev,
+                                          float* fromto_dev, int32_t* status_dev, const rsim_attach* att);
+int rsim_config_clearance_grad_signed(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, int npair, const int32_t* pairs, float distmax,
+                                      const rsim_clear_opts* opts, const rsim_pen_opts* pen /* NULL: defaults */, float* dist_dev, int32_t* pair_dev,
+                                      float* fromto_dev, int32_t* status_dev, float* grad_dev);
+int rsim_config_clearance_grad_signed_attached(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, int npair, const int32_t* pairs,
+                                               float distmax, const rsim_clear_opts* opts, const rsim_pen_opts* pen, float* dist_dev, int32_t* pair_dev,
+                                               float* fromto_dev, int32_t* status_dev, float* grad_dev, const rsim_attach* att);
 
 /* Collision-aware inverse kinematics: rsim_ik_site with the collision cost's gradient as a SECONDARY TASK in the null space of the pose task, K problems per env,
  * for the whole batch, on the device (csrc/rsim_ik_avoid.hip; robosuite_amd/ik_avoid.py is the fp64 host mirror and the definition).  The arm's
@@ -820,7 +842,8 @@ int rsim_config_collision_cost_signed_attached(rsim_batch* b, int ndof, const in
  * the chunk sum, the step and both walks at the new q) behind k_ika_init; rsim_grad.hip, rsim_clear.hip and rsim_ik.hip are untouched.  A batch that never asks
  * allocates and launches nothing new (rsim_ik_avoid_tables, a diagnostic like rsim_config_grad_tables, counts the (site, dofs) keys asked for; the first call of
  * a dof list also uploads that list's signature table, which rsim_config_grad_tables counts).
- * LIMITS: a pair that STARTS in a general convex overlap (status 2) adds cost and no push -- hand in several start vectors, K > 1; a listed pair that stays inside
+ * LIMITS: in THIS entry a pair that STARTS in a general convex overlap (status 2) adds cost and no push -- use rsim_ik_site_avoid_signed below, or hand in
+ * several start vectors, K > 1; a listed pair that stays inside
  * d_safe whatever the arm does (the Panda's link0 / link1 geoms, 1 mm apart) never lets a problem finish -- hand in the list without parent / child pairs, as for
  * rsim_config_sweep; a 6-dof arm with a pose target has no null space to use.
  * NOT HANDLED: avoidance as a weighted primary task; per-pair active sets between iterations; a sweep or avoidance term inside the fused step; free or ball joints
@@ -845,6 +868,16 @@ int rsim_ik_site_avoid(rsim_batch* b, int site, int ndof, const int32_t* dof_ids
                        float* cost_dev               /* [B][k]: the collision cost at q_out */,
                        int32_t* nnear_dev            /* [B][k] or NULL */, int32_t* noverlap_dev /* [B][k] or NULL */);
 int rsim_ik_avoid_tables(const rsim_batch* b);
+/* rsim_ik_site_avoid with rsim_config_collision_cost_signed as the cost of every evaluation (csrc/rsim_pen_query.hip k_ika_cost_signed (_att) in front of the
+ * unchanged k_ika_step, behind the unchanged k_ika_init): a pair that starts in a general convex overlap has a depth and a normal, so it pushes, and a problem
+ * whose start vector sits in an overlap with its target already reached moves out through the null space instead of standing still for max_iters evaluations.
+ * noverlap_dev counts dist < 0.  With avoid_gain 0 and cost_tol +inf, q_out, err and iters are rsim_ik_site_avoid's bit for bit.  Everything else is that
+ * call's (it takes att itself: no _attached twin); in addition a penetration option out of range is refused by name.  rsim_ik_avoid_tables counts its keys
+ * as that call's. */
+int rsim_ik_site_avoid_signed(rsim_batch* b, int site, int ndof, const int32_t* dof_ids, int k, const float* target_pos_dev, const float* target_quat_dev,
+                              const float* q_init_dev, int npair, const int32_t* pairs, const rsim_ik_avoid_opts* opts, const rsim_clear_opts* clear_opts,
+                              const rsim_pen_opts* pen /* NULL: defaults */, const rsim_attach* att, float* q_out_dev, float* err_dev, int32_t* iters_dev,
+                              float* cost_dev, int32_t* nnear_dev, int32_t* noverlap_dev);
 
 #ifdef __cplusplus
 }

@@ -301,6 +301,16 @@ def lib():
             cc = list(L.rsim_config_collision_cost.argtypes)
             L.rsim_config_collision_cost_signed.argtypes = cc[:9] + [C.POINTER(PenOpts)] + cc[9:]
             L.rsim_config_collision_cost_signed_attached.argtypes = cc[:9] + [C.POINTER(PenOpts)] + cc[9:] + [C.POINTER(Attach)]
+        if hasattr(L, "rsim_config_clearance_signed"):     # (as above)
+            cs = list(L.rsim_config_clearance.argtypes)
+            cs = cs[:9] + [C.POINTER(PenOpts)] + cs[9:]
+            L.rsim_config_clearance_signed.argtypes = cs
+            L.rsim_config_clearance_signed_attached.argtypes = cs + [C.POINTER(Attach)]
+            L.rsim_config_clearance_grad_signed.argtypes = cs + [vp]
+            L.rsim_config_clearance_grad_signed_attached.argtypes = cs + [vp, C.POINTER(Attach)]
+        if hasattr(L, "rsim_ik_site_avoid_signed"):
+            L.rsim_ik_site_avoid_signed.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, vp, vp, vp, C.c_int, C.POINTER(C.c_int32), C.POINTER(IkAvoidOpts),
+                                                    C.POINTER(ClearOpts), C.POINTER(PenOpts), C.POINTER(Attach), vp, vp, vp, vp, vp, vp]
         if hasattr(L, "rsim_ik_site_avoid"):               # (as above)
             L.rsim_ik_site_avoid.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, vp, vp, vp, C.c_int, C.POINTER(C.c_int32), C.POINTER(IkAvoidOpts),
                                              C.POINTER(ClearOpts), C.POINTER(Attach), vp, vp, vp, vp, vp, vp]
@@ -1064,7 +1074,8 @@ class HipBatch:
             raise RsimError(lib().rsim_last_error().decode())
         return out
 
-    def config_clearance(self, dofs, q, pairs=None, distmax=1.0, fromto=True, tol=None, max_iters=None, chunks=0, attach=None, held=None, rel=None):
+    def config_clearance(self, dofs, q, pairs=None, distmax=1.0, fromto=True, tol=None, max_iters=None, chunks=0, attach=None, held=None, rel=None, signed=False,
+                         pen=None):
         """Is this joint configuration free, and by how much?  For K candidate joint vectors per env (q, dofs: as config_fk) the smallest distance between the
         geoms of `pairs` at the candidate's poses: pairs is an int array [P, 2] of MODEL geom ids (host; anything geom_distance accepts), or None for the
         default list (config_pairs).  -> (dist float32 [B, K], pair int32 [B, K] -- the index INTO THE LIST of the pair that attains dist, the lowest on ties
@@ -1073,11 +1084,17 @@ class HipBatch:
         (distmax, -1, zeros, 1).  chunks: into how many pieces the pair list is cut for the device (0 = chosen from B K and P).  A grasped object moves with
         the candidate only if the call says so: attach / held / rel (_attach).  With them the default list is config_pairs(dofs, attach), and an env evaluates
         only the pairs its own held row makes candidate-dependent (a held cube against its fingers drops out, against the table comes in); an explicit list is
-        taken as given, every pair in every env.  A pure query on the batch's stream; robosuite_amd/clearance.py is the fp64 host mirror."""
+        taken as given, every pair in every env.  A pure query on the batch's stream; robosuite_amd/clearance.py is the fp64 host mirror.
+        signed=True (rsim_config_clearance_signed): the pair routine is geom_distance(signed=True)'s and the minimum runs over the signed values, so a colliding
+        candidate reports its DEEPEST listed pair: dist < 0, that pair's witnesses (n = (p2 - p1) / dist) and status 0 (or with bits 256 / 512), never 2.  A
+        candidate without an overlap is bit for bit as without it.  pen: as geom_distance."""
         import torch
 
         from . import distance as _dist
 
+        if pen is not None and not signed:
+            raise RsimError("config_clearance: pen goes with signed=True")
+        po = self._pen_opts("config_clearance", "rsim_config_clearance_signed", pen) if signed else None
         try:
             o = _dist.options(**{k: v for k, v in (("tol", tol), ("max_iters", max_iters)) if v is not None})
         except (TypeError, ValueError) as e:
@@ -1098,9 +1115,13 @@ class HipBatch:
         st = torch.empty((self.B, K), dtype=torch.int32, device=dev)
         co = ClearOpts(o["tol"], o["max_iters"], int(chunks))
         self._ray_fence_in()
-        args = (self.ptr, len(dofs), (C.c_int32 * len(dofs))(*dofs), K, C.c_void_p(qc.data_ptr()), n, parg, float(distmax), C.byref(co),
-                C.c_void_p(dist.data_ptr()), C.c_void_p(pid.data_ptr()), C.c_void_p(ft.data_ptr()) if fromto else None, C.c_void_p(st.data_ptr()))
-        _chk(self._L.rsim_config_clearance(*args) if att is None else self._L.rsim_config_clearance_attached(*args, C.byref(att)))
+        args = (self.ptr, len(dofs), (C.c_int32 * len(dofs))(*dofs), K, C.c_void_p(qc.data_ptr()), n, parg, float(distmax), C.byref(co)) + \
+            ((C.byref(po),) if signed else ()) + \
+            (C.c_void_p(dist.data_ptr()), C.c_void_p(pid.data_ptr()), C.c_void_p(ft.data_ptr()) if fromto else None, C.c_void_p(st.data_ptr()))
+        if signed:
+            _chk(self._L.rsim_config_clearance_signed(*args) if att is None else self._L.rsim_config_clearance_signed_attached(*args, C.byref(att)))
+        else:
+            _chk(self._L.rsim_config_clearance(*args) if att is None else self._L.rsim_config_clearance_attached(*args, C.byref(att)))
         self._ray_fence_out()
         if flat2:
             return dist[:, 0], pid[:, 0], (ft[:, 0] if fromto else None), st[:, 0]
@@ -1134,15 +1155,20 @@ class HipBatch:
         """how many signature tables the gradient / cost queries have uploaded so far: 0 for a batch that never asked.  A diagnostic (include/rsim.h)."""
         return int(self._L.rsim_config_grad_tables(self.ptr)) if hasattr(self._L, "rsim_config_grad_tables") else 0
 
-    def config_clearance_grad(self, dofs, q, pairs=None, distmax=1.0, tol=None, max_iters=None, chunks=0, attach=None, held=None, rel=None):
+    def config_clearance_grad(self, dofs, q, pairs=None, distmax=1.0, tol=None, max_iters=None, chunks=0, attach=None, held=None, rel=None, signed=False, pen=None):
         """config_clearance with the derivative of dist with respect to the controlled dofs: -> (dist, pair, fromto, status, grad float32 [B, K, n]); the first
         four are bit for bit config_clearance's.  grad = n . (s2 v(p2) - s1 v(p1)) for the pair that attains the minimum, n = (p2 - p1) / dist from fromto,
         v_c(p) = a_c x (p - anchor_c) for a hinge and a_c for a slide at the candidate, s_i the dof signatures of the pair's bodies (a held carried body has its
         carrier's).  All zeros where pair < 0, where status has OVERLAP (2) and where |dist| < 1e-7.  The direction is read from fromto: its accuracy falls
         as ulp / |dist| below about a millimetre; where witnesses are not unique (parallel faces) or the nearest pair ties the gradient is one-sided.  2-D q
-        gives [B] / [B, 6] / [B, n].  A pure query on the batch's stream; robosuite_amd/clearance.py clearance_grad is the fp64 host mirror."""
+        gives [B] / [B, 6] / [B, n].  A pure query on the batch's stream; robosuite_amd/clearance.py clearance_grad is the fp64 host mirror.
+        signed=True (rsim_config_clearance_grad_signed): the first four are bit for bit config_clearance(signed=True)'s, and a colliding candidate has the
+        gradient of its deepest pair's signed distance -- the same formula along n = (p2 - p1) / dist -- instead of zeros.  pen: as geom_distance."""
         import torch
 
+        if pen is not None and not signed:
+            raise RsimError("config_clearance_grad: pen goes with signed=True")
+        po = self._pen_opts("config_clearance_grad", "rsim_config_clearance_grad_signed", pen) if signed else None
         head, co, att, qc, K, flat2, n, _keep = self._config_call("config_clearance_grad", dofs, q, pairs, tol, max_iters, chunks, attach, held, rel)
         dev = qc.device
         dist = torch.empty((self.B, K), dtype=torch.float32, device=dev)
@@ -1151,8 +1177,11 @@ class HipBatch:
         st = torch.empty((self.B, K), dtype=torch.int32, device=dev)
         grad = torch.empty((self.B, K, n), dtype=torch.float32, device=dev)
         self._ray_fence_in()
-        args = head + (float(distmax), C.byref(co)) + tuple(C.c_void_p(t.data_ptr()) for t in (dist, pid, ft, st, grad))
-        _chk(self._L.rsim_config_clearance_grad(*args) if att is None else self._L.rsim_config_clearance_grad_attached(*args, C.byref(att)))
+        args = head + (float(distmax), C.byref(co)) + ((C.byref(po),) if signed else ()) + tuple(C.c_void_p(t.data_ptr()) for t in (dist, pid, ft, st, grad))
+        if signed:
+            _chk(self._L.rsim_config_clearance_grad_signed(*args) if att is None else self._L.rsim_config_clearance_grad_signed_attached(*args, C.byref(att)))
+        else:
+            _chk(self._L.rsim_config_clearance_grad(*args) if att is None else self._L.rsim_config_clearance_grad_attached(*args, C.byref(att)))
         self._ray_fence_out()
         return tuple(t[:, 0] for t in (dist, pid, ft, st, grad)) if flat2 else (dist, pid, ft, st, grad)
 
@@ -1191,7 +1220,7 @@ class HipBatch:
         return int(self._L.rsim_ik_avoid_tables(self.ptr)) if hasattr(self._L, "rsim_ik_avoid_tables") else 0
 
     def solve_ik_avoid(self, site, dofs, pos, quat=None, q_init=None, pairs=None, d_safe=0.05, avoid_gain=None, cost_tol=None, check_every=0, tol=None,
-                       dist_max_iters=None, chunks=0, attach=None, held=None, rel=None, **opts):
+                       dist_max_iters=None, chunks=0, attach=None, held=None, rel=None, signed=False, pen=None, **opts):
         """solve_ik that leaves the obstacles: the gradient of config_collision_cost as a secondary task in the null space of the pose task, K problems per env, on
         the device.  site, dofs, pos, quat, q_init and opts (damping, max_dq, max_iters, pos_tol, rot_tol, posture_gain, clamp_range): as solve_ik.  pairs, attach
         / held / rel, tol, dist_max_iters (the distance iteration's cap) and chunks: as config_collision_cost.  Per iteration v = posture_gain (q_rest - q) -
@@ -1200,8 +1229,10 @@ class HipBatch:
         check_every = c > 0: the host looks after every c evaluations whether any problem still runs and ends the chain early (the call then synchronises the
         stream; the results are bit for bit those of 0).
         -> (q [B, K, n], err [B, K, 2], iters int32 [B, K], converged bool [B, K], finished bool [B, K], cost [B, K], nnear int32 [B, K], noverlap int32 [B, K]),
-        err / cost / counts AT q; 2-D inputs mean K = 1 and give 2-D results.  A pair that starts in a general convex overlap adds cost and no push (use K > 1
-        starts); a listed pair that can never leave d_safe (the Panda's link0 / link1 geoms) never lets a problem finish (hand in the list without parent / child
+        err / cost / counts AT q; 2-D inputs mean K = 1 and give 2-D results.  signed=True (rsim_ik_site_avoid_signed): every evaluation's cost is
+        config_collision_cost(signed=True)'s, so a pair that STARTS in a general convex overlap has a depth and a normal and pushes -- a start vector that touches
+        or sits in an obstacle moves out through the null space; noverlap then counts dist < 0; pen: as geom_distance.  Without it such a pair adds cost and no
+        push (use K > 1 starts); a listed pair that can never leave d_safe (the Panda's link0 / link1 geoms) never lets a problem finish (hand in the list without parent / child
         pairs); a 6-dof arm with a pose target has no null space.  robosuite_amd/ik_avoid.py is the fp64 host mirror and the definition."""
         import torch
 
@@ -1211,6 +1242,9 @@ class HipBatch:
         who = "solve_ik_avoid"
         if not hasattr(self._L, "rsim_ik_site_avoid"):
             raise RsimError(f"{who}: the loaded library has no rsim_ik_site_avoid")
+        if pen is not None and not signed:
+            raise RsimError(f"{who}: pen goes with signed=True")
+        po = self._pen_opts(who, "rsim_ik_site_avoid_signed", pen) if signed else None
         try:
             o = _ia.options(d_safe=d_safe, cost_tol=cost_tol, check_every=check_every, **({} if avoid_gain is None else {"avoid_gain": avoid_gain}), **opts)
             do = _dist.options(**{k: v for k, v in (("tol", tol), ("max_iters", dist_max_iters)) if v is not None})
@@ -1252,8 +1286,9 @@ class HipBatch:
         co = ClearOpts(do["tol"], do["max_iters"], int(chunks))
         P = lambda t: None if t is None else C.c_void_p(t.data_ptr())      # noqa: E731
         self._ray_fence_in()
-        _chk(self._L.rsim_ik_site_avoid(self.ptr, int(site), n, (C.c_int32 * max(n, 1))(*dofs), K, P(p), P(qt), P(qi), npair, parg, C.byref(io), C.byref(co),
-                                        C.byref(att) if att is not None else None, P(q), P(err), P(it), P(cost), P(nnear), P(nover)))
+        args = (self.ptr, int(site), n, (C.c_int32 * max(n, 1))(*dofs), K, P(p), P(qt), P(qi), npair, parg, C.byref(io), C.byref(co)) + \
+            ((C.byref(po),) if signed else ()) + (C.byref(att) if att is not None else None, P(q), P(err), P(it), P(cost), P(nnear), P(nover))
+        _chk(self._L.rsim_ik_site_avoid_signed(*args) if signed else self._L.rsim_ik_site_avoid(*args))
         self._ray_fence_out()
         conv, fin = (it & (1 << 30)) != 0, (it & (1 << 29)) != 0
         it = it & ((1 << 29) - 1)

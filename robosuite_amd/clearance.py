@@ -10,6 +10,8 @@ force (tests/test_clearance_host.py).
     default_pairs(flat, dofs)     -> int32 [P, 2]: the model's collision pairs whose two bodies have different signatures, in the collision list's order
     fk(flat, qpos, dofs, q, overrides=None)  -> (xpos [nbody, 3], xquat [nbody, 4]) at the candidate, on fp32-rounded parameters (ik.rounded)
     clearance(flat, qpos, dofs, q, pairs=None, distmax=1.0, tol=1e-6, max_iters=64, params=None, overrides=None) -> (dist, pair, fromto [6], status)
+    clearance / clearance_grad (..., signed=True, pen=None): the minimum over the SIGNED per-pair values (penetration.pair_signed), include/rsim.h
+                                  rsim_config_clearance_signed / rsim_config_clearance_grad_signed
 
 Semantics (include/rsim.h).  A candidate holds positions of the controlled dofs, each of a hinge or slide joint; every other joint is held at `qpos`, and no
 range clamp is applied.  dist is the minimum over the pair list of that pair's geom distance at the candidate's poses, pair the index into the list of the pair
@@ -282,11 +284,18 @@ def fk(flat, qpos, dofs, q, overrides=None, model32=None, attach=None, held=None
 
 
 def clearance(flat, qpos, dofs, q, pairs=None, distmax=1.0, tol=distance.DEFAULTS["tol"], max_iters=distance.DEFAULTS["max_iters"], params=None, overrides=None,
-              poses=None, attach=None, held=None, rel=None):
+              poses=None, attach=None, held=None, rel=None, signed=False, pen=None):
     """One candidate: -> (dist, pair, fromto [6], status).  pairs=None: default_pairs.  params: the env's geom arrays (distance.world_geoms); overrides: its FK
     tables; poses: (xpos, xquat) to use instead of fk() -- the device tests hand the device's own poses in, to hold the distance layer apart from FK.
     attach / held / rel: the env's carried objects; with the default list the pairs the env does not evaluate (active_pairs) are left out of the minimum,
-    `pair` still indexing the whole list."""
+    `pair` still indexing the whole list.  signed=True: the minimum runs over the SIGNED per-pair values (penetration.pair_signed; pen: its options), the
+    lowest index on ties: a colliding candidate reports its deepest pair, dist < 0, with that pair's witnesses and status (never OVERLAP)."""
+    if signed:
+        p, d, ft, st, _ = _pair_distances(flat, qpos, dofs, q, pairs, distmax, tol, max_iters, params, overrides, poses, attach, held, rel, True, True, pen)
+        rd, rf, rk = distance.reduce_min(np.where(((st & distance.FAR) == 0) & (d < distmax), d, np.inf), ft)
+        if not rd < distmax:
+            return float(distmax), -1, np.zeros(6), distance.FAR
+        return float(rd), int(rk), rf, int(st[rk])
     p = default_pairs(flat, dofs, attach) if pairs is None else distance.check_pairs(flat, pairs)
     xpos, xquat = fk(flat, qpos, dofs, q, overrides, attach=attach, held=held, rel=rel) if poses is None else poses
     d, ft, st = distance.geom_distance(flat, xpos, xquat, p, distmax, tol, max_iters, params)
@@ -381,10 +390,11 @@ def reduce_cost(flat, p, d, ft, st, sig, frames, d_safe, signed=False):
 
 
 def clearance_grad(flat, qpos, dofs, q, pairs=None, distmax=1.0, tol=distance.DEFAULTS["tol"], max_iters=distance.DEFAULTS["max_iters"], params=None,
-                   overrides=None, poses=None, attach=None, held=None, rel=None, frames=None, check_options=True):
+                   overrides=None, poses=None, attach=None, held=None, rel=None, frames=None, check_options=True, signed=False, pen=None):
     """One candidate: -> (dist, pair, fromto [6], status, grad [n]): clearance()'s result and the derivative of dist with respect to the controlled columns.
-    frames: joint_frames() of the candidate, to save the walk; check_options=False lets the distance be iterated past the query's own limits (a reference)."""
-    p, d, ft, st, sig = _pair_distances(flat, qpos, dofs, q, pairs, distmax, tol, max_iters, params, overrides, poses, attach, held, rel, check_options)
+    frames: joint_frames() of the candidate, to save the walk; check_options=False lets the distance be iterated past the query's own limits (a reference).
+    signed=True: clearance(signed=True)'s four, and the gradient along n = (p2 - p1) / dist of the deepest pair where dist < 0."""
+    p, d, ft, st, sig = _pair_distances(flat, qpos, dofs, q, pairs, distmax, tol, max_iters, params, overrides, poses, attach, held, rel, check_options, signed, pen)
     fr = frames if frames is not None else joint_frames(flat, qpos, dofs, q, overrides)
     return reduce_grad(flat, p, d, ft, st, sig, fr, distmax)
 

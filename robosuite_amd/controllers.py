@@ -87,7 +87,7 @@ class BatchState:
     def solve_ik_avoid(self, site, dofs, pos, quat=None, q_init=None, **opts):
         """solve_ik with the collision cost's gradient in the null space of the pose task (HipBatch.solve_ik_avoid): -> (q, err, iters, converged, finished,
         cost, nnear, noverlap).  Unmoved bodies are at the poses as they stand: valid between step1 and step2, like the other views.  opts: pairs, d_safe,
-        avoid_gain, cost_tol, check_every, the solver's and the distance query's options, attach / held / rel."""
+        avoid_gain, cost_tol, check_every, the solver's and the distance query's options, attach / held / rel, signed / pen (an overlapping pair pushes)."""
         return self.batch.solve_ik_avoid(site, dofs, pos, quat=quat, q_init=q_init, **opts)
 
     def config_fk(self, dofs, q, attach=None, held=None, rel=None):
@@ -101,12 +101,12 @@ class BatchState:
     def config_clearance(self, dofs, q, pairs=None, distmax=1.0, **opts):
         """The smallest distance over `pairs` at candidate joint vectors of `dofs`, away from the state (HipBatch.config_clearance): -> (dist, pair, fromto,
         status).  Unmoved bodies are at the poses as they stand: valid between step1 and step2, like the other views.  opts: fromto, tol, max_iters, chunks, and the
-        carried objects attach / held / rel (HipBatch._attach), handed through as they are."""
+        carried objects attach / held / rel (HipBatch._attach), handed through as they are; signed / pen: a colliding candidate reports dist < 0."""
         return self.batch.config_clearance(dofs, q, pairs=pairs, distmax=distmax, **opts)
 
     def config_clearance_grad(self, dofs, q, pairs=None, distmax=1.0, **opts):
         """config_clearance with the derivative of dist with respect to `dofs` (HipBatch.config_clearance_grad): -> (dist, pair, fromto, status, grad).  opts: tol,
-        max_iters, chunks, attach / held / rel."""
+        max_iters, chunks, attach / held / rel, signed / pen (the gradient of a negative distance instead of zeros)."""
         return self.batch.config_clearance_grad(dofs, q, pairs=pairs, distmax=distmax, **opts)
 
     def config_collision_cost(self, dofs, q, pairs=None, d_safe=0.05, **opts):

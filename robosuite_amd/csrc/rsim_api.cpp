@@ -87,6 +87,7 @@ extern "C" int rsim_launch_randomize(const DModel* m, const DBatch* b, const DDr
 #include "rsim_ray.h"
 #include "rsim_dist.h"
 #include "rsim_pen.h"
+#include "rsim_pen_query.h"
 #include "rsim_ik.h"
 #include "rsim_clear.h"
 #include "rsim_clear_core.h"
@@ -2692,7 +2693,11 @@ static int config_clearance(const char* who, rsim_batch* b, int ndof, const int3
     g.grad = grad_dev;
   }
   int e = rsim_launch_clear_fk(&a, b->stream);
-  if (!e) e = rsim_launch_clear_dist(&a, b->stream);
+  if (is_signed) {   // the pair loop of rsim_pen_query.hip in k_clear_dist's place; k_clear_min and the gradient kernels are the same
+    DPenClear ap;
+    ap.c = a; ap.pen_tol = po.pen_tol; ap.offset = po.offset; ap.pen_iters = po.pen_iters;
+    if (!e) e = rsim_launch_clear_dist_signed(&ap, b->stream);
+  } else if (!e) e = rsim_launch_clear_dist(&a, b->stream);
   if (want_grad && !e) e = rsim_launch_clear_joints(&g, b->stream);
   if (want_grad && !e) e = rsim_launch_clear_grad(&g, b->stream);
   return launched(who, e);
@@ -2743,26 +2748,53 @@ extern "C" int rsim_config_collision_cost_signed_attached(rsim_batch* b, int ndo
   return config_clearance(att && att->n ? "rsim_config_collision_cost_signed_attached" : "rsim_config_collision_cost_signed", b, ndof, dof_ids, k, q_dev, npair, pairs,
                           d_safe, opts, cost_dev, nnear_dev, nullptr, noverlap_dev, att, false, grad_dev, true, true, pen);
 }
+// ---- signed distances in the clearance and its gradient (rsim_pen_query.hip, include/rsim.h rsim_config_clearance_signed / rsim_config_clearance_grad_signed)
+extern "C" int rsim_config_clearance_signed(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, int npair, const int32_t* pairs, float distmax,
+                                            const rsim_clear_opts* opts, const rsim_pen_opts* pen, float* dist_dev, int32_t* pair_dev, float* fromto_dev,
+                                            int32_t* status_dev) {
+  return config_clearance("rsim_config_clearance_signed", b, ndof, dof_ids, k, q_dev, npair, pairs, distmax, opts, dist_dev, pair_dev, fromto_dev, status_dev, nullptr,
+                          false, nullptr, false, true, pen);
+}
+extern "C" int rsim_config_clearance_signed_attached(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, int npair, const int32_t* pairs,
+                                                     float distmax, const rsim_clear_opts* opts, const rsim_pen_opts* pen, float* dist_dev, int32_t* pair_dev,
+                                                     float* fromto_dev, int32_t* status_dev, const rsim_attach* att) {
+  return config_clearance(att && att->n ? "rsim_config_clearance_signed_attached" : "rsim_config_clearance_signed", b, ndof, dof_ids, k, q_dev, npair, pairs, distmax,
+                          opts, dist_dev, pair_dev, fromto_dev, status_dev, att, false, nullptr, false, true, pen);
+}
+extern "C" int rsim_config_clearance_grad_signed(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, int npair, const int32_t* pairs,
+                                                 float distmax, const rsim_clear_opts* opts, const rsim_pen_opts* pen, float* dist_dev, int32_t* pair_dev,
+                                                 float* fromto_dev, int32_t* status_dev, float* grad_dev) {
+  return config_clearance("rsim_config_clearance_grad_signed", b, ndof, dof_ids, k, q_dev, npair, pairs, distmax, opts, dist_dev, pair_dev, fromto_dev, status_dev,
+                          nullptr, true, grad_dev, false, true, pen);
+}
+extern "C" int rsim_config_clearance_grad_signed_attached(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, int npair, const int32_t* pairs,
+                                                          float distmax, const rsim_clear_opts* opts, const rsim_pen_opts* pen, float* dist_dev, int32_t* pair_dev,
+                                                          float* fromto_dev, int32_t* status_dev, float* grad_dev, const rsim_attach* att) {
+  return config_clearance(att && att->n ? "rsim_config_clearance_grad_signed_attached" : "rsim_config_clearance_grad_signed", b, ndof, dof_ids, k, q_dev, npair, pairs,
+                          distmax, opts, dist_dev, pair_dev, fromto_dev, status_dev, att, true, grad_dev, false, true, pen);
+}
 
 // ---- collision-aware inverse kinematics (rsim_ik_avoid.hip, include/rsim.h rsim_ik_site_avoid): rsim_ik_site's path rules and chain head, the collision cost's plan,
 // tables, scratch and chunking, and a chain of two launches per evaluation
-static int ika_path(rsim_batch* b, int site, int ndof, const int32_t* dofs, const int** head) {
+static int ika_path(rsim_batch* b, const char* who, int site, int ndof, const int32_t* dofs, const int** head) {
   int nel = 0;
   if (!ik_chain(b, site, ndof, dofs, head, &nel)) return 0;
   const char from[] = "rsim_ik_site:";   // the path rules are rsim_ik_site's, and so are their words: only the entry's name differs
   if (!strncmp(g_err, from, sizeof(from) - 1)) {
     const std::string rest(g_err + sizeof(from) - 1);
-    snprintf(g_err, sizeof(g_err), "rsim_ik_site_avoid:%s", rest.c_str());
+    snprintf(g_err, sizeof(g_err), "%s:%s", who, rest.c_str());
   }
   return 1;
 }
 extern "C" int rsim_ik_avoid_tables(const rsim_batch* b) { return b ? (int)b->ika_keys.size() : 0; }
-extern "C" int rsim_ik_site_avoid(rsim_batch* b, int site, int ndof, const int32_t* dof_ids, int k, const float* target_pos_dev, const float* target_quat_dev,
-                                  const float* q_init_dev, int npair, const int32_t* pairs, const rsim_ik_avoid_opts* opts, const rsim_clear_opts* copts,
-                                  const rsim_attach* att, float* q_out_dev, float* err_dev, int32_t* iters_dev, float* cost_dev, int32_t* nnear_dev,
-                                  int32_t* noverlap_dev) {
-  const char* who = "rsim_ik_site_avoid";
+// is_signed: every evaluation's cost kernel is rsim_pen_query.hip's (rsim_ik_site_avoid_signed); the refusals keep the entry's own name
+static int ik_site_avoid(const char* who, rsim_batch* b, int site, int ndof, const int32_t* dof_ids, int k, const float* target_pos_dev, const float* target_quat_dev,
+                         const float* q_init_dev, int npair, const int32_t* pairs, const rsim_ik_avoid_opts* opts, const rsim_clear_opts* copts,
+                         const rsim_attach* att, float* q_out_dev, float* err_dev, int32_t* iters_dev, float* cost_dev, int32_t* nnear_dev,
+                         int32_t* noverlap_dev, bool is_signed, const rsim_pen_opts* pen) {
   if (!b) return fail("%s: batch is NULL", who);
+  rsim_pen_opts po;
+  if (is_signed && pen_options(who, pen, &po)) return 1;
   if (ndof < 1 || ndof > RSIM_JNT_MAX) return fail("%s: ndof %d outside 1..%d", who, ndof, RSIM_JNT_MAX);
   if (!dof_ids) return fail("%s: dof_ids is NULL", who);
   if (k < 1) return fail("%s: k %d < 1", who, k);
@@ -2790,7 +2822,7 @@ extern "C" int rsim_ik_site_avoid(rsim_batch* b, int site, int ndof, const int32
   HIPCHK(hipSetDevice(b->device));
   DIkAvoid a;
   memset(&a, 0, sizeof(a));
-  if (ika_path(b, site, ndof, dof_ids, &a.head)) return 1;   // (refusals come before anything is launched)
+  if (ika_path(b, who, site, ndof, dof_ids, &a.head)) return 1;   // (refusals come before anything is launched)
   DClear c;
   const ClearTab* tab;
   if (clear_args(b, who, ndof, dof_ids, k, q_out_dev, att, &c, &tab)) return 1;   // Cand::q IS q_out
@@ -2825,12 +2857,14 @@ extern "C" int rsim_ik_site_avoid(rsim_batch* b, int site, int ndof, const int32
   std::vector<int> key(1, site);
   key.insert(key.end(), dof_ids, dof_ids + ndof);
   b->ika_keys[key]++;
+  DPenIka as;
+  if (is_signed) { as.a = a; as.pen_tol = po.pen_tol; as.offset = po.offset; as.pen_iters = po.pen_iters; }
   int e = rsim_launch_ika_init(&a, b->stream);
   // max_iters + 1 evaluations, the last of which never updates; check_every = c > 0: after every c of them one word says whether any problem still runs
   for (int done = 0; !e && done <= o.max_iters;) {
     const int block = o.check_every > 0 ? std::min(o.check_every, o.max_iters + 1 - done) : o.max_iters + 1;
     if (o.check_every > 0) HIPCHK(hipMemsetAsync(a.any, 0, sizeof(int), b->stream));
-    for (int i = 0; i < block && !e; i++) e = rsim_launch_ika_iter(&a, b->stream);
+    for (int i = 0; i < block && !e; i++) e = is_signed ? rsim_launch_ika_iter_signed(&as, b->stream) : rsim_launch_ika_iter(&a, b->stream);
     done += block;
     if (!e && o.check_every > 0 && done <= o.max_iters) {
       int any = 0;
@@ -2840,6 +2874,20 @@ extern "C" int rsim_ik_site_avoid(rsim_batch* b, int site, int ndof, const int32
     }
   }
   return launched(who, e);
+}
+extern "C" int rsim_ik_site_avoid(rsim_batch* b, int site, int ndof, const int32_t* dof_ids, int k, const float* target_pos_dev, const float* target_quat_dev,
+                                  const float* q_init_dev, int npair, const int32_t* pairs, const rsim_ik_avoid_opts* opts, const rsim_clear_opts* copts,
+                                  const rsim_attach* att, float* q_out_dev, float* err_dev, int32_t* iters_dev, float* cost_dev, int32_t* nnear_dev,
+                                  int32_t* noverlap_dev) {
+  return ik_site_avoid("rsim_ik_site_avoid", b, site, ndof, dof_ids, k, target_pos_dev, target_quat_dev, q_init_dev, npair, pairs, opts, copts, att, q_out_dev, err_dev,
+                       iters_dev, cost_dev, nnear_dev, noverlap_dev, false, nullptr);
+}
+extern "C" int rsim_ik_site_avoid_signed(rsim_batch* b, int site, int ndof, const int32_t* dof_ids, int k, const float* target_pos_dev, const float* target_quat_dev,
+                                         const float* q_init_dev, int npair, const int32_t* pairs, const rsim_ik_avoid_opts* opts, const rsim_clear_opts* copts,
+                                         const rsim_pen_opts* pen, const rsim_attach* att, float* q_out_dev, float* err_dev, int32_t* iters_dev, float* cost_dev,
+                                         int32_t* nnear_dev, int32_t* noverlap_dev) {
+  return ik_site_avoid("rsim_ik_site_avoid_signed", b, site, ndof, dof_ids, k, target_pos_dev, target_quat_dev, q_init_dev, npair, pairs, opts, copts, att, q_out_dev,
+                       err_dev, iters_dev, cost_dev, nnear_dev, noverlap_dev, true, pen);
 }
 
 // ---- swept clearance (rsim_sweep.hip, include/rsim.h rsim_config_sweep / rsim_config_motion_bound) -----------------------------------------------------------

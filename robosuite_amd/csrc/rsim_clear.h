@@ -44,3 +44,5 @@ struct DClear {
 
 extern "C" int rsim_launch_clear_fk(const DClear* a, hipStream_t stream);
 extern "C" int rsim_launch_clear_dist(const DClear* a, hipStream_t stream);
+// k_clear_min alone, behind a pair loop that another code object ran (rsim_pen_query.hip k_clear_dist_signed); nothing with chunks <= 1
+extern "C" int rsim_launch_clear_min(const DClear* a, hipStream_t stream);

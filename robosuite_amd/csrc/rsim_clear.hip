@@ -136,3 +136,10 @@ extern "C" int rsim_launch_clear_dist(const DClear* a, hipStream_t stream) {
   hipLaunchKernelGGL(k_clear_min, dim3(waves), dim3(RSIM_CLEAR_LANES), 0, stream, *a);
   return (int)hipGetLastError();
 }
+
+// k_clear_min alone, behind a pair loop that another code object ran (rsim_pen_query.hip k_clear_dist_signed); nothing with chunks <= 1
+extern "C" int rsim_launch_clear_min(const DClear* a, hipStream_t stream) {
+  if (a->NC <= 0 || a->npair <= 0 || a->chunks <= 1) return 0;
+  hipLaunchKernelGGL(k_clear_min, dim3((a->NC + RSIM_CLEAR_LANES - 1) / RSIM_CLEAR_LANES), dim3(RSIM_CLEAR_LANES), 0, stream, *a);
+  return (int)hipGetLastError();
+}

@@ -24,3 +24,5 @@ struct DIkAvoid {
 
 extern "C" int rsim_launch_ika_init(const DIkAvoid* a, hipStream_t stream);
 extern "C" int rsim_launch_ika_iter(const DIkAvoid* a, hipStream_t stream);   // one evaluation: k_ika_cost, k_ika_step
+// k_ika_step alone, behind a cost kernel that another code object ran (rsim_pen_query.hip k_ika_cost_signed)
+extern "C" int rsim_launch_ika_step(const DIkAvoid* a, hipStream_t stream);

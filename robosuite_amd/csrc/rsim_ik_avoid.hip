@@ -158,3 +158,10 @@ extern "C" int rsim_launch_ika_iter(const DIkAvoid* a, hipStream_t stream) {
   hipLaunchKernelGGL(a->g.c.natt > 0 ? k_ika_step_att : k_ika_step, dim3(waves), dim3(RSIM_CLEAR_LANES), 0, stream, *a);
   return (int)hipGetLastError();
 }
+
+// k_ika_step (_att) alone, behind a cost kernel that another code object ran (rsim_pen_query.hip k_ika_cost_signed)
+extern "C" int rsim_launch_ika_step(const DIkAvoid* a, hipStream_t stream) {
+  if (a->g.c.NC <= 0 || a->g.c.npair <= 0 || a->g.c.chunks <= 0) return 0;
+  hipLaunchKernelGGL(a->g.c.natt > 0 ? k_ika_step_att : k_ika_step, dim3((a->g.c.NC + RSIM_CLEAR_LANES - 1) / RSIM_CLEAR_LANES), dim3(RSIM_CLEAR_LANES), 0, stream, *a);
+  return (int)hipGetLastError();
+}

@@ -13,8 +13,7 @@
 #include <hip/hip_runtime.h>
 #include "../../include/rsim.h"
 #include "rsim_pen.h"
-#include "rsim_pen_core.h"
-#include "rsim_grad_core.h"
+#include "rsim_pen_clear_core.h"
 
 using namespace rsim_grad;
 static_assert(DIST_PEN_CAP == RSIM_DIST_PEN_CAP, "rsim_pen_core.h DIST_PEN_CAP is include/rsim.h RSIM_DIST_PEN_CAP");
@@ -55,41 +54,7 @@ __device__ __forceinline__ JointStore joints(const DGrad& a, int c) {
   return s;
 }
 
-// rsim_grad_core.h cost_pairs with pair_signed as the pair routine; noverlap is dist < 0
-template <bool ATT, class GeomRec>
-__device__ __forceinline__ Cost cost_pairs_signed(const Scene<GeomRec>& sc, int p0, int p1, const Cand& c, const PoseStore& st, const JointStore& js, int n,
-                                                  unsigned slide_mask, float d_safe, float tol, int max_iters, const PenOpts& po, const Att& at, const int* sig,
-                                                  const int* body_att, const GradAcc& ga) {
-  Cost acc;
-  acc.cost = 0.f; acc.nnear = acc.nover = 0;
-  for (int col = 0; col < n; col++) ga.g[col * ga.gs] = 0.f;
-  for (int p = p0; p < p1; p++) {
-    const int* rec = sc.pairs + (size_t)p * sc.rec;
-    const int g1 = RSIM_CLEAR_U(rec[0]), g2 = RSIM_CLEAR_U(rec[1]);
-    const int b1 = RSIM_CLEAR_U(sc.geom[g1].body), b2 = RSIM_CLEAR_U(sc.geom[g2].body);
-    if (ATT && !pair_active(at, b1, b2)) continue;
-    Geom A = load_geom(sc, g1, c, st, RSIM_CLEAR_U(rec[2]), RSIM_CLEAR_U(rec[3]));
-    Geom Bg = load_geom(sc, g2, c, st, RSIM_CLEAR_U(rec[4]), RSIM_CLEAR_U(rec[5]));
-    const V3 org = A.p;
-    A.p = v3(0, 0, 0); Bg.p = Bg.p - org;
-    const Result r = pair_signed(A, Bg, d_safe, tol, max_iters, po);
-    if ((r.status & DIST_FAR) != 0 || !(r.dist < d_safe)) continue;
-    const float w = d_safe - r.dist;
-    acc.cost += 0.5f * w * w;
-    acc.nnear++;
-    acc.nover += r.dist < 0.f ? 1 : 0;
-    const V3 q1 = r.p1 + org, q2 = r.p2 + org;
-    V3 dir;
-    if (!grad_dir(r.dist, p, r.status, q1, q2, dir)) continue;
-    const unsigned w1 = (unsigned)RSIM_CLEAR_U(sig[b1]), w2 = (unsigned)RSIM_CLEAR_U(sig[b2]);
-    const unsigned s1 = sig_pick(w1, ATT && body_att ? RSIM_CLEAR_U(body_att[b1]) : -1, at.held);
-    const unsigned s2 = sig_pick(w2, ATT && body_att ? RSIM_CLEAR_U(body_att[b2]) : -1, at.held);
-    for (int col = 0; col < n; col++)
-      if (((s1 ^ s2) >> col) & 1u) ga.g[col * ga.gs] -= w * col_grad(js, col, (slide_mask >> col) & 1u, dir, q1, q2, s1, s2);
-  }
-  return acc;
-}
-
+// the cost loop itself, cost_pairs_signed, is rsim_pen_clear_core.h
 template <bool ATT>
 __device__ __forceinline__ void cost_signed_lane(const DPenCost& ap) {
   const DGrad& a = ap.g;

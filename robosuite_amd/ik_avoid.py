@@ -16,7 +16,10 @@ inverse).  Every term of the cost is at most the cost, so cost <= 1/2 (d_safe - 
 cost_tol = 1/2 (d_safe / 2)^2 proves d_free = d_safe / 2 and excludes an overlapping pair (which adds 1/2 d_safe^2).  cost_tol = inf: never wait for the cost.
 A finished problem is frozen.  With avoid_gain = 0 and cost_tol = inf this is ik.solve, exactly.
 
-Limits.  A pair that starts in a general convex overlap (status 2) adds cost and no push: hand in several start vectors.  A listed pair that stays inside
+signed=True (rsim_ik_site_avoid_signed): the cost of every evaluation is clearance.collision_cost(signed=True, pen=pen) -- an overlapping pair has a depth and a
+normal, so it pushes, and noverlap counts dist < 0.
+
+Limits.  Without signed, a pair that starts in a general convex overlap (status 2) adds cost and no push: pass signed=True, or hand in several start vectors.  A listed pair that stays inside
 d_safe whatever the arm does (the Panda's link0 / link1 geoms, 1 mm apart) never lets a problem finish: hand in the list without parent / child pairs.  A
 6-dof arm with a pose target has no null space to use."""
 import numpy as np
@@ -62,11 +65,12 @@ def step(P, q, q_rest, e, J, g, o, rows):
 
 
 def solve(flat, qpos, site, dofs, pos, quat=None, q_init=None, pairs=None, overrides=None, params=None, attach=None, held=None, rel=None,
-          tol=distance.DEFAULTS["tol"], dist_max_iters=distance.DEFAULTS["max_iters"], trace=None, **opts):
+          tol=distance.DEFAULTS["tol"], dist_max_iters=distance.DEFAULTS["max_iters"], trace=None, signed=False, pen=None, **opts):
     """One problem of one env -> (q [n], err [2] = |err_pos|, |w| at q, iters, converged, finished, cost, nnear, noverlap), everything AT q.  pairs=None:
     clearance.default_pairs; params / overrides: the env's geom arrays / FK tables; attach / held / rel: its carried objects.  trace: a list that receives
-    (q, e, J, cost, g) of every evaluation."""
+    (q, e, J, cost, g) of every evaluation.  signed / pen: clearance.collision_cost's."""
     o = options(**opts)
+    sg = dict(signed=True, pen=pen) if signed else {}      # (nothing is passed on without it: the unsigned call is what it was)
     P = ik.Problem(flat, qpos, site, dofs, overrides)
     p = clearance.default_pairs(flat, dofs, attach) if pairs is None else pairs
     m32 = clearance._model32(flat, overrides)
@@ -77,11 +81,12 @@ def solve(flat, qpos, site, dofs, pos, quat=None, q_init=None, pairs=None, overr
     while True:
         e, J = P.error(q, pos, quat)
         if pairs is None and attach is not None and len(attach):      # the default list: per env, only the pairs its held row makes candidate-dependent
-            cost, g, nnear, nover = clearance.collision_cost(flat, qpos, dofs, q, None, o["d_safe"], tol, dist_max_iters, params, overrides, attach=attach, held=held, rel=rel)
+            cost, g, nnear, nover = clearance.collision_cost(flat, qpos, dofs, q, None, o["d_safe"], tol, dist_max_iters, params, overrides, attach=attach, held=held, rel=rel,
+                                                             **sg)
         else:
             xp = clearance.fk(flat, qpos, dofs, q, model32=m32, attach=attach, held=held, rel=rel)
             cost, g, nnear, nover = clearance.collision_cost(flat, qpos, dofs, q, p, o["d_safe"], tol, dist_max_iters, params, overrides, poses=xp, attach=attach, held=held,
-                                                             rel=rel, frames=clearance.joint_frames(flat, qpos, dofs, q, model32=m32))
+                                                             rel=rel, frames=clearance.joint_frames(flat, qpos, dofs, q, model32=m32), **sg)
         if trace is not None:
             trace.append((q.copy(), e.copy(), J.copy(), cost, g.copy()))
         en, wn = float(np.linalg.norm(e[:3])), float(np.linalg.norm(e[3:]))
@@ -106,7 +111,7 @@ def held_to(flat, qpos, site, dofs, pos, quat=None, q_init=None, pairs=None, **k
 
 
 def update(flat, qpos, site, dofs, q, q_rest, pos, quat=None, pairs=None, g=None, overrides=None, params=None, attach=None, held=None, rel=None,
-           tol=distance.DEFAULTS["tol"], dist_max_iters=distance.DEFAULTS["max_iters"], **opts):
+           tol=distance.DEFAULTS["tol"], dist_max_iters=distance.DEFAULTS["max_iters"], signed=False, pen=None, **opts):
     """clamp(q + step): the iterate one update makes of q, whatever the stopping rule says.  g: the cost's gradient to use in place of the mirror's own (the
     device tests hand the device's gradient in, to hold the step arithmetic apart from the distance layer)."""
     o = options(**opts)
@@ -114,5 +119,6 @@ def update(flat, qpos, site, dofs, q, q_rest, pos, quat=None, pairs=None, g=None
     q, q_rest = np.asarray(q, dtype=np.float64), np.asarray(q_rest, dtype=np.float64)
     e, J = P.error(q, pos, quat)
     if g is None:
-        g = clearance.collision_cost(flat, qpos, dofs, q, pairs, o["d_safe"], tol, dist_max_iters, params, overrides, attach=attach, held=held, rel=rel)[1]
+        g = clearance.collision_cost(flat, qpos, dofs, q, pairs, o["d_safe"], tol, dist_max_iters, params, overrides, attach=attach, held=held, rel=rel,
+                                     **(dict(signed=True, pen=pen) if signed else {}))[1]
     return P.clamp(q + step(P, q, q_rest, e, J, g, o, 3 if quat is None else 6), o)

@@ -219,7 +219,7 @@ class VecEnv:
             raise ValueError(f"solve_ik: the controller description has no arm {arm}")
         return self.env.batch.solve_ik(site, dofs, pos, quat=quat, q_init=q_init, **opts)
 
-    def solve_ik_avoid(self, pos, quat=None, arm=0, q_init=None, pairs=None, d_safe=0.05, attach=None, held=None, rel=None, **opts):
+    def solve_ik_avoid(self, pos, quat=None, arm=0, q_init=None, pairs=None, d_safe=0.05, attach=None, held=None, rel=None, signed=False, pen=None, **opts):
         """Which arm joint positions put the gripper site at this pose AND stand clear of the scene?  solve_ik with the gradient of config_collision_cost as a
         secondary task in the null space of the pose task -> (q, err, iters, converged, finished, cost, nnear, noverlap) (HipBatch.solve_ik_avoid).  finished =
         converged and cost <= cost_tol, by default 1/2 (d_safe / 2)^2: every listed pair is then at least d_safe / 2 apart.  Site and dofs: as solve_ik; pairs,
@@ -227,6 +227,9 @@ class VecEnv:
 
             pairs = [p for p in env.batch.config_pairs(dofs) if not parent_child(p)]      # a pair that can never leave d_safe never lets a problem finish
             q, err, it, ok, free, cost, nnear, nover = env.solve_ik_avoid(pos, quat, pairs=pairs, q_init=starts)      # K > 1 starts: an overlap gives no push
+
+        signed=True: an overlapping pair enters every evaluation with its negative distance and pushes, so a start that touches or sits in an obstacle -- the
+        robot's current configuration, often -- moves out (HipBatch.solve_ik_avoid); pen: the descent's options.
         """
         from .backend import ctrl_desc
 
@@ -239,7 +242,7 @@ class VecEnv:
             raise ValueError(f"solve_ik_avoid: the controller description has no arm {arm}")
         ids = None if pairs is None else self._geom_ids(pairs)
         return self.env.batch.solve_ik_avoid(site, dofs, pos, quat=quat, q_init=q_init, pairs=ids, d_safe=d_safe,
-                                             attach=self._attach_ids("solve_ik_avoid", attach, arm), held=held, rel=rel, **opts)
+                                             attach=self._attach_ids("solve_ik_avoid", attach, arm), held=held, rel=rel, signed=signed, pen=pen, **opts)
 
     def _arm_dofs(self, who, arm):
         from .backend import ctrl_desc
@@ -290,7 +293,7 @@ class VecEnv:
         config_clearance."""
         return self.env.batch.config_fk(self._arm_dofs("config_fk", arm), q, attach=self._attach_ids("config_fk", attach, arm), held=held, rel=rel)
 
-    def config_clearance(self, q, arm=0, pairs=None, distmax=1.0, attach=None, held=None, rel=None, **opts):
+    def config_clearance(self, q, arm=0, pairs=None, distmax=1.0, attach=None, held=None, rel=None, signed=False, pen=None, **opts):
         """Is this arm configuration free, and by how much?  q [n_envs, K, n] (2-D for K = 1) candidate joint positions of the arm -> (dist, pair, fromto,
         status) per candidate: the smallest distance over `pairs`, the index into the list of the pair that attains it, its nearest points and its status
         (HipBatch.config_clearance: the status codes, the convex-hull and overlap rules).  pairs: a list of (geom, geom), names or model geom ids; None: the
@@ -307,19 +310,25 @@ class VecEnv:
         against the fingers that hold it and comes in against the table, the bin and the other arm (HipBatch.config_clearance):
 
             d, pair, ft, st = env.config_clearance(q, attach=[("cube_main", None)], held=grasped)
+
+        signed=True: a colliding candidate reports its deepest listed pair, dist < 0 with that pair's witnesses, instead of 0 with status 2: two colliding
+        candidates can be ranked (HipBatch.config_clearance); pen: the descent's options.
         """
         ids = None if pairs is None else self._geom_ids(pairs)
         return self.env.batch.config_clearance(self._arm_dofs("config_clearance", arm), q, pairs=ids, distmax=distmax,
-                                               attach=self._attach_ids("config_clearance", attach, arm), held=held, rel=rel, **opts)
+                                               attach=self._attach_ids("config_clearance", attach, arm), held=held, rel=rel, signed=signed, pen=pen, **opts)
 
-    def config_clearance_grad(self, q, arm=0, pairs=None, distmax=1.0, attach=None, held=None, rel=None, **opts):
+    def config_clearance_grad(self, q, arm=0, pairs=None, distmax=1.0, attach=None, held=None, rel=None, signed=False, pen=None, **opts):
         """Which way does this arm configuration move away from the scene?  config_clearance with one more result: -> (dist, pair, fromto, status, grad), grad
         [n_envs, K, n] the derivative of dist with respect to the arm's joints for the pair that attains the minimum (HipBatch.config_clearance_grad: the
         formula, the zero rules -- far, overlap, |dist| < 1e-7 -- and the two limits).  arm, pairs, attach / held / rel: as config_clearance.  A step of
-        q + step * grad raises the clearance of that pair; the gradient jumps where the nearest pair switches -- collision_cost does not."""
+        q + step * grad raises the clearance of that pair; the gradient jumps where the nearest pair switches -- collision_cost does not.  signed=True: a
+        colliding candidate has the gradient of its deepest pair's negative distance instead of zeros (HipBatch.config_clearance_grad); pen: the descent's
+        options."""
         ids = None if pairs is None else self._geom_ids(pairs)
         return self.env.batch.config_clearance_grad(self._arm_dofs("config_clearance_grad", arm), q, pairs=ids, distmax=distmax,
-                                                    attach=self._attach_ids("config_clearance_grad", attach, arm), held=held, rel=rel, **opts)
+                                                    attach=self._attach_ids("config_clearance_grad", attach, arm), held=held, rel=rel, signed=signed, pen=pen,
+                                                    **opts)
 
     def config_collision_cost(self, q, d_safe=0.05, arm=0, pairs=None, attach=None, held=None, rel=None, signed=False, pen=None, **opts):
         """The smooth collision cost of arm configurations and its gradient: -> (cost, grad, nnear, noverlap) (HipBatch.config_collision_cost): the sum of
