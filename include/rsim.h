@@ -879,6 +879,35 @@ int rsim_ik_site_avoid_signed(rsim_batch* b, int site, int ndof, const int32_t* 
                               const rsim_pen_opts* pen /* NULL: defaults */, const rsim_attach* att, float* q_out_dev, float* err_dev, int32_t* iters_dev,
                               float* cost_dev, int32_t* nnear_dev, int32_t* noverlap_dev);
 
+/* Dynamics at candidate configurations: "can the arm hold or execute this?" -- joint torques, the joint-space inertia and a site Jacobian at k candidate joint
+ * vectors per env, for the whole batch, on the device (csrc/rsim_dyn.hip; robosuite_amd/dynamics.py is the fp64 statement by the definition).
+ * Candidates, controlled dofs, refusals, the env's OWN float table (per_env_params overrides, domain-randomisation draws) and the pure-query rules are
+ * rsim_config_fk's, word for word: ndof is 1 .. RSIM_JNT_MAX dof ids of hinge or slide joints, which need not lie on one chain; every other joint is held at the
+ * env's current qpos; no range clamp; a batch that never asks allocates and launches nothing.
+ * In addition EVERY JOINT THAT IS NOT CONTROLLED HAS ZERO VELOCITY AND ZERO ACCELERATION.  With q~ the env's qpos with the controlled entries replaced, and qd~ /
+ * qdd~ zero but for the controlled entries:
+ *   rsim_config_inverse_dynamics   tau[c] = (M(q~) qdd~)[dof_c] + qfrc_bias(q~, qd~)[dof_c] + dof_damping[dof_c] * qd_c.  M includes dof_armature; qfrc_bias is
+ *               MuJoCo's: Coriolis, centrifugal and gravity, gravity from the env's own opt table.  qd_dev / qdd_dev may each be NULL (zeros): with both NULL the
+ *               result is the gravity torque.  Only moved bodies contribute -- held gripper bodies that ride on the arm are moved bodies.
+ *               NOT INCLUDED: tendon springs and dampers, fluid forces, friction loss, actuator, contact, equality and applied forces.  (Joint springs cannot
+ *               occur: rsim_batch_create refuses them.)
+ *   rsim_config_mass_matrix        the block of M(q~) on the controlled dofs, [B][k][ndof][ndof]: the inertia of the mechanism with all other joints locked.  Both
+ *               triangles are written and are equal bit for bit; two columns on different branches give exactly 0.
+ *   rsim_config_jacobian           mj_jacSite at the candidate in the controlled columns, [B][k][3][ndof] each (either output may be NULL, not both); the site is
+ *               placed from the env's own site_pos on its body's candidate pose.  A site on a body no controlled dof moves is valid and reads zeros.
+ * Kernels: behind the unchanged k_clear_fk and k_clear_joints, which leave the moved bodies' poses and the controlled joints' world axes and anchors, ONE kernel
+ * each, lane = candidate: k_dyn_rne (recursive Newton-Euler: a forward and a backward walk of the body table), k_dyn_crb (composite rigid bodies) and k_dyn_jac.
+ * Moments are taken about the candidate's position of the first moved body, not the world origin.  Per-body words live in a batch scratch grown on demand; a lane
+ * touches only its own words: no atomics, a repeat call is bit-identical.  Asynchronous on the batch's stream, DEVICE pointers in and out.
+ * Refused by name: what rsim_config_fk refuses, a NULL output, and for the Jacobian a site out of range.
+ * NOT CARRIED: the payload of carried objects (rsim_attach); free or ball joints as controlled dofs; body or point Jacobians other than sites; derivatives of
+ * the dynamics; forward dynamics at candidates; a torque-limit term inside IK or the fused step; tendon and fluid terms. */
+int rsim_config_inverse_dynamics(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev /* [B][k][ndof] */,
+                                 const float* qd_dev /* [B][k][ndof] or NULL: zeros */, const float* qdd_dev /* likewise */, float* tau_dev /* [B][k][ndof] */);
+int rsim_config_mass_matrix(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, float* M_dev /* [B][k][ndof][ndof] */);
+int rsim_config_jacobian(rsim_batch* b, int site, int ndof, const int32_t* dof_ids, int k, const float* q_dev,
+                         float* jacp_dev /* [B][k][3][ndof] or NULL */, float* jacr_dev /* likewise */);
+
 #ifdef __cplusplus
 }
 #endif

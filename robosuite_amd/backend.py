@@ -315,6 +315,10 @@ def lib():
             L.rsim_ik_site_avoid.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, vp, vp, vp, C.c_int, C.POINTER(C.c_int32), C.POINTER(IkAvoidOpts),
                                              C.POINTER(ClearOpts), C.POINTER(Attach), vp, vp, vp, vp, vp, vp]
             L.rsim_ik_avoid_tables.argtypes = [vp]
+        if hasattr(L, "rsim_config_inverse_dynamics"):     # (as above)
+            L.rsim_config_inverse_dynamics.argtypes = [vp, C.c_int, C.POINTER(C.c_int32), C.c_int, vp, vp, vp, vp]
+            L.rsim_config_mass_matrix.argtypes = [vp, C.c_int, C.POINTER(C.c_int32), C.c_int, vp, vp]
+            L.rsim_config_jacobian.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, vp, vp, vp]
         L.rsim_comm_unique_id.argtypes = [vp, C.c_size_t]
         L.rsim_comm_create.argtypes = [vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
         L.rsim_allreduce_stats.argtypes = [vp, vp, C.c_int, C.c_int]
@@ -1213,6 +1217,73 @@ class HipBatch:
             _chk(self._L.rsim_config_collision_cost(*args) if att is None else self._L.rsim_config_collision_cost_attached(*args, C.byref(att)))
         self._ray_fence_out()
         return tuple(t[:, 0] for t in (cost, grad, nnear, nover)) if flat2 else (cost, grad, nnear, nover)
+
+    # ---- dynamics at candidates (include/rsim.h rsim_config_inverse_dynamics / rsim_config_mass_matrix / rsim_config_jacobian, csrc/rsim_dyn.hip) -------
+    def _config_like(self, who, name, x, qc):
+        """qd / qdd of a dynamics call: None, or a CUDA float tensor on q's device and of q's shape -> contiguous float32 [B, K, n] or None"""
+        import torch
+
+        if x is None:
+            return None
+        if not (isinstance(x, torch.Tensor) and x.is_cuda):
+            raise RsimError(f"{who}: {name} must be a CUDA tensor or None")
+        if x.device != qc.device:
+            raise RsimError(f"{who}: {name} lives on {x.device}, q on {qc.device}")
+        B, K, n = qc.shape
+        if tuple(x.shape) != (B, K, n) and not (K == 1 and tuple(x.shape) == (B, n)):
+            raise RsimError(f"{who}: {name} must have q's shape {(B, K, n)}{f' (or {(B, n)})' if K == 1 else ''}, got {tuple(x.shape)}")
+        return x.contiguous().float().reshape(qc.shape)
+
+    def _dyn_head(self, who, dofs, q):
+        if not hasattr(self._L, "rsim_config_inverse_dynamics"):
+            raise RsimError(f"{who}: the loaded library has no rsim_{who}")
+        dofs, qc, K, flat2 = self._config_q(who, dofs, q)
+        return (len(dofs), (C.c_int32 * len(dofs))(*dofs), K, C.c_void_p(qc.data_ptr())), qc, K, flat2, len(dofs)
+
+    def config_inverse_dynamics(self, dofs, q, qd=None, qdd=None):
+        """Joint torques at candidate joint vectors, away from the state: q (and qd, qdd, each None for zeros) CUDA float32 [B, K, n] for the controlled `dofs`
+        as for config_fk, or [B, n] for K = 1.  Every other joint is held at the env's current qpos with ZERO velocity and acceleration.  -> tau float32
+        [B, K, n] ([B, n] for 2-D q):  tau_c = (M qdd)_c + qfrc_bias(q, qd)_c + dof_damping_c qd_c  -- M with dof_armature, qfrc_bias MuJoCo's Coriolis,
+        centrifugal and gravity terms, gravity and every inertial parameter from the env's own tables.  With qd = qdd = None: the gravity torque.  Held gripper
+        bodies that ride on the arm count.  NOT included: tendon springs and dampers, fluid forces, friction loss, actuator, contact, equality and applied
+        forces, the payload of carried objects.  A pure query on the batch's stream; robosuite_amd/dynamics.py is the fp64 statement by the definition."""
+        import torch
+
+        head, qc, K, flat2, n = self._dyn_head("config_inverse_dynamics", dofs, q)
+        v, a = self._config_like("config_inverse_dynamics", "qd", qd, qc), self._config_like("config_inverse_dynamics", "qdd", qdd, qc)
+        tau = torch.empty((self.B, K, n), dtype=torch.float32, device=qc.device)
+        self._ray_fence_in()
+        _chk(self._L.rsim_config_inverse_dynamics(self.ptr, *head, C.c_void_p(v.data_ptr()) if v is not None else None,
+                                                  C.c_void_p(a.data_ptr()) if a is not None else None, C.c_void_p(tau.data_ptr())))
+        self._ray_fence_out()
+        return tau[:, 0] if flat2 else tau
+
+    def config_mass_matrix(self, dofs, q):
+        """The joint-space inertia at candidate joint vectors: -> M float32 [B, K, n, n] ([B, n, n] for 2-D q), the block of M(q) on the controlled dofs with
+        dof_armature on the diagonal -- the inertia of the mechanism with every other joint locked.  Symmetric bit for bit; two dofs on different branches
+        (the two arms of a two-arm robot) give exactly 0.  Arguments and rules as config_inverse_dynamics."""
+        import torch
+
+        head, qc, K, flat2, n = self._dyn_head("config_mass_matrix", dofs, q)
+        M = torch.empty((self.B, K, n, n), dtype=torch.float32, device=qc.device)
+        self._ray_fence_in()
+        _chk(self._L.rsim_config_mass_matrix(self.ptr, *head, C.c_void_p(M.data_ptr())))
+        self._ray_fence_out()
+        return M[:, 0] if flat2 else M
+
+    def config_jacobian(self, site, dofs, q):
+        """mj_jacSite at candidate joint vectors, in the controlled columns: -> (jacp, jacr) float32 [B, K, 3, n] each ([B, 3, n] for 2-D q).  The site is placed
+        from the env's own site_pos on its body's candidate pose; a site on a body no controlled dof moves reads zeros.  Arguments and rules as
+        config_inverse_dynamics."""
+        import torch
+
+        head, qc, K, flat2, n = self._dyn_head("config_jacobian", dofs, q)
+        jp = torch.empty((self.B, K, 3, n), dtype=torch.float32, device=qc.device)
+        jr = torch.empty((self.B, K, 3, n), dtype=torch.float32, device=qc.device)
+        self._ray_fence_in()
+        _chk(self._L.rsim_config_jacobian(self.ptr, int(site), *head, C.c_void_p(jp.data_ptr()), C.c_void_p(jr.data_ptr())))
+        self._ray_fence_out()
+        return (jp[:, 0], jr[:, 0]) if flat2 else (jp, jr)
 
     # ---- collision-aware inverse kinematics (include/rsim.h rsim_ik_site_avoid, csrc/rsim_ik_avoid.hip) ---------------------------------------------------
     def ik_avoid_tables(self):

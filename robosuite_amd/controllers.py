@@ -123,6 +123,21 @@ class BatchState:
         """The motion bound L config_sweep uses for these segments (HipBatch.config_motion_bound)."""
         return self.batch.config_motion_bound(dofs, q0, q1, pairs=pairs, attach=attach, held=held, rel=rel)
 
+    def config_inverse_dynamics(self, dofs, q, qd=None, qdd=None):
+        """Joint torques of `dofs` at candidate joint vectors, velocities and accelerations, away from the state (HipBatch.config_inverse_dynamics): -> tau.
+        Every other joint is held where it is, at rest.  Valid between step1 and step2."""
+        return self.batch.config_inverse_dynamics(dofs, q, qd=qd, qdd=qdd)
+
+    def config_mass_matrix(self, dofs, q):
+        """The joint-space inertia on `dofs` at candidate joint vectors, away from the state (HipBatch.config_mass_matrix): -> M [B, K, n, n].  `mass_matrix`
+        is the current state's."""
+        return self.batch.config_mass_matrix(dofs, q)
+
+    def config_jacobian(self, site, dofs, q):
+        """mj_jacSite of `site` in the columns of `dofs` at candidate joint vectors, away from the state (HipBatch.config_jacobian): -> (jacp, jacr)
+        [B, K, 3, n].  `site_jacobian` is the current state's."""
+        return self.batch.config_jacobian(site, dofs, q)
+
     def body_dofs(self, body: int):
         """bool [nv]: the dofs that move `body` (its own joints and those of its ancestors)."""
         import torch

@@ -93,6 +93,8 @@ extern "C" int rsim_launch_randomize(const DModel* m, const DBatch* b, const DDr
 #include "rsim_clear_core.h"
 #include "rsim_grad.h"
 #include "rsim_ik_avoid.h"
+#include "rsim_dyn.h"
+#include "rsim_dyn_core.h"
 #include "rsim_sweep.h"
 #include "rsim_hull.h"
 
@@ -158,6 +160,8 @@ struct ClearTab {
   // the gradient and cost queries (rsim_grad.hip): every body's signature word on the host, on the device (d_sig) once one of them has asked; bit c of
   // slide_mask: controlled column c is a slide joint
   std::vector<int> sig_words; int* d_sig; unsigned slide_mask;
+  // the dynamics queries (rsim_dyn.hip): dof id and table element of every controlled column, on the device once one of them has asked
+  int* d_cols;
 };
 
 struct rsim_batch {
@@ -255,6 +259,9 @@ struct rsim_batch {
   float *d_grad_jscr, *d_grad_part;
   size_t grad_jscr_n, grad_part_n;
   int grad_tabs;                      // signature tables uploaded (rsim_config_grad_tables)
+  // dynamics queries (rsim_dyn.hip): the per-body words of the two walks, grown on demand by the first call that asks
+  float* d_dyn_scr;
+  size_t dyn_scr_n;
   // collision-aware IK (rsim_ik_avoid.hip): the problems' state (clamped start vectors, done flags, the `any` word), grown on demand by the first call that asks
   float* d_ika_work;
   size_t ika_work_n;
@@ -1144,7 +1151,8 @@ extern "C" void rsim_batch_free(rsim_batch* b) {
   if (b->d_ray_rf) hipFree(b->d_ray_rf);
   for (auto& kv : b->ik_chains) hipFree(kv.second.first);
   for (auto& kv : b->dist_tables) hipFree(kv.second);
-  for (auto& kv : b->clear_tabs) { hipFree(kv.second.d_tab); hipFree(kv.second.d_slot); if (kv.second.d_att) hipFree(kv.second.d_att); if (kv.second.d_sig) hipFree(kv.second.d_sig); }
+  for (auto& kv : b->clear_tabs) { hipFree(kv.second.d_tab); hipFree(kv.second.d_slot); if (kv.second.d_att) hipFree(kv.second.d_att); if (kv.second.d_sig) hipFree(kv.second.d_sig); if (kv.second.d_cols) hipFree(kv.second.d_cols); }
+  if (b->d_dyn_scr) hipFree(b->d_dyn_scr);
   if (b->d_grad_jscr) hipFree(b->d_grad_jscr);
   if (b->d_grad_part) hipFree(b->d_grad_part);
   if (b->d_ika_work) hipFree(b->d_ika_work);
@@ -2516,7 +2524,7 @@ static int clear_table(rsim_batch* b, const char* who, int ndof, const int32_t* 
     if (clear_plan(b->m, who, ndof, dofs, natt, natt > 0 ? att->bodies : nullptr, &plan)) return 1;
     ClearTab t;
     t.d_tab = t.d_slot = t.d_att = nullptr; t.nel = plan.nel; t.nslot = plan.nslot; t.slot = plan.slot; t.natt = plan.natt;
-    t.d_sig = nullptr; t.slide_mask = plan.slide_mask;
+    t.d_sig = nullptr; t.slide_mask = plan.slide_mask; t.d_cols = nullptr;
     t.sig_words.resize((size_t)b->m->nbody);
     for (int i = 0; i < b->m->nbody; i++) t.sig_words[i] = (int)((plan.sig[i] & 0xffffu) | (plan.sig_held[i] << 16));
     std::vector<int> h;   // what the pair loop's skip rule reads: [nbody] both signatures in one word, [nbody] the attachment a body belongs to
@@ -2888,6 +2896,86 @@ extern "C" int rsim_ik_site_avoid_signed(rsim_batch* b, int site, int ndof, cons
                                          int32_t* nnear_dev, int32_t* noverlap_dev) {
   return ik_site_avoid("rsim_ik_site_avoid_signed", b, site, ndof, dof_ids, k, target_pos_dev, target_quat_dev, q_init_dev, npair, pairs, opts, copts, att, q_out_dev,
                        err_dev, iters_dev, cost_dev, nnear_dev, noverlap_dev, true, pen);
+}
+
+// ---- dynamics at candidates (rsim_dyn.hip, include/rsim.h rsim_config_inverse_dynamics / rsim_config_mass_matrix / rsim_config_jacobian): rsim_config_fk's
+// argument and refusals, the pose scratch and the joint store of the gradient entries, then one kernel of rsim_dyn.hip behind k_clear_fk and k_clear_joints
+static int dyn_args(rsim_batch* b, const char* who, int ndof, const int32_t* dof_ids, int k, const float* q_dev, int words, DDyn* d, const ClearTab** tab) {
+  DClear a;
+  if (clear_args(b, who, ndof, dof_ids, k, q_dev, nullptr, &a, tab)) return 1;
+  if (refresh_derived(b, RSIM_XPOS)) return 1;
+  const rsim_model* m = b->m;
+  if (clear_grow(b, &b->d_clear_scr, &b->clear_scr_n, (size_t)a.nslot * 7 * a.NC)) return 1;
+  a.scr = b->d_clear_scr;
+  memset(d, 0, sizeof(*d));
+  if (grad_args(b, *tab, a, &d->g)) return 1;
+  if (!(*tab)->d_cols) {   // which dof and which table element each controlled column is: from the plan of the dof list, once
+    ClearPlan plan;
+    if (clear_plan(m, who, ndof, dof_ids, 0, nullptr, &plan)) return 1;
+    std::vector<int> cols((size_t)RSIM_DYN_COL * ndof, -1);
+    for (int e = 0; e < plan.nel; e++) {
+      const int* el = plan.tab.data() + (size_t)RSIM_CLEAR_REC * e;
+      if (el[rsim_clear::CLE_KIND] == rsim_clear::CL_BODY || el[rsim_clear::CLE_KIND] == rsim_clear::CL_ATTACH || el[rsim_clear::CLE_COL] < 0) continue;
+      cols[(size_t)RSIM_DYN_COL * el[rsim_clear::CLE_COL]] = dof_ids[el[rsim_clear::CLE_COL]];
+      cols[(size_t)RSIM_DYN_COL * el[rsim_clear::CLE_COL] + 1] = e;
+    }
+    for (int c = 0; c < ndof; c++)
+      if (cols[(size_t)RSIM_DYN_COL * c] < 0) return fail("%s: controlled dof %d has no element in the body table", who, dof_ids[c]);
+    int* dc = nullptr;
+    if (dalloc(&dc, cols.size())) return 1;
+    if (hipMemcpy(dc, cols.data(), cols.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(dc); return fail("hipMemcpy of the column table failed"); }
+    const_cast<ClearTab*>(*tab)->d_cols = dc;   // (the table lives in the batch's map; no other entry reads this field)
+  }
+  d->cols = (*tab)->d_cols;
+  if (words > 0) {
+    if (clear_grow(b, &b->d_dyn_scr, &b->dyn_scr_n, (size_t)a.nslot * words * a.NC)) return 1;
+    d->dscr = b->d_dyn_scr;
+  }
+  d->fo_mass = m->fo[FO_body_mass]; d->fo_inertia = m->fo[FO_body_inertia]; d->fo_ipos = m->fo[FO_body_ipos]; d->fo_iquat = m->fo[FO_body_iquat];
+  d->fo_armature = m->fo[FO_dof_armature]; d->fo_damping = m->fo[FO_dof_damping]; d->fo_opt = m->fo[FO_opt];
+  return 0;
+}
+static int dyn_run(const char* who, rsim_batch* b, const DDyn& d, int (*launch)(const DDyn*, hipStream_t)) {
+  int e = rsim_launch_clear_fk(&d.g.c, b->stream);
+  if (!e) e = rsim_launch_clear_joints(&d.g, b->stream);
+  if (!e) e = launch(&d, b->stream);
+  return launched(who, e);
+}
+extern "C" int rsim_config_inverse_dynamics(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, const float* qd_dev, const float* qdd_dev,
+                                            float* tau_dev) {
+  const char* who = "rsim_config_inverse_dynamics";
+  if (!b) return fail("%s: batch is NULL", who);
+  if (!tau_dev) return fail("%s: tau_dev is NULL", who);
+  DDyn d;
+  const ClearTab* tab;
+  if (dyn_args(b, who, ndof, dof_ids, k, q_dev, RSIM_DYN_RNE_WORDS, &d, &tab)) return 1;
+  d.qd = qd_dev; d.qdd = qdd_dev; d.tau = tau_dev;
+  return dyn_run(who, b, d, rsim_launch_dyn_rne);
+}
+extern "C" int rsim_config_mass_matrix(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, float* M_dev) {
+  const char* who = "rsim_config_mass_matrix";
+  if (!b) return fail("%s: batch is NULL", who);
+  if (!M_dev) return fail("%s: M_dev is NULL", who);
+  DDyn d;
+  const ClearTab* tab;
+  if (dyn_args(b, who, ndof, dof_ids, k, q_dev, RSIM_DYN_CRB_WORDS, &d, &tab)) return 1;
+  d.M = M_dev;
+  return dyn_run(who, b, d, rsim_launch_dyn_crb);
+}
+extern "C" int rsim_config_jacobian(rsim_batch* b, int site, int ndof, const int32_t* dof_ids, int k, const float* q_dev, float* jacp_dev, float* jacr_dev) {
+  const char* who = "rsim_config_jacobian";
+  if (!b) return fail("%s: batch is NULL", who);
+  if (site < 0 || site >= b->m->nsite) return fail("%s: site %d out of range (%d sites)", who, site, b->m->nsite);
+  if (!jacp_dev && !jacr_dev) return fail("%s: jacp_dev and jacr_dev are both NULL", who);
+  const int body = b->m->I("site_bodyid")[site];
+  if (body < 0 || body >= b->m->nbody) return fail("%s: site %d names body %d of %d", who, site, body, b->m->nbody);
+  DDyn d;
+  const ClearTab* tab;
+  if (dyn_args(b, who, ndof, dof_ids, k, q_dev, 0, &d, &tab)) return 1;
+  d.site_body = body; d.site_slot = tab->slot[body]; d.o_site_pos = b->m->fo[FO_site_pos] + 3 * site;
+  d.site_sig = (unsigned)tab->sig_words[body] & 0xffffu;
+  d.jacp = jacp_dev; d.jacr = jacr_dev;
+  return dyn_run(who, b, d, rsim_launch_dyn_jac);
 }
 
 // ---- swept clearance (rsim_sweep.hip, include/rsim.h rsim_config_sweep / rsim_config_motion_bound) -----------------------------------------------------------

@@ -1,0 +1,158 @@
+"""Dynamics at candidate configurations: the fp64 host statement, BY THE DEFINITION, of the device routines (csrc/rsim_dyn.hip, include/rsim.h
+rsim_config_inverse_dynamics / rsim_config_mass_matrix / rsim_config_jacobian).
+
+The candidate: q~ is the env's qpos with the controlled entries replaced by q; qd~ and qdd~ are zero but for the controlled entries -- every joint that is not
+controlled is held, with zero velocity and zero acceleration.  Then
+
+    tau[c] = (M(q~) qdd~)[dof_c] + qfrc_bias(q~, qd~)[dof_c] + dof_damping[dof_c] qd_c
+           = sum over bodies of  Jp^T m (a - g) + Jr^T (I alpha + omega x I omega)   [dof_c]  +  dof_armature[dof_c] qdd_c  +  dof_damping[dof_c] qd_c
+
+with Jp / Jr the Jacobian of the body's centre of mass / orientation (mjcf.body_jacobian_np on mjcf.kinematics_np), omega = Jr qd~, a = Jp qdd~ + Jp' qd~ and
+alpha = Jr qdd~ + Jr' qd~, I the body's inertia about its centre of mass in the world frame.  The velocity-product terms come from differentiating the Jacobian's
+columns one by one: the axis of column j turns with the frame that carries it, a_j' = omega_j x a_j, its anchor moves with that frame, and the column of a hinge
+at the point c is a_j x (c - p_j).  No recursion over the tree carries a velocity, an acceleration or a force here: the kernels run recursive Newton-Euler and
+composite rigid bodies, the fp64 oracle its own RNE, and this file shares an algorithm with neither.  Bodies the controlled dofs do not move have zero columns
+and drop out by themselves.
+
+Not included, as on the device: tendon springs and dampers, fluid forces, friction loss, actuator, contact, equality and applied forces, the payload of carried
+objects.  Free and ball joints cannot be controlled (clearance._columns refuses them, in the device's words)."""
+from collections import OrderedDict
+
+import numpy as np
+
+from . import clearance, mjcf
+
+# every float table the definition reads: what the device holds in fp32 (per-env overrides replace the model's)
+FIELDS = ("body_pos", "body_quat", "body_ipos", "body_iquat", "body_mass", "body_inertia", "jnt_pos", "jnt_axis", "qpos0", "site_pos", "dof_armature",
+          "dof_damping", "gravity")
+
+
+def model32(flat, overrides=None):
+    """the model with every table in FIELDS rounded to float32 (overrides: {field: array} of one env) -- the model as the device sees it"""
+    m = mjcf.FlatModel()
+    m.arrays = OrderedDict(flat.arrays)
+    m.names = flat.names
+    for k in FIELDS:
+        src = overrides[k] if overrides is not None and k in overrides else flat.arrays[k]
+        m.arrays[k] = np.asarray(src, dtype=np.float64).astype(np.float32).astype(np.float64).reshape(np.asarray(flat.arrays[k]).shape)
+    return m
+
+
+def _model(flat, overrides, m32):
+    if m32 is not None:
+        return m32
+    if overrides is None:
+        return flat
+    m = mjcf.FlatModel()
+    m.arrays = OrderedDict(flat.arrays)
+    m.names = flat.names
+    for k, v in overrides.items():
+        m.arrays[k] = np.asarray(v, dtype=np.float64).reshape(np.asarray(flat.arrays[k]).shape)
+    return m
+
+
+def _full(flat, dofs, x):
+    out = np.zeros(int(flat.nv))
+    if x is not None:
+        out[np.asarray(dofs, dtype=int)] = np.asarray(x, dtype=np.float64).ravel()
+    return out
+
+
+def _column_rates(m, kin, col, v):
+    """{joint: (a_j', p_j')} for the controlled joints: the rate of the world axis and the velocity of the anchor of column j, both riding on the frame the
+    joint is applied in -- moved by the joints before it (those of the ancestors, and the earlier ones of its own body) and by nothing else"""
+    xpos, _, xmat, _, _, xanchor, xaxis = kin
+    jbody = np.repeat(np.arange(int(m.nbody)), clearance._I(m, "body_jntnum"))
+    dadr = clearance._I(m, "jnt_dofadr")
+    out = {}
+    for j in col:
+        jp, jr = mjcf.body_jacobian_np(m, xpos, xmat, xanchor, xaxis, int(jbody[j]), xanchor[j])
+        before = v.copy()
+        before[dadr[j] + 1:] = 0.0      # dof order is joint order: later joints of the body do not carry this one (the joint itself moves neither)
+        out[j] = (np.cross(jr @ before, xaxis[j]), jp @ before)
+    return out
+
+
+def inverse_dynamics(flat, qpos, dofs, q, qd=None, qdd=None, overrides=None, model32=None):
+    """tau [n] of one candidate.  qpos: the env's [nq]; q / qd / qdd: [n] of the controlled dofs (None: zeros)"""
+    m = _model(flat, overrides, model32)
+    col = clearance._columns(flat, dofs)
+    dofs = [int(d) for d in np.asarray(dofs).ravel()]
+    kin = mjcf.kinematics_np(m, clearance.candidate_qpos(flat, qpos, dofs, q))
+    xpos, _, xmat, xipos, ximat, xanchor, xaxis = kin
+    v, a = _full(flat, dofs, qd), _full(flat, dofs, qdd)
+    rates = _column_rates(m, kin, col, v) if np.any(v) else {}
+    jtype, dadr = clearance._I(m, "jnt_type"), clearance._I(m, "jnt_dofadr")
+    g = np.asarray(m.gravity, dtype=np.float64).ravel()
+    tau = np.zeros(int(flat.nv))
+    for b in range(1, int(m.nbody)):
+        jp, jr = mjcf.body_jacobian_np(m, xpos, xmat, xanchor, xaxis, b, xipos[b])
+        if not (np.any(jp[:, dofs]) or np.any(jr[:, dofs])):
+            continue      # not moved
+        omega, vc = jr @ v, jp @ v
+        acc, alpha = jp @ a, jr @ a
+        for j, (da, dp) in rates.items():      # Jp' qd~ and Jr' qd~, column by column
+            d = dadr[j]
+            if not (np.any(jp[:, d]) or np.any(jr[:, d])):
+                continue      # the column does not move this body
+            if jtype[j] == mjcf.JNT_SLIDE:
+                acc += da * v[d]
+            else:
+                acc += (np.cross(da, xipos[b] - xanchor[j]) + np.cross(xaxis[j], vc - dp)) * v[d]
+                alpha += da * v[d]
+        Iw = ximat[b] @ np.diag(m.body_inertia[b]) @ ximat[b].T
+        tau += jp.T @ (float(m.body_mass[b]) * (acc - g)) + jr.T @ (Iw @ alpha + np.cross(omega, Iw @ omega))
+    tau += np.asarray(m.dof_armature).ravel() * a + np.asarray(m.dof_damping).ravel() * v
+    return tau[dofs]
+
+
+def gravity_torque(flat, qpos, dofs, q, overrides=None, model32=None):
+    return inverse_dynamics(flat, qpos, dofs, q, None, None, overrides, model32)
+
+
+def mass_matrix(flat, qpos, dofs, q, overrides=None, model32=None):
+    """M [n, n]: the block of the joint-space inertia at the candidate on the controlled dofs, M = sum Jp^T m Jp + Jr^T I Jr + armature"""
+    m = _model(flat, overrides, model32)
+    clearance._columns(flat, dofs)
+    dofs = [int(d) for d in np.asarray(dofs).ravel()]
+    M, _ = mjcf.mass_matrix_np(m, clearance.candidate_qpos(flat, qpos, dofs, q))
+    return M[np.ix_(dofs, dofs)]
+
+
+def site_jacobian(flat, qpos, site, dofs, q, overrides=None, model32=None):
+    """(jacp [3, n], jacr [3, n]): mj_jacSite at the candidate in the controlled columns"""
+    m = _model(flat, overrides, model32)
+    clearance._columns(flat, dofs)
+    if not 0 <= int(site) < int(flat.nsite):
+        raise clearance.ClearanceError(f"dynamics: site {site} out of range ({int(flat.nsite)} sites)")
+    dofs = [int(d) for d in np.asarray(dofs).ravel()]
+    xpos, _, xmat, _, _, xanchor, xaxis = mjcf.kinematics_np(m, clearance.candidate_qpos(flat, qpos, dofs, q))
+    b = int(clearance._I(m, "site_bodyid")[int(site)])
+    p = xpos[b] + xmat[b] @ np.asarray(m.site_pos, dtype=np.float64).reshape(-1, 3)[int(site)]
+    jp, jr = mjcf.body_jacobian_np(m, xpos, xmat, xanchor, xaxis, b, p)
+    return jp[:, dofs], jr[:, dofs]
+
+
+def site_position(flat, qpos, site, dofs, q, overrides=None, model32=None):
+    m = _model(flat, overrides, model32)
+    dofs = [int(d) for d in np.asarray(dofs).ravel()]
+    xpos, _, xmat = mjcf.kinematics_np(m, clearance.candidate_qpos(flat, qpos, dofs, q))[:3]
+    b = int(clearance._I(m, "site_bodyid")[int(site)])
+    return xpos[b] + xmat[b] @ np.asarray(m.site_pos, dtype=np.float64).reshape(-1, 3)[int(site)]
+
+
+def potential_energy(flat, qpos, dofs, q, overrides=None, model32=None):
+    """- sum m g . xipos at the candidate (its gradient along the controlled dofs is the gravity torque)"""
+    m = _model(flat, overrides, model32)
+    dofs = [int(d) for d in np.asarray(dofs).ravel()]
+    xipos = mjcf.kinematics_np(m, clearance.candidate_qpos(flat, qpos, dofs, q))[3]
+    return -float(np.asarray(m.body_mass).ravel() @ (xipos @ np.asarray(m.gravity, dtype=np.float64).ravel()))
+
+
+def path_derivatives(waypoints, dt):
+    """(qd, qdd) of waypoints [..., W, n] spaced dt apart: central differences, one-sided at the two ends (what VecEnv.path_torques forms in torch)"""
+    w = np.asarray(waypoints, dtype=np.float64)
+    if w.shape[-2] < 2:
+        return np.zeros_like(w), np.zeros_like(w)
+    qd = np.gradient(w, dt, axis=-2)
+    return qd, np.gradient(qd, dt, axis=-2)

@@ -382,6 +382,68 @@ class VecEnv:
         pick = lambda x: x.gather(2, seg[..., None])[..., 0]                        # noqa: E731
         return free, torch.where(free, torch.full_like(seg, -1), seg), pick(t), pick(dist), pick(pair)
 
+    def _arm_site(self, who, arm, site):
+        """site None: the arm's `eef_site` (arm 0 or 1); a name or a model site id otherwise"""
+        from .backend import ctrl_desc
+
+        if site is None:
+            d = ctrl_desc(self.env.cfg)
+            if arm == 0:
+                return int(d.eef_site)
+            if arm == 1 and d.narm == 2:
+                return int(d.eef_site2)
+            raise ValueError(f"{who}: site=None needs one arm's eef_site, got arm {arm!r}")
+        if isinstance(site, str):
+            names = self.env.model.flat.names["site"]
+            if site not in names:
+                raise KeyError(f"no site named {site!r}")
+            return names.index(site)
+        return int(site)
+
+    def config_inverse_dynamics(self, q, qd=None, qdd=None, arm=0):
+        """Can the arm hold or execute this?  q (and qd, qdd, each None for zeros) [n_envs, K, n] (2-D for K = 1) candidate joint positions, velocities and
+        accelerations of the arm -> tau [n_envs, K, n], the joint torques that produce qdd at (q, qd):  M qdd + Coriolis / centrifugal + gravity + joint
+        damping, M with the armature (HipBatch.config_inverse_dynamics).  Every joint that is not the arm's -- fingers, objects, the other arm -- is held
+        where it is, at rest; the hand and fingers ride along as load.  The simulation state is not touched.  arm: as config_fk.  With solve_ik:
+
+            q, err, it, ok = env.solve_ik(pos, quat)
+            holdable = ok & (env.config_gravity_torque(q).abs() <= limit).all(-1)
+
+        NOT included: tendon, fluid, friction loss, actuator, contact, equality and applied forces, and the payload of a grasped object."""
+        return self.env.batch.config_inverse_dynamics(self._arm_dofs("config_inverse_dynamics", arm), q, qd=qd, qdd=qdd)
+
+    def config_gravity_torque(self, q, arm=0):
+        """The torques that hold the arm still at q: config_inverse_dynamics at zero velocity and acceleration (JOINT_TORQUE feed-forward)."""
+        return self.config_inverse_dynamics(q, arm=arm)
+
+    def config_mass_matrix(self, q, arm=0):
+        """The joint-space inertia of the arm at candidate joint vectors -> M [n_envs, K, n, n] (HipBatch.config_mass_matrix): every other joint locked,
+        armature on the diagonal, symmetric bit for bit.  arm: as config_fk; with arm="both" the arm-to-arm blocks are exactly zero."""
+        return self.env.batch.config_mass_matrix(self._arm_dofs("config_mass_matrix", arm), q)
+
+    def config_jacobian(self, q, arm=0, site=None):
+        """mj_jacSite at candidate arm joint vectors -> (jacp, jacr) [n_envs, K, 3, n] in the arm's columns (HipBatch.config_jacobian).  site: a name or a
+        model site id; None: the arm's `eef_site`.  arm: as config_fk (site=None needs arm 0 or 1)."""
+        return self.env.batch.config_jacobian(self._arm_site("config_jacobian", arm, site), self._arm_dofs("config_jacobian", arm), q)
+
+    def path_torques(self, waypoints, dt, arm=0):
+        """The torques along joint-space paths: is the motion executable, not merely collision-free?  waypoints [n_envs, K, W, n]: K paths per env of W arm
+        joint vectors `dt` seconds apart -> tau [n_envs, K, W, n].  Velocities are central differences of the waypoints, one-sided at the two ends, and
+        accelerations the same differences of the velocities, formed in torch; then ONE config_inverse_dynamics call on the K W candidates.  Compare
+        tau.abs().amax(2) with the actuators' limits."""
+        import torch
+
+        if not (isinstance(waypoints, torch.Tensor) and waypoints.dim() == 4 and waypoints.shape[2] >= 2):
+            raise ValueError(f"path_torques: waypoints must be a tensor [n_envs, K, W, n] with W >= 2, got {tuple(getattr(waypoints, 'shape', ()))}")
+        if not dt > 0:
+            raise ValueError(f"path_torques: dt {dt!r} is not > 0")
+        B, K, W, n = waypoints.shape
+        w = waypoints.float()
+        qd = torch.gradient(w, spacing=float(dt), dim=2)[0]
+        qdd = torch.gradient(qd, spacing=float(dt), dim=2)[0]
+        flat = lambda x: x.reshape(B, K * W, n)      # noqa: E731
+        return self.config_inverse_dynamics(flat(w), qd=flat(qd), qdd=flat(qdd), arm=arm).reshape(B, K, W, n)
+
     def enable_applied_forces(self, on: bool = True):
         """Honour `qfrc_applied` and `xfrc_applied` in `step` (off by default: the control step then reads neither).  An env that reports `done`
         has both rows zeroed for its next episode, in the same step, so a force written after seeing `done` acts on the new episode."""
