@@ -901,12 +901,42 @@ int rsim_ik_site_avoid_signed(rsim_batch* b, int site, int ndof, const int32_t* 
  * touches only its own words: no atomics, a repeat call is bit-identical.  Asynchronous on the batch's stream, DEVICE pointers in and out.
  * Refused by name: what rsim_config_fk refuses, a NULL output, and for the Jacobian a site out of range.
  * NOT CARRIED: the payload of carried objects (rsim_attach); free or ball joints as controlled dofs; body or point Jacobians other than sites; derivatives of
- * the dynamics; forward dynamics at candidates; a torque-limit term inside IK or the fused step; tendon and fluid terms. */
+ * the dynamics; a torque-limit term inside IK or the fused step; tendon and fluid terms.  (Forward dynamics at candidates: rsim_config_forward_dynamics below.) */
 int rsim_config_inverse_dynamics(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev /* [B][k][ndof] */,
                                  const float* qd_dev /* [B][k][ndof] or NULL: zeros */, const float* qdd_dev /* likewise */, float* tau_dev /* [B][k][ndof] */);
 int rsim_config_mass_matrix(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, float* M_dev /* [B][k][ndof][ndof] */);
 int rsim_config_jacobian(rsim_batch* b, int site, int ndof, const int32_t* dof_ids, int k, const float* q_dev,
                          float* jacp_dev /* [B][k][3][ndof] or NULL */, float* jacr_dev /* likewise */);
+
+/* M^-1 at candidate configurations: "what acceleration does this torque give here, what is the end effector's apparent inertia here?" -- the other half of the
+ * dynamics queries above, on the device (csrc/rsim_dyn_solve.hip; robosuite_amd/dynamics.py forward_dynamics / mass_solve / opspace is the fp64 statement;
+ * DESIGN.md 5.3).  Candidates, controlled dofs, refusals, the env's OWN float table and the pure-query rules are rsim_config_fk's, word for word, as for
+ * rsim_config_mass_matrix; M below is that call's block: the inertia of the mechanism with every other joint locked, at zero velocity and acceleration.
+ *   rsim_config_forward_dynamics   qdd = M(q~)^-1 (tau - qfrc_bias(q~, qd~) - dof_damping qd), [B][k][ndof]: the bias and damping terms are exactly what
+ *               rsim_config_inverse_dynamics returns with qdd_dev NULL.  qd_dev / tau_dev may each be NULL (zeros).  The exact inverse of
+ *               rsim_config_inverse_dynamics, with its limits: NOT INCLUDED are tendon, fluid, friction-loss, actuator, contact, equality and applied forces.
+ *   rsim_config_mass_solve         x = M(q~)^-1 rhs for rhs [B][k][ndof][nrhs], 1 <= nrhs <= RSIM_JNT_MAX; x has rhs's shape.
+ *   rsim_config_opspace            with J = [jacp; jacr] of rsim_config_jacobian (6 x ndof): minv_jt = M^-1 J^T [B][k][ndof][6] and lambda_inv = J M^-1 J^T
+ *               [B][k][6][6].  Each unordered pair of lambda_inv is computed once and written to both triangles: symmetric bit for bit.  Either output may be
+ *               NULL, not both.  The operational-space inertia Lambda itself is NOT returned: lambda_inv is singular for ndof < 6 and at kinematic singularities,
+ *               and robosuite takes its pseudo-inverse -- Lambda = pinv(lambda_inv), Jbar = minv_jt Lambda are two lines for the caller.
+ * ok_dev, int32 [B][k] or NULL: 1 where every pivot of the Cholesky factorisation of M was finite and > 0.  Where it is 0 that candidate's outputs are NaN; no
+ * other candidate is affected.
+ * Kernels: the unchanged k_clear_fk, k_clear_joints, k_dyn_crb (and k_dyn_rne with qdd NULL, or k_dyn_jac), writing into batch scratches grown on demand, then
+ * ONE kernel k_dyn_solve, lane = candidate, one wavefront per workgroup: the lane's packed lower triangle and one right-hand-side column in dynamic LDS laid out
+ * [word][lane] ((ndof (ndof + 1) / 2 + ndof) * 256 B per workgroup), Cholesky in place, forward and back substitution per column.  A lane touches only its own
+ * words: no barrier, no atomics, a repeat call is bit-identical.  A block-diagonal M (two arms) factorises to a block-diagonal L exactly.  Asynchronous on the
+ * batch's stream, DEVICE pointers in and out.  A batch that never asks allocates and launches nothing.
+ * Refused by name: what rsim_config_fk refuses, a NULL output (for rsim_config_opspace: both NULL), nrhs out of range, a site out of range.
+ * NOT CARRIED: Lambda or pseudo-inverses; the payload of carried objects; free or ball joints as controlled dofs; constraint, contact or actuator forces in the
+ * acceleration; integrating candidates forward in time; derivatives. */
+int rsim_config_forward_dynamics(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev /* [B][k][ndof] */,
+                                 const float* qd_dev /* [B][k][ndof] or NULL: zeros */, const float* tau_dev /* likewise */, float* qdd_dev /* [B][k][ndof] */,
+                                 int32_t* ok_dev /* [B][k] or NULL */);
+int rsim_config_mass_solve(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, int nrhs, const float* rhs_dev /* [B][k][ndof][nrhs] */,
+                           float* x_dev /* [B][k][ndof][nrhs] */, int32_t* ok_dev /* [B][k] or NULL */);
+int rsim_config_opspace(rsim_batch* b, int site, int ndof, const int32_t* dof_ids, int k, const float* q_dev, float* lambda_inv_dev /* [B][k][6][6] or NULL */,
+                        float* minv_jt_dev /* [B][k][ndof][6] or NULL */, int32_t* ok_dev /* [B][k] or NULL */);
 
 #ifdef __cplusplus
 }

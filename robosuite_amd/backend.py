@@ -319,6 +319,10 @@ def lib():
             L.rsim_config_inverse_dynamics.argtypes = [vp, C.c_int, C.POINTER(C.c_int32), C.c_int, vp, vp, vp, vp]
             L.rsim_config_mass_matrix.argtypes = [vp, C.c_int, C.POINTER(C.c_int32), C.c_int, vp, vp]
             L.rsim_config_jacobian.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, vp, vp, vp]
+        if hasattr(L, "rsim_config_forward_dynamics"):     # (as above)
+            L.rsim_config_forward_dynamics.argtypes = [vp, C.c_int, C.POINTER(C.c_int32), C.c_int, vp, vp, vp, vp, vp]
+            L.rsim_config_mass_solve.argtypes = [vp, C.c_int, C.POINTER(C.c_int32), C.c_int, vp, C.c_int, vp, vp, vp]
+            L.rsim_config_opspace.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, vp, vp, vp, vp]
         L.rsim_comm_unique_id.argtypes = [vp, C.c_size_t]
         L.rsim_comm_create.argtypes = [vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
         L.rsim_allreduce_stats.argtypes = [vp, vp, C.c_int, C.c_int]
@@ -1284,6 +1288,78 @@ class HipBatch:
         _chk(self._L.rsim_config_jacobian(self.ptr, int(site), *head, C.c_void_p(jp.data_ptr()), C.c_void_p(jr.data_ptr())))
         self._ray_fence_out()
         return (jp[:, 0], jr[:, 0]) if flat2 else (jp, jr)
+
+    # ---- M^-1 at candidates (include/rsim.h rsim_config_forward_dynamics / rsim_config_mass_solve / rsim_config_opspace, csrc/rsim_dyn_solve.hip) --------
+    def _solve_head(self, who, dofs, q):
+        if not hasattr(self._L, "rsim_config_forward_dynamics"):
+            raise RsimError(f"{who}: the loaded library has no rsim_{who}")
+        return self._dyn_head(who, dofs, q)
+
+    def config_forward_dynamics(self, dofs, q, qd=None, tau=None, return_ok=False):
+        """Joint accelerations at candidate joint vectors, away from the state: -> qdd float32 [B, K, n] ([B, n] for 2-D q),
+        qdd = M(q)^-1 (tau - qfrc_bias(q, qd) - dof_damping qd), M config_mass_matrix's block -- every other joint locked, at zero velocity and acceleration --
+        and the bias and damping terms exactly what config_inverse_dynamics(q, qd) returns.  qd / tau: None for zeros.  The exact inverse of
+        config_inverse_dynamics, with its limits: no tendon, fluid, friction-loss, actuator, contact, equality or applied forces.  return_ok=True: ->
+        (qdd, ok bool [B, K]); ok is False where a Cholesky pivot of M was not finite and > 0, and that candidate's qdd is then NaN (no other candidate is
+        affected).  Arguments and rules as config_inverse_dynamics; robosuite_amd/dynamics.py forward_dynamics is the fp64 statement."""
+        import torch
+
+        head, qc, K, flat2, n = self._solve_head("config_forward_dynamics", dofs, q)
+        v, t = self._config_like("config_forward_dynamics", "qd", qd, qc), self._config_like("config_forward_dynamics", "tau", tau, qc)
+        qdd = torch.empty((self.B, K, n), dtype=torch.float32, device=qc.device)
+        ok = torch.empty((self.B, K), dtype=torch.int32, device=qc.device)
+        self._ray_fence_in()
+        _chk(self._L.rsim_config_forward_dynamics(self.ptr, *head, C.c_void_p(v.data_ptr()) if v is not None else None,
+                                                  C.c_void_p(t.data_ptr()) if t is not None else None, C.c_void_p(qdd.data_ptr()), C.c_void_p(ok.data_ptr())))
+        self._ray_fence_out()
+        qdd, ok = (qdd[:, 0], ok[:, 0] != 0) if flat2 else (qdd, ok != 0)
+        return (qdd, ok) if return_ok else qdd
+
+    def config_mass_solve(self, dofs, q, rhs, return_ok=False):
+        """x = M(q)^-1 rhs at candidate joint vectors: rhs CUDA float32 [B, K, n, r], 1 <= r <= 16 -> x of the same shape; rhs [B, K, n] is r = 1 and returns
+        [B, K, n].  With a 2-D q, rhs is [B, n, r] or [B, n].  M is config_mass_matrix's block.  return_ok: as config_forward_dynamics."""
+        import torch
+
+        who = "config_mass_solve"
+        head, qc, K, flat2, n = self._solve_head(who, dofs, q)
+        if not (isinstance(rhs, torch.Tensor) and rhs.is_cuda):
+            raise RsimError(f"{who}: rhs must be a CUDA tensor")
+        if rhs.device != qc.device:
+            raise RsimError(f"{who}: rhs lives on {rhs.device}, q on {qc.device}")
+        lead = (self.B, n) if flat2 else (self.B, K, n)
+        shape = tuple(rhs.shape)
+        if shape[:len(lead)] != lead or len(shape) - len(lead) > 1:
+            raise RsimError(f"{who}: rhs must have shape {lead} or {lead} + (r,), got {shape}")
+        vec = len(shape) == len(lead)
+        r = 1 if vec else shape[-1]
+        if not 1 <= r <= 16:
+            raise RsimError(f"{who}: nrhs {r} out of range (1..16)")
+        rc = rhs.contiguous().float().reshape(self.B, K, n, r)
+        x = torch.empty_like(rc)
+        ok = torch.empty((self.B, K), dtype=torch.int32, device=qc.device)
+        self._ray_fence_in()
+        _chk(self._L.rsim_config_mass_solve(self.ptr, *head, r, C.c_void_p(rc.data_ptr()), C.c_void_p(x.data_ptr()), C.c_void_p(ok.data_ptr())))
+        self._ray_fence_out()
+        x = x.reshape(shape)
+        ok = ok[:, 0] != 0 if flat2 else ok != 0
+        return (x, ok) if return_ok else x
+
+    def config_opspace(self, site, dofs, q, return_ok=False):
+        """The operational-space quantities of `site` at candidate joint vectors: -> (lambda_inv float32 [B, K, 6, 6], minv_jt float32 [B, K, n, 6]) (without the
+        K axis for 2-D q).  With J = [jacp; jacr] of config_jacobian and M of config_mass_matrix: minv_jt = M^-1 J^T, lambda_inv = J M^-1 J^T, symmetric bit for
+        bit.  The operational-space inertia itself is left to the caller, as robosuite does it: lambda_inv is singular for n < 6 and at kinematic singularities,
+        so Lambda = torch.linalg.pinv(lambda_inv), Jbar = minv_jt @ Lambda.  return_ok: as config_forward_dynamics."""
+        import torch
+
+        head, qc, K, flat2, n = self._solve_head("config_opspace", dofs, q)
+        lam = torch.empty((self.B, K, 6, 6), dtype=torch.float32, device=qc.device)
+        mjt = torch.empty((self.B, K, n, 6), dtype=torch.float32, device=qc.device)
+        ok = torch.empty((self.B, K), dtype=torch.int32, device=qc.device)
+        self._ray_fence_in()
+        _chk(self._L.rsim_config_opspace(self.ptr, int(site), *head, C.c_void_p(lam.data_ptr()), C.c_void_p(mjt.data_ptr()), C.c_void_p(ok.data_ptr())))
+        self._ray_fence_out()
+        lam, mjt, ok = (lam[:, 0], mjt[:, 0], ok[:, 0] != 0) if flat2 else (lam, mjt, ok != 0)
+        return (lam, mjt, ok) if return_ok else (lam, mjt)
 
     # ---- collision-aware inverse kinematics (include/rsim.h rsim_ik_site_avoid, csrc/rsim_ik_avoid.hip) ---------------------------------------------------
     def ik_avoid_tables(self):

@@ -138,6 +138,20 @@ class BatchState:
         [B, K, 3, n].  `site_jacobian` is the current state's."""
         return self.batch.config_jacobian(site, dofs, q)
 
+    def config_forward_dynamics(self, dofs, q, qd=None, tau=None, return_ok=False):
+        """Joint accelerations of `dofs` at candidate joint vectors, velocities and torques, away from the state (HipBatch.config_forward_dynamics): -> qdd
+        [B, K, n] = M^-1 (tau - bias - damping qd), the exact inverse of config_inverse_dynamics.  return_ok=True: -> (qdd, ok bool [B, K])."""
+        return self.batch.config_forward_dynamics(dofs, q, qd=qd, tau=tau, return_ok=return_ok)
+
+    def config_mass_solve(self, dofs, q, rhs, return_ok=False):
+        """M^-1 rhs on `dofs` at candidate joint vectors, away from the state (HipBatch.config_mass_solve): rhs [B, K, n, r] or [B, K, n] -> x of rhs's shape."""
+        return self.batch.config_mass_solve(dofs, q, rhs, return_ok=return_ok)
+
+    def config_opspace(self, site, dofs, q, return_ok=False):
+        """J M^-1 J^T and M^-1 J^T of `site` in the columns of `dofs` at candidate joint vectors, away from the state (HipBatch.config_opspace): ->
+        (lambda_inv [B, K, 6, 6], minv_jt [B, K, n, 6]).  Lambda = pinv(lambda_inv) is the caller's, as in TorchOSCPoseController.torques_from."""
+        return self.batch.config_opspace(site, dofs, q, return_ok=return_ok)
+
     def body_dofs(self, body: int):
         """bool [nv]: the dofs that move `body` (its own joints and those of its ancestors)."""
         import torch

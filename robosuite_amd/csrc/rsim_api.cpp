@@ -95,6 +95,7 @@ extern "C" int rsim_launch_randomize(const DModel* m, const DBatch* b, const DDr
 #include "rsim_ik_avoid.h"
 #include "rsim_dyn.h"
 #include "rsim_dyn_core.h"
+#include "rsim_dyn_solve.h"
 #include "rsim_sweep.h"
 #include "rsim_hull.h"
 
@@ -262,6 +263,10 @@ struct rsim_batch {
   // dynamics queries (rsim_dyn.hip): the per-body words of the two walks, grown on demand by the first call that asks
   float* d_dyn_scr;
   size_t dyn_scr_n;
+  // M^-1 queries (rsim_dyn_solve.hip): M [B K][n][n] and the bias torques or the site Jacobian, as k_dyn_crb / k_dyn_rne / k_dyn_jac leave them for k_dyn_solve,
+  // grown on demand by the first call that asks
+  float *d_solve_M, *d_solve_in;
+  size_t solve_M_n, solve_in_n;
   // collision-aware IK (rsim_ik_avoid.hip): the problems' state (clamped start vectors, done flags, the `any` word), grown on demand by the first call that asks
   float* d_ika_work;
   size_t ika_work_n;
@@ -1153,6 +1158,8 @@ extern "C" void rsim_batch_free(rsim_batch* b) {
   for (auto& kv : b->dist_tables) hipFree(kv.second);
   for (auto& kv : b->clear_tabs) { hipFree(kv.second.d_tab); hipFree(kv.second.d_slot); if (kv.second.d_att) hipFree(kv.second.d_att); if (kv.second.d_sig) hipFree(kv.second.d_sig); if (kv.second.d_cols) hipFree(kv.second.d_cols); }
   if (b->d_dyn_scr) hipFree(b->d_dyn_scr);
+  if (b->d_solve_M) hipFree(b->d_solve_M);
+  if (b->d_solve_in) hipFree(b->d_solve_in);
   if (b->d_grad_jscr) hipFree(b->d_grad_jscr);
   if (b->d_grad_part) hipFree(b->d_grad_part);
   if (b->d_ika_work) hipFree(b->d_ika_work);
@@ -2976,6 +2983,77 @@ extern "C" int rsim_config_jacobian(rsim_batch* b, int site, int ndof, const int
   d.site_sig = (unsigned)tab->sig_words[body] & 0xffffu;
   d.jacp = jacp_dev; d.jacr = jacr_dev;
   return dyn_run(who, b, d, rsim_launch_dyn_jac);
+}
+
+// ---- M^-1 at candidates (rsim_dyn_solve.hip, include/rsim.h rsim_config_forward_dynamics / rsim_config_mass_solve / rsim_config_opspace): dyn_args above, the
+// unchanged kernels of rsim_dyn.hip into batch scratches, then k_dyn_solve.  rne: k_dyn_rne (qdd null: the bias torques) in front of k_dyn_crb; jac: k_dyn_jac
+// behind it; either leaves in_words floats per candidate in the input scratch.  Both walks keep their per-body words in the one dynamics scratch, which dyn_args
+// has sized for the larger of the two the call runs: they run one after the other on the stream.
+static int solve_run(const char* who, rsim_batch* b, DDyn& d, DSolve& s, int in_words, bool rne, bool jac) {
+  const DClear& c = d.g.c;
+  if (clear_grow(b, &b->d_solve_M, &b->solve_M_n, (size_t)c.NC * c.n * c.n)) return 1;
+  if (in_words > 0 && clear_grow(b, &b->d_solve_in, &b->solve_in_n, (size_t)c.NC * in_words)) return 1;
+  d.M = b->d_solve_M;
+  s.NC = c.NC; s.n = c.n; s.M = b->d_solve_M;
+  int e = rsim_launch_clear_fk(&c, b->stream);
+  if (!e) e = rsim_launch_clear_joints(&d.g, b->stream);
+  if (!e && rne) {
+    d.qdd = nullptr; d.tau = b->d_solve_in; s.bias = b->d_solve_in;
+    e = rsim_launch_dyn_rne(&d, b->stream);
+  }
+  if (!e) e = rsim_launch_dyn_crb(&d, b->stream);
+  if (!e && jac) {
+    d.jacp = b->d_solve_in; d.jacr = b->d_solve_in + (size_t)c.NC * 3 * c.n; s.jacp = d.jacp; s.jacr = d.jacr;
+    e = rsim_launch_dyn_jac(&d, b->stream);
+  }
+  if (!e) e = rsim_launch_dyn_solve(&s, b->stream);
+  return launched(who, e);
+}
+extern "C" int rsim_config_forward_dynamics(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, const float* qd_dev, const float* tau_dev,
+                                            float* qdd_dev, int32_t* ok_dev) {
+  const char* who = "rsim_config_forward_dynamics";
+  if (!b) return fail("%s: batch is NULL", who);
+  if (!qdd_dev) return fail("%s: qdd_dev is NULL", who);
+  DDyn d;
+  const ClearTab* tab;
+  if (dyn_args(b, who, ndof, dof_ids, k, q_dev, RSIM_DYN_RNE_WORDS, &d, &tab)) return 1;
+  DSolve s;
+  memset(&s, 0, sizeof(s));
+  d.qd = qd_dev;
+  s.mode = RSIM_SOLVE_FD; s.tau = tau_dev; s.x = qdd_dev; s.ok = ok_dev;
+  return solve_run(who, b, d, s, ndof, true, false);
+}
+extern "C" int rsim_config_mass_solve(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, int nrhs, const float* rhs_dev, float* x_dev,
+                                      int32_t* ok_dev) {
+  const char* who = "rsim_config_mass_solve";
+  if (!b) return fail("%s: batch is NULL", who);
+  if (nrhs < 1 || nrhs > RSIM_JNT_MAX) return fail("%s: nrhs %d out of range (1..%d)", who, nrhs, RSIM_JNT_MAX);
+  if (!rhs_dev || !x_dev) return fail("%s: %s is NULL", who, !rhs_dev ? "rhs_dev" : "x_dev");
+  DDyn d;
+  const ClearTab* tab;
+  if (dyn_args(b, who, ndof, dof_ids, k, q_dev, RSIM_DYN_CRB_WORDS, &d, &tab)) return 1;
+  DSolve s;
+  memset(&s, 0, sizeof(s));
+  s.mode = RSIM_SOLVE_RHS; s.nrhs = nrhs; s.rhs = rhs_dev; s.x = x_dev; s.ok = ok_dev;
+  return solve_run(who, b, d, s, 0, false, false);
+}
+extern "C" int rsim_config_opspace(rsim_batch* b, int site, int ndof, const int32_t* dof_ids, int k, const float* q_dev, float* lambda_inv_dev, float* minv_jt_dev,
+                                   int32_t* ok_dev) {
+  const char* who = "rsim_config_opspace";
+  if (!b) return fail("%s: batch is NULL", who);
+  if (site < 0 || site >= b->m->nsite) return fail("%s: site %d out of range (%d sites)", who, site, b->m->nsite);
+  if (!lambda_inv_dev && !minv_jt_dev) return fail("%s: lambda_inv_dev and minv_jt_dev are both NULL", who);
+  const int body = b->m->I("site_bodyid")[site];
+  if (body < 0 || body >= b->m->nbody) return fail("%s: site %d names body %d of %d", who, site, body, b->m->nbody);
+  DDyn d;
+  const ClearTab* tab;
+  if (dyn_args(b, who, ndof, dof_ids, k, q_dev, RSIM_DYN_CRB_WORDS, &d, &tab)) return 1;
+  d.site_body = body; d.site_slot = tab->slot[body]; d.o_site_pos = b->m->fo[FO_site_pos] + 3 * site;
+  d.site_sig = (unsigned)tab->sig_words[body] & 0xffffu;
+  DSolve s;
+  memset(&s, 0, sizeof(s));
+  s.mode = RSIM_SOLVE_OPSPACE; s.x = minv_jt_dev; s.lambda_inv = lambda_inv_dev; s.ok = ok_dev;
+  return solve_run(who, b, d, s, 6 * ndof, false, true);
 }
 
 // ---- swept clearance (rsim_sweep.hip, include/rsim.h rsim_config_sweep / rsim_config_motion_bound) -----------------------------------------------------------

@@ -15,7 +15,10 @@ composite rigid bodies, the fp64 oracle its own RNE, and this file shares an alg
 and drop out by themselves.
 
 Not included, as on the device: tendon springs and dampers, fluid forces, friction loss, actuator, contact, equality and applied forces, the payload of carried
-objects.  Free and ball joints cannot be controlled (clearance._columns refuses them, in the device's words)."""
+objects.  Free and ball joints cannot be controlled (clearance._columns refuses them, in the device's words).
+
+M^-1 (csrc/rsim_dyn_solve.hip, rsim_config_forward_dynamics / rsim_config_mass_solve / rsim_config_opspace): forward_dynamics, mass_solve and opspace are
+numpy.linalg.solve on this file's own mass_matrix, inverse_dynamics and site_jacobian; the kernel runs a Cholesky factorisation in fp32."""
 from collections import OrderedDict
 
 import numpy as np
@@ -131,6 +134,27 @@ def site_jacobian(flat, qpos, site, dofs, q, overrides=None, model32=None):
     p = xpos[b] + xmat[b] @ np.asarray(m.site_pos, dtype=np.float64).reshape(-1, 3)[int(site)]
     jp, jr = mjcf.body_jacobian_np(m, xpos, xmat, xanchor, xaxis, b, p)
     return jp[:, dofs], jr[:, dofs]
+
+
+def forward_dynamics(flat, qpos, dofs, q, qd=None, tau=None, overrides=None, model32=None):
+    """qdd [n] of one candidate: M(q)^-1 (tau - qfrc_bias(q, qd) - dof_damping qd), every other joint locked -- the exact inverse of inverse_dynamics, with its
+    limits (rsim_config_forward_dynamics).  tau None: zeros"""
+    bias = inverse_dynamics(flat, qpos, dofs, q, qd, None, overrides, model32)
+    t = np.zeros_like(bias) if tau is None else np.asarray(tau, dtype=np.float64).ravel()
+    return np.linalg.solve(mass_matrix(flat, qpos, dofs, q, overrides, model32), t - bias)
+
+
+def mass_solve(flat, qpos, dofs, q, rhs, overrides=None, model32=None):
+    """x = M(q)^-1 rhs for rhs [n] or [n, r] (rsim_config_mass_solve)"""
+    return np.linalg.solve(mass_matrix(flat, qpos, dofs, q, overrides, model32), np.asarray(rhs, dtype=np.float64))
+
+
+def opspace(flat, qpos, site, dofs, q, overrides=None, model32=None):
+    """(lambda_inv [6, 6], minv_jt [n, 6]) with J = [jacp; jacr] of site_jacobian: minv_jt = M^-1 J^T, lambda_inv = J M^-1 J^T (rsim_config_opspace).  The
+    operational-space inertia is pinv(lambda_inv) -- lambda_inv is singular for n < 6 and at kinematic singularities -- and Jbar = minv_jt @ pinv(lambda_inv)."""
+    J = np.concatenate(site_jacobian(flat, qpos, site, dofs, q, overrides, model32), axis=0)
+    minv_jt = np.linalg.solve(mass_matrix(flat, qpos, dofs, q, overrides, model32), J.T)
+    return J @ minv_jt, minv_jt
 
 
 def site_position(flat, qpos, site, dofs, q, overrides=None, model32=None):

@@ -426,6 +426,25 @@ class VecEnv:
         model site id; None: the arm's `eef_site`.  arm: as config_fk (site=None needs arm 0 or 1)."""
         return self.env.batch.config_jacobian(self._arm_site("config_jacobian", arm, site), self._arm_dofs("config_jacobian", arm), q)
 
+    def config_forward_dynamics(self, q, qd=None, tau=None, arm=0, return_ok=False):
+        """What acceleration does this torque give here?  q (and qd, tau, each None for zeros) [n_envs, K, n] (2-D for K = 1) candidate joint positions,
+        velocities and joint torques of the arm -> qdd [n_envs, K, n] = M(q)^-1 (tau - Coriolis / centrifugal - gravity - joint damping)
+        (HipBatch.config_forward_dynamics): the exact inverse of config_inverse_dynamics, with its conventions and its limits -- every joint that is not the
+        arm's is locked, and no tendon, fluid, friction-loss, actuator, contact, equality or applied force acts.  return_ok=True: -> (qdd, ok bool
+        [n_envs, K]); where ok is False M was not positive definite in fp32 and qdd is NaN.  arm: as config_fk."""
+        return self.env.batch.config_forward_dynamics(self._arm_dofs("config_forward_dynamics", arm), q, qd=qd, tau=tau, return_ok=return_ok)
+
+    def config_mass_solve(self, q, rhs, arm=0, return_ok=False):
+        """M(q)^-1 rhs at candidate arm joint vectors: rhs [n_envs, K, n, r] (r <= 16) or [n_envs, K, n] -> x of rhs's shape (HipBatch.config_mass_solve)."""
+        return self.env.batch.config_mass_solve(self._arm_dofs("config_mass_solve", arm), q, rhs, return_ok=return_ok)
+
+    def config_opspace(self, q, arm=0, site=None, return_ok=False):
+        """What is the end effector's apparent inertia here?  -> (lambda_inv [n_envs, K, 6, 6], minv_jt [n_envs, K, n, 6]) at candidate arm joint vectors
+        (HipBatch.config_opspace): with J = [jacp; jacr] of config_jacobian, minv_jt = M^-1 J^T and lambda_inv = J M^-1 J^T, symmetric bit for bit.  The
+        inertia itself takes a pseudo-inverse, as robosuite does it: Lambda = torch.linalg.pinv(lambda_inv), Jbar = minv_jt @ Lambda.  site, arm: as
+        config_jacobian."""
+        return self.env.batch.config_opspace(self._arm_site("config_opspace", arm, site), self._arm_dofs("config_opspace", arm), q, return_ok=return_ok)
+
     def path_torques(self, waypoints, dt, arm=0):
         """The torques along joint-space paths: is the motion executable, not merely collision-free?  waypoints [n_envs, K, W, n]: K paths per env of W arm
         joint vectors `dt` seconds apart -> tau [n_envs, K, W, n].  Velocities are central differences of the waypoints, one-sided at the two ends, and
