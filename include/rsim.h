@@ -900,8 +900,9 @@ int rsim_ik_site_avoid_signed(rsim_batch* b, int site, int ndof, const int32_t* 
  * Moments are taken about the candidate's position of the first moved body, not the world origin.  Per-body words live in a batch scratch grown on demand; a lane
  * touches only its own words: no atomics, a repeat call is bit-identical.  Asynchronous on the batch's stream, DEVICE pointers in and out.
  * Refused by name: what rsim_config_fk refuses, a NULL output, and for the Jacobian a site out of range.
- * NOT CARRIED: the payload of carried objects (rsim_attach); free or ball joints as controlled dofs; body or point Jacobians other than sites; derivatives of
- * the dynamics; a torque-limit term inside IK or the fused step; tendon and fluid terms.  (Forward dynamics at candidates: rsim_config_forward_dynamics below.) */
+ * NOT CARRIED: free or ball joints as controlled dofs; body or point Jacobians other than sites; derivatives of the dynamics; a torque-limit term inside IK or
+ * the fused step; tendon and fluid terms.  (Forward dynamics at candidates: rsim_config_forward_dynamics below; the payload of carried objects: the _attached
+ * entries at the end of this file.) */
 int rsim_config_inverse_dynamics(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev /* [B][k][ndof] */,
                                  const float* qd_dev /* [B][k][ndof] or NULL: zeros */, const float* qdd_dev /* likewise */, float* tau_dev /* [B][k][ndof] */);
 int rsim_config_mass_matrix(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, float* M_dev /* [B][k][ndof][ndof] */);
@@ -928,7 +929,7 @@ int rsim_config_jacobian(rsim_batch* b, int site, int ndof, const int32_t* dof_i
  * words: no barrier, no atomics, a repeat call is bit-identical.  A block-diagonal M (two arms) factorises to a block-diagonal L exactly.  Asynchronous on the
  * batch's stream, DEVICE pointers in and out.  A batch that never asks allocates and launches nothing.
  * Refused by name: what rsim_config_fk refuses, a NULL output (for rsim_config_opspace: both NULL), nrhs out of range, a site out of range.
- * NOT CARRIED: Lambda or pseudo-inverses; the payload of carried objects; free or ball joints as controlled dofs; constraint, contact or actuator forces in the
+ * NOT CARRIED: Lambda or pseudo-inverses; free or ball joints as controlled dofs; constraint, contact or actuator forces in the
  * acceleration; integrating candidates forward in time; derivatives. */
 int rsim_config_forward_dynamics(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev /* [B][k][ndof] */,
                                  const float* qd_dev /* [B][k][ndof] or NULL: zeros */, const float* tau_dev /* likewise */, float* qdd_dev /* [B][k][ndof] */,
@@ -937,6 +938,40 @@ int rsim_config_mass_solve(rsim_batch* b, int ndof, const int32_t* dof_ids, int 
                            float* x_dev /* [B][k][ndof][nrhs] */, int32_t* ok_dev /* [B][k] or NULL */);
 int rsim_config_opspace(rsim_batch* b, int site, int ndof, const int32_t* dof_ids, int k, const float* q_dev, float* lambda_inv_dev /* [B][k][6][6] or NULL */,
                         float* minv_jt_dev /* [B][k][ndof][6] or NULL */, int32_t* ok_dev /* [B][k] or NULL */);
+
+/* Carried payloads in the dynamics queries: "is this executable WITH THE OBJECT IN HAND?" -- the six entries above with bodies ATTACHED to links
+ * (csrc/rsim_dyn_att.hip; robosuite_amd/dynamics.py with attach / held / rel is the fp64 statement).  Each _attached entry is the entry of the same
+ * name plus a trailing const rsim_attach*; NULL or n == 0 IS that entry, with its results, its tables and its kernels.  The attachment rules are rsim_attach's,
+ * unchanged: up to RSIM_ATTACH_MAX pairs (body, carrier), held_dev [B][n] or NULL (all held), rel_dev [B][n][7] or NULL (the env's current poses), the same
+ * refusals by name, plus the plain entry's own.
+ * In an env whose held row holds attachment i:
+ *   - the attached body and every body below it are RIGID LOAD on the carrier, at X_carrier(q) o rel; the joints below are held at the env's qpos, as in FK.
+ *   - each such body has the carrier's velocity and acceleration and contributes its wrench to tau and its inertia to M, through the carrier's dof signature (the
+ *     held half of the signature word).  Nothing else sees them.
+ *   - masses, inertias, ipos and iquat are the env's OWN tables: two envs with the same grasp and a different body_mass get different torques.
+ *   - the free joint of the attached body has no column and no armature: it is ignored, as in FK.
+ * In an env that does not hold attachment i its bodies contribute nothing, and EVERY OUTPUT OF THAT ENV IS BIT FOR BIT WHAT THE PLAIN ENTRY RETURNS.
+ * Site Jacobians (rsim_config_jacobian_attached, rsim_config_opspace_attached): the site may sit on an attached body or below one.  Held: the point is placed
+ * from the attached pose and the columns are the carrier's signature.  Not held: zeros, the rule for a site no controlled dof moves.
+ * rsim_config_forward_dynamics_attached is the exact inverse of rsim_config_inverse_dynamics_attached with the same attachment.
+ * Kernels: behind k_clear_fk_att and the unchanged k_clear_joints, ONE kernel each, lane = candidate: k_dyn_rne_att, k_dyn_crb_att, k_dyn_jac_att -- the walks of
+ * the plain kernels in which a held attached body takes V and A from its carrier's slot and adds its wrench / inertia there (moments are about one fixed point,
+ * so they add); where the env does not hold it the slot is stored as zero and nothing is added.  k_dyn_solve runs unchanged behind them.  The dynamics scratch
+ * is sized by the table's slots, which count the attached ones.  A lane touches only its own words: no atomics, a repeat call is bit-identical.  A batch that
+ * never names an attachment in a dynamics call builds no new table, launches no new kernel and allocates nothing new.
+ * NOT CARRIED: a virtual payload with no body in the model; deciding on the device what is grasped; contact or grasp forces between hand and object; attachments
+ * in rsim_ik_site; an object attached to an attached object; free or ball joints as controlled dofs; derivatives. */
+int rsim_config_inverse_dynamics_attached(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, const float* qd_dev, const float* qdd_dev,
+                                          float* tau_dev, const rsim_attach* att);
+int rsim_config_mass_matrix_attached(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, float* M_dev, const rsim_attach* att);
+int rsim_config_jacobian_attached(rsim_batch* b, int site, int ndof, const int32_t* dof_ids, int k, const float* q_dev, float* jacp_dev, float* jacr_dev,
+                                  const rsim_attach* att);
+int rsim_config_forward_dynamics_attached(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, const float* qd_dev, const float* tau_dev,
+                                          float* qdd_dev, int32_t* ok_dev, const rsim_attach* att);
+int rsim_config_mass_solve_attached(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, int nrhs, const float* rhs_dev, float* x_dev,
+                                    int32_t* ok_dev, const rsim_attach* att);
+int rsim_config_opspace_attached(rsim_batch* b, int site, int ndof, const int32_t* dof_ids, int k, const float* q_dev, float* lambda_inv_dev, float* minv_jt_dev,
+                                 int32_t* ok_dev, const rsim_attach* att);
 
 #ifdef __cplusplus
 }

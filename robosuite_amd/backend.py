@@ -323,6 +323,10 @@ def lib():
             L.rsim_config_forward_dynamics.argtypes = [vp, C.c_int, C.POINTER(C.c_int32), C.c_int, vp, vp, vp, vp, vp]
             L.rsim_config_mass_solve.argtypes = [vp, C.c_int, C.POINTER(C.c_int32), C.c_int, vp, C.c_int, vp, vp, vp]
             L.rsim_config_opspace.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, vp, vp, vp, vp]
+        if hasattr(L, "rsim_config_inverse_dynamics_attached"):     # (as above)
+            for f in ("rsim_config_inverse_dynamics", "rsim_config_mass_matrix", "rsim_config_jacobian", "rsim_config_forward_dynamics", "rsim_config_mass_solve",
+                      "rsim_config_opspace"):
+                getattr(L, f + "_attached").argtypes = list(getattr(L, f).argtypes) + [C.POINTER(Attach)]
         L.rsim_comm_unique_id.argtypes = [vp, C.c_size_t]
         L.rsim_comm_create.argtypes = [vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
         L.rsim_allreduce_stats.argtypes = [vp, vp, C.c_int, C.c_int]
@@ -1244,48 +1248,65 @@ class HipBatch:
         dofs, qc, K, flat2 = self._config_q(who, dofs, q)
         return (len(dofs), (C.c_int32 * len(dofs))(*dofs), K, C.c_void_p(qc.data_ptr())), qc, K, flat2, len(dofs)
 
-    def config_inverse_dynamics(self, dofs, q, qd=None, qdd=None):
+    def _dyn_call(self, who, att, *args):
+        """the plain entry rsim_<who>, or with carried objects (att: _attach's C argument) rsim_<who>_attached with att behind the same arguments"""
+        if att is None:
+            return _chk(getattr(self._L, "rsim_" + who)(*args))
+        if not hasattr(self._L, "rsim_" + who + "_attached"):
+            raise RsimError(f"{who}: the loaded library has no rsim_{who}_attached")
+        return _chk(getattr(self._L, "rsim_" + who + "_attached")(*args, C.byref(att)))
+
+    def config_inverse_dynamics(self, dofs, q, qd=None, qdd=None, attach=None, held=None, rel=None):
         """Joint torques at candidate joint vectors, away from the state: q (and qd, qdd, each None for zeros) CUDA float32 [B, K, n] for the controlled `dofs`
         as for config_fk, or [B, n] for K = 1.  Every other joint is held at the env's current qpos with ZERO velocity and acceleration.  -> tau float32
         [B, K, n] ([B, n] for 2-D q):  tau_c = (M qdd)_c + qfrc_bias(q, qd)_c + dof_damping_c qd_c  -- M with dof_armature, qfrc_bias MuJoCo's Coriolis,
         centrifugal and gravity terms, gravity and every inertial parameter from the env's own tables.  With qd = qdd = None: the gravity torque.  Held gripper
         bodies that ride on the arm count.  NOT included: tendon springs and dampers, fluid forces, friction loss, actuator, contact, equality and applied
-        forces, the payload of carried objects.  A pure query on the batch's stream; robosuite_amd/dynamics.py is the fp64 statement by the definition."""
+        forces.  A pure query on the batch's stream; robosuite_amd/dynamics.py is the fp64 statement by the definition.
+        THE PAYLOAD OF CARRIED OBJECTS counts only if the call says so: attach / held / rel (_attach, as for config_fk).  In the envs that hold it an attached
+        free body, and every body below it, is rigid load on its carrier at X_carrier(q) o rel: it has the carrier's velocity and acceleration and adds its
+        wrench, from the env's own body_mass / body_inertia / body_ipos / body_iquat, through the carrier's dofs.  An env that does not hold it returns the
+        bits of the call without attach.  The same three arguments on every dynamics call below mean the same."""
         import torch
 
         head, qc, K, flat2, n = self._dyn_head("config_inverse_dynamics", dofs, q)
         v, a = self._config_like("config_inverse_dynamics", "qd", qd, qc), self._config_like("config_inverse_dynamics", "qdd", qdd, qc)
+        att, _keep = self._attach("config_inverse_dynamics", attach, held, rel)
         tau = torch.empty((self.B, K, n), dtype=torch.float32, device=qc.device)
         self._ray_fence_in()
-        _chk(self._L.rsim_config_inverse_dynamics(self.ptr, *head, C.c_void_p(v.data_ptr()) if v is not None else None,
-                                                  C.c_void_p(a.data_ptr()) if a is not None else None, C.c_void_p(tau.data_ptr())))
+        self._dyn_call("config_inverse_dynamics", att, self.ptr, *head, C.c_void_p(v.data_ptr()) if v is not None else None,
+                       C.c_void_p(a.data_ptr()) if a is not None else None, C.c_void_p(tau.data_ptr()))
         self._ray_fence_out()
         return tau[:, 0] if flat2 else tau
 
-    def config_mass_matrix(self, dofs, q):
+    def config_mass_matrix(self, dofs, q, attach=None, held=None, rel=None):
         """The joint-space inertia at candidate joint vectors: -> M float32 [B, K, n, n] ([B, n, n] for 2-D q), the block of M(q) on the controlled dofs with
         dof_armature on the diagonal -- the inertia of the mechanism with every other joint locked.  Symmetric bit for bit; two dofs on different branches
-        (the two arms of a two-arm robot) give exactly 0.  Arguments and rules as config_inverse_dynamics."""
+        (the two arms of a two-arm robot) give exactly 0.  Arguments and rules as config_inverse_dynamics; a held attached body adds its inertia to its
+        carrier's."""
         import torch
 
         head, qc, K, flat2, n = self._dyn_head("config_mass_matrix", dofs, q)
+        att, _keep = self._attach("config_mass_matrix", attach, held, rel)
         M = torch.empty((self.B, K, n, n), dtype=torch.float32, device=qc.device)
         self._ray_fence_in()
-        _chk(self._L.rsim_config_mass_matrix(self.ptr, *head, C.c_void_p(M.data_ptr())))
+        self._dyn_call("config_mass_matrix", att, self.ptr, *head, C.c_void_p(M.data_ptr()))
         self._ray_fence_out()
         return M[:, 0] if flat2 else M
 
-    def config_jacobian(self, site, dofs, q):
+    def config_jacobian(self, site, dofs, q, attach=None, held=None, rel=None):
         """mj_jacSite at candidate joint vectors, in the controlled columns: -> (jacp, jacr) float32 [B, K, 3, n] each ([B, 3, n] for 2-D q).  The site is placed
         from the env's own site_pos on its body's candidate pose; a site on a body no controlled dof moves reads zeros.  Arguments and rules as
-        config_inverse_dynamics."""
+        config_inverse_dynamics.  With attach the site may sit on an attached body or below one: where the env holds it the point is placed from the attached
+        pose and the columns are the carrier's; where it does not, zeros."""
         import torch
 
         head, qc, K, flat2, n = self._dyn_head("config_jacobian", dofs, q)
+        att, _keep = self._attach("config_jacobian", attach, held, rel)
         jp = torch.empty((self.B, K, 3, n), dtype=torch.float32, device=qc.device)
         jr = torch.empty((self.B, K, 3, n), dtype=torch.float32, device=qc.device)
         self._ray_fence_in()
-        _chk(self._L.rsim_config_jacobian(self.ptr, int(site), *head, C.c_void_p(jp.data_ptr()), C.c_void_p(jr.data_ptr())))
+        self._dyn_call("config_jacobian", att, self.ptr, int(site), *head, C.c_void_p(jp.data_ptr()), C.c_void_p(jr.data_ptr()))
         self._ray_fence_out()
         return (jp[:, 0], jr[:, 0]) if flat2 else (jp, jr)
 
@@ -1295,29 +1316,32 @@ class HipBatch:
             raise RsimError(f"{who}: the loaded library has no rsim_{who}")
         return self._dyn_head(who, dofs, q)
 
-    def config_forward_dynamics(self, dofs, q, qd=None, tau=None, return_ok=False):
+    def config_forward_dynamics(self, dofs, q, qd=None, tau=None, return_ok=False, attach=None, held=None, rel=None):
         """Joint accelerations at candidate joint vectors, away from the state: -> qdd float32 [B, K, n] ([B, n] for 2-D q),
         qdd = M(q)^-1 (tau - qfrc_bias(q, qd) - dof_damping qd), M config_mass_matrix's block -- every other joint locked, at zero velocity and acceleration --
         and the bias and damping terms exactly what config_inverse_dynamics(q, qd) returns.  qd / tau: None for zeros.  The exact inverse of
         config_inverse_dynamics, with its limits: no tendon, fluid, friction-loss, actuator, contact, equality or applied forces.  return_ok=True: ->
         (qdd, ok bool [B, K]); ok is False where a Cholesky pivot of M was not finite and > 0, and that candidate's qdd is then NaN (no other candidate is
-        affected).  Arguments and rules as config_inverse_dynamics; robosuite_amd/dynamics.py forward_dynamics is the fp64 statement."""
+        affected).  Arguments and rules as config_inverse_dynamics -- attach / held / rel too: with them this is the exact inverse of
+        config_inverse_dynamics with the same attachment; robosuite_amd/dynamics.py forward_dynamics is the fp64 statement."""
         import torch
 
         head, qc, K, flat2, n = self._solve_head("config_forward_dynamics", dofs, q)
         v, t = self._config_like("config_forward_dynamics", "qd", qd, qc), self._config_like("config_forward_dynamics", "tau", tau, qc)
+        att, _keep = self._attach("config_forward_dynamics", attach, held, rel)
         qdd = torch.empty((self.B, K, n), dtype=torch.float32, device=qc.device)
         ok = torch.empty((self.B, K), dtype=torch.int32, device=qc.device)
         self._ray_fence_in()
-        _chk(self._L.rsim_config_forward_dynamics(self.ptr, *head, C.c_void_p(v.data_ptr()) if v is not None else None,
-                                                  C.c_void_p(t.data_ptr()) if t is not None else None, C.c_void_p(qdd.data_ptr()), C.c_void_p(ok.data_ptr())))
+        self._dyn_call("config_forward_dynamics", att, self.ptr, *head, C.c_void_p(v.data_ptr()) if v is not None else None,
+                       C.c_void_p(t.data_ptr()) if t is not None else None, C.c_void_p(qdd.data_ptr()), C.c_void_p(ok.data_ptr()))
         self._ray_fence_out()
         qdd, ok = (qdd[:, 0], ok[:, 0] != 0) if flat2 else (qdd, ok != 0)
         return (qdd, ok) if return_ok else qdd
 
-    def config_mass_solve(self, dofs, q, rhs, return_ok=False):
+    def config_mass_solve(self, dofs, q, rhs, return_ok=False, attach=None, held=None, rel=None):
         """x = M(q)^-1 rhs at candidate joint vectors: rhs CUDA float32 [B, K, n, r], 1 <= r <= 16 -> x of the same shape; rhs [B, K, n] is r = 1 and returns
-        [B, K, n].  With a 2-D q, rhs is [B, n, r] or [B, n].  M is config_mass_matrix's block.  return_ok: as config_forward_dynamics."""
+        [B, K, n].  With a 2-D q, rhs is [B, n, r] or [B, n].  M is config_mass_matrix's block (attach / held / rel: with the held payload).  return_ok: as
+        config_forward_dynamics."""
         import torch
 
         who = "config_mass_solve"
@@ -1335,28 +1359,31 @@ class HipBatch:
         if not 1 <= r <= 16:
             raise RsimError(f"{who}: nrhs {r} out of range (1..16)")
         rc = rhs.contiguous().float().reshape(self.B, K, n, r)
+        att, _keep = self._attach(who, attach, held, rel)
         x = torch.empty_like(rc)
         ok = torch.empty((self.B, K), dtype=torch.int32, device=qc.device)
         self._ray_fence_in()
-        _chk(self._L.rsim_config_mass_solve(self.ptr, *head, r, C.c_void_p(rc.data_ptr()), C.c_void_p(x.data_ptr()), C.c_void_p(ok.data_ptr())))
+        self._dyn_call(who, att, self.ptr, *head, r, C.c_void_p(rc.data_ptr()), C.c_void_p(x.data_ptr()), C.c_void_p(ok.data_ptr()))
         self._ray_fence_out()
         x = x.reshape(shape)
         ok = ok[:, 0] != 0 if flat2 else ok != 0
         return (x, ok) if return_ok else x
 
-    def config_opspace(self, site, dofs, q, return_ok=False):
+    def config_opspace(self, site, dofs, q, return_ok=False, attach=None, held=None, rel=None):
         """The operational-space quantities of `site` at candidate joint vectors: -> (lambda_inv float32 [B, K, 6, 6], minv_jt float32 [B, K, n, 6]) (without the
         K axis for 2-D q).  With J = [jacp; jacr] of config_jacobian and M of config_mass_matrix: minv_jt = M^-1 J^T, lambda_inv = J M^-1 J^T, symmetric bit for
         bit.  The operational-space inertia itself is left to the caller, as robosuite does it: lambda_inv is singular for n < 6 and at kinematic singularities,
-        so Lambda = torch.linalg.pinv(lambda_inv), Jbar = minv_jt @ Lambda.  return_ok: as config_forward_dynamics."""
+        so Lambda = torch.linalg.pinv(lambda_inv), Jbar = minv_jt @ Lambda.  return_ok: as config_forward_dynamics.  attach / held / rel: J and M with the held
+        payload -- the apparent inertia at a point on the carried object (a peg tip) is this call with the site on that object."""
         import torch
 
         head, qc, K, flat2, n = self._solve_head("config_opspace", dofs, q)
+        att, _keep = self._attach("config_opspace", attach, held, rel)
         lam = torch.empty((self.B, K, 6, 6), dtype=torch.float32, device=qc.device)
         mjt = torch.empty((self.B, K, n, 6), dtype=torch.float32, device=qc.device)
         ok = torch.empty((self.B, K), dtype=torch.int32, device=qc.device)
         self._ray_fence_in()
-        _chk(self._L.rsim_config_opspace(self.ptr, int(site), *head, C.c_void_p(lam.data_ptr()), C.c_void_p(mjt.data_ptr()), C.c_void_p(ok.data_ptr())))
+        self._dyn_call("config_opspace", att, self.ptr, int(site), *head, C.c_void_p(lam.data_ptr()), C.c_void_p(mjt.data_ptr()), C.c_void_p(ok.data_ptr()))
         self._ray_fence_out()
         lam, mjt, ok = (lam[:, 0], mjt[:, 0], ok[:, 0] != 0) if flat2 else (lam, mjt, ok != 0)
         return (lam, mjt, ok) if return_ok else (lam, mjt)

@@ -123,34 +123,35 @@ class BatchState:
         """The motion bound L config_sweep uses for these segments (HipBatch.config_motion_bound)."""
         return self.batch.config_motion_bound(dofs, q0, q1, pairs=pairs, attach=attach, held=held, rel=rel)
 
-    def config_inverse_dynamics(self, dofs, q, qd=None, qdd=None):
+    def config_inverse_dynamics(self, dofs, q, qd=None, qdd=None, attach=None, held=None, rel=None):
         """Joint torques of `dofs` at candidate joint vectors, velocities and accelerations, away from the state (HipBatch.config_inverse_dynamics): -> tau.
-        Every other joint is held where it is, at rest.  Valid between step1 and step2."""
-        return self.batch.config_inverse_dynamics(dofs, q, qd=qd, qdd=qdd)
+        Every other joint is held where it is, at rest.  Valid between step1 and step2.  attach / held / rel (HipBatch._attach), here and on the five calls
+        below: the payload of carried objects -- in the envs that hold it an attached body is rigid load on its carrier."""
+        return self.batch.config_inverse_dynamics(dofs, q, qd=qd, qdd=qdd, attach=attach, held=held, rel=rel)
 
-    def config_mass_matrix(self, dofs, q):
+    def config_mass_matrix(self, dofs, q, attach=None, held=None, rel=None):
         """The joint-space inertia on `dofs` at candidate joint vectors, away from the state (HipBatch.config_mass_matrix): -> M [B, K, n, n].  `mass_matrix`
         is the current state's."""
-        return self.batch.config_mass_matrix(dofs, q)
+        return self.batch.config_mass_matrix(dofs, q, attach=attach, held=held, rel=rel)
 
-    def config_jacobian(self, site, dofs, q):
+    def config_jacobian(self, site, dofs, q, attach=None, held=None, rel=None):
         """mj_jacSite of `site` in the columns of `dofs` at candidate joint vectors, away from the state (HipBatch.config_jacobian): -> (jacp, jacr)
         [B, K, 3, n].  `site_jacobian` is the current state's."""
-        return self.batch.config_jacobian(site, dofs, q)
+        return self.batch.config_jacobian(site, dofs, q, attach=attach, held=held, rel=rel)
 
-    def config_forward_dynamics(self, dofs, q, qd=None, tau=None, return_ok=False):
+    def config_forward_dynamics(self, dofs, q, qd=None, tau=None, return_ok=False, attach=None, held=None, rel=None):
         """Joint accelerations of `dofs` at candidate joint vectors, velocities and torques, away from the state (HipBatch.config_forward_dynamics): -> qdd
         [B, K, n] = M^-1 (tau - bias - damping qd), the exact inverse of config_inverse_dynamics.  return_ok=True: -> (qdd, ok bool [B, K])."""
-        return self.batch.config_forward_dynamics(dofs, q, qd=qd, tau=tau, return_ok=return_ok)
+        return self.batch.config_forward_dynamics(dofs, q, qd=qd, tau=tau, return_ok=return_ok, attach=attach, held=held, rel=rel)
 
-    def config_mass_solve(self, dofs, q, rhs, return_ok=False):
+    def config_mass_solve(self, dofs, q, rhs, return_ok=False, attach=None, held=None, rel=None):
         """M^-1 rhs on `dofs` at candidate joint vectors, away from the state (HipBatch.config_mass_solve): rhs [B, K, n, r] or [B, K, n] -> x of rhs's shape."""
-        return self.batch.config_mass_solve(dofs, q, rhs, return_ok=return_ok)
+        return self.batch.config_mass_solve(dofs, q, rhs, return_ok=return_ok, attach=attach, held=held, rel=rel)
 
-    def config_opspace(self, site, dofs, q, return_ok=False):
+    def config_opspace(self, site, dofs, q, return_ok=False, attach=None, held=None, rel=None):
         """J M^-1 J^T and M^-1 J^T of `site` in the columns of `dofs` at candidate joint vectors, away from the state (HipBatch.config_opspace): ->
         (lambda_inv [B, K, 6, 6], minv_jt [B, K, n, 6]).  Lambda = pinv(lambda_inv) is the caller's, as in TorchOSCPoseController.torques_from."""
-        return self.batch.config_opspace(site, dofs, q, return_ok=return_ok)
+        return self.batch.config_opspace(site, dofs, q, return_ok=return_ok, attach=attach, held=held, rel=rel)
 
     def body_dofs(self, body: int):
         """bool [nv]: the dofs that move `body` (its own joints and those of its ancestors)."""

@@ -95,6 +95,7 @@ extern "C" int rsim_launch_randomize(const DModel* m, const DBatch* b, const DDr
 #include "rsim_ik_avoid.h"
 #include "rsim_dyn.h"
 #include "rsim_dyn_core.h"
+#include "rsim_dyn_att.h"
 #include "rsim_dyn_solve.h"
 #include "rsim_sweep.h"
 #include "rsim_hull.h"
@@ -163,6 +164,7 @@ struct ClearTab {
   std::vector<int> sig_words; int* d_sig; unsigned slide_mask;
   // the dynamics queries (rsim_dyn.hip): dof id and table element of every controlled column, on the device once one of them has asked
   int* d_cols;
+  std::vector<int> att_of;   // with attachments: [nbody] the attachment a body belongs to or -1 (the host copy of d_att's second half; the site of a Jacobian)
 };
 
 struct rsim_batch {
@@ -2532,6 +2534,7 @@ static int clear_table(rsim_batch* b, const char* who, int ndof, const int32_t* 
     ClearTab t;
     t.d_tab = t.d_slot = t.d_att = nullptr; t.nel = plan.nel; t.nslot = plan.nslot; t.slot = plan.slot; t.natt = plan.natt;
     t.d_sig = nullptr; t.slide_mask = plan.slide_mask; t.d_cols = nullptr;
+    if (plan.natt > 0) t.att_of = plan.att_of;
     t.sig_words.resize((size_t)b->m->nbody);
     for (int i = 0; i < b->m->nbody; i++) t.sig_words[i] = (int)((plan.sig[i] & 0xffffu) | (plan.sig_held[i] << 16));
     std::vector<int> h;   // what the pair loop's skip rule reads: [nbody] both signatures in one word, [nbody] the attachment a body belongs to
@@ -2907,9 +2910,12 @@ extern "C" int rsim_ik_site_avoid_signed(rsim_batch* b, int site, int ndof, cons
 
 // ---- dynamics at candidates (rsim_dyn.hip, include/rsim.h rsim_config_inverse_dynamics / rsim_config_mass_matrix / rsim_config_jacobian): rsim_config_fk's
 // argument and refusals, the pose scratch and the joint store of the gradient entries, then one kernel of rsim_dyn.hip behind k_clear_fk and k_clear_joints
-static int dyn_args(rsim_batch* b, const char* who, int ndof, const int32_t* dof_ids, int k, const float* q_dev, int words, DDyn* d, const ClearTab** tab) {
+// att: the carried objects of an _attached entry (NULL or n == 0: the plain entry, with its tables and its kernels).  clear_args refuses what rsim_config_fk_attached
+// refuses and picks the table of (dof list, attachment list), whose nslot counts the attached slots: the scratches below are sized by it.
+static int dyn_args(rsim_batch* b, const char* who, int ndof, const int32_t* dof_ids, int k, const float* q_dev, int words, DDyn* d, const ClearTab** tab,
+                    const rsim_attach* att) {
   DClear a;
-  if (clear_args(b, who, ndof, dof_ids, k, q_dev, nullptr, &a, tab)) return 1;
+  if (clear_args(b, who, ndof, dof_ids, k, q_dev, att, &a, tab)) return 1;
   if (refresh_derived(b, RSIM_XPOS)) return 1;
   const rsim_model* m = b->m;
   if (clear_grow(b, &b->d_clear_scr, &b->clear_scr_n, (size_t)a.nslot * 7 * a.NC)) return 1;
@@ -2918,7 +2924,7 @@ static int dyn_args(rsim_batch* b, const char* who, int ndof, const int32_t* dof
   if (grad_args(b, *tab, a, &d->g)) return 1;
   if (!(*tab)->d_cols) {   // which dof and which table element each controlled column is: from the plan of the dof list, once
     ClearPlan plan;
-    if (clear_plan(m, who, ndof, dof_ids, 0, nullptr, &plan)) return 1;
+    if (clear_plan(m, who, ndof, dof_ids, a.natt, a.natt > 0 ? att->bodies : nullptr, &plan)) return 1;   // (the table's own plan: with its attachment list)
     std::vector<int> cols((size_t)RSIM_DYN_COL * ndof, -1);
     for (int e = 0; e < plan.nel; e++) {
       const int* el = plan.tab.data() + (size_t)RSIM_CLEAR_REC * e;
@@ -2942,35 +2948,55 @@ static int dyn_args(rsim_batch* b, const char* who, int ndof, const int32_t* dof
   d->fo_armature = m->fo[FO_dof_armature]; d->fo_damping = m->fo[FO_dof_damping]; d->fo_opt = m->fo[FO_opt];
   return 0;
 }
-static int dyn_run(const char* who, rsim_batch* b, const DDyn& d, int (*launch)(const DDyn*, hipStream_t)) {
+// the three kernels of a call: rsim_dyn.hip's, or with attachments rsim_dyn_att.hip's (k_clear_fk likewise picks its attached instantiation by natt)
+static int dyn_rne(const DDyn& d, hipStream_t s) { return d.g.c.natt > 0 ? rsim_launch_dyn_rne_att(&d, s) : rsim_launch_dyn_rne(&d, s); }
+static int dyn_crb(const DDyn& d, hipStream_t s) { return d.g.c.natt > 0 ? rsim_launch_dyn_crb_att(&d, s) : rsim_launch_dyn_crb(&d, s); }
+static int dyn_jac(const DDyn& d, int site_att, hipStream_t s) { return d.g.c.natt > 0 ? rsim_launch_dyn_jac_att(&d, site_att, s) : rsim_launch_dyn_jac(&d, s); }
+// the site of a Jacobian: its body, that body's slot and signature.  With attachments the whole signature word travels and the kernel takes the half the lane's
+// env selects; -> the attachment the body belongs to, -1 for none
+static int dyn_site(const rsim_batch* b, const ClearTab* tab, int site, int body, DDyn* d) {
+  d->site_body = body; d->site_slot = tab->slot[body]; d->o_site_pos = b->m->fo[FO_site_pos] + 3 * site;
+  d->site_sig = tab->natt > 0 ? (unsigned)tab->sig_words[body] : (unsigned)tab->sig_words[body] & 0xffffu;
+  return tab->natt > 0 ? tab->att_of[body] : -1;
+}
+static int dyn_run(const char* who, rsim_batch* b, const DDyn& d, int kernel, int site_att = -1) {
   int e = rsim_launch_clear_fk(&d.g.c, b->stream);
   if (!e) e = rsim_launch_clear_joints(&d.g, b->stream);
-  if (!e) e = launch(&d, b->stream);
+  if (!e) e = kernel == 0 ? dyn_rne(d, b->stream) : kernel == 1 ? dyn_crb(d, b->stream) : dyn_jac(d, site_att, b->stream);
   return launched(who, e);
 }
-extern "C" int rsim_config_inverse_dynamics(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, const float* qd_dev, const float* qdd_dev,
-                                            float* tau_dev) {
-  const char* who = "rsim_config_inverse_dynamics";
+static const char* dyn_who(const rsim_attach* att, const char* plain, const char* attached) { return att && att->n ? attached : plain; }
+extern "C" int rsim_config_inverse_dynamics_attached(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, const float* qd_dev,
+                                                     const float* qdd_dev, float* tau_dev, const rsim_attach* att) {
+  const char* who = dyn_who(att, "rsim_config_inverse_dynamics", "rsim_config_inverse_dynamics_attached");
   if (!b) return fail("%s: batch is NULL", who);
   if (!tau_dev) return fail("%s: tau_dev is NULL", who);
   DDyn d;
   const ClearTab* tab;
-  if (dyn_args(b, who, ndof, dof_ids, k, q_dev, RSIM_DYN_RNE_WORDS, &d, &tab)) return 1;
+  if (dyn_args(b, who, ndof, dof_ids, k, q_dev, RSIM_DYN_RNE_WORDS, &d, &tab, att)) return 1;
   d.qd = qd_dev; d.qdd = qdd_dev; d.tau = tau_dev;
-  return dyn_run(who, b, d, rsim_launch_dyn_rne);
+  return dyn_run(who, b, d, 0);
 }
-extern "C" int rsim_config_mass_matrix(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, float* M_dev) {
-  const char* who = "rsim_config_mass_matrix";
+extern "C" int rsim_config_inverse_dynamics(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, const float* qd_dev, const float* qdd_dev,
+                                            float* tau_dev) {
+  return rsim_config_inverse_dynamics_attached(b, ndof, dof_ids, k, q_dev, qd_dev, qdd_dev, tau_dev, nullptr);
+}
+extern "C" int rsim_config_mass_matrix_attached(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, float* M_dev, const rsim_attach* att) {
+  const char* who = dyn_who(att, "rsim_config_mass_matrix", "rsim_config_mass_matrix_attached");
   if (!b) return fail("%s: batch is NULL", who);
   if (!M_dev) return fail("%s: M_dev is NULL", who);
   DDyn d;
   const ClearTab* tab;
-  if (dyn_args(b, who, ndof, dof_ids, k, q_dev, RSIM_DYN_CRB_WORDS, &d, &tab)) return 1;
+  if (dyn_args(b, who, ndof, dof_ids, k, q_dev, RSIM_DYN_CRB_WORDS, &d, &tab, att)) return 1;
   d.M = M_dev;
-  return dyn_run(who, b, d, rsim_launch_dyn_crb);
+  return dyn_run(who, b, d, 1);
 }
-extern "C" int rsim_config_jacobian(rsim_batch* b, int site, int ndof, const int32_t* dof_ids, int k, const float* q_dev, float* jacp_dev, float* jacr_dev) {
-  const char* who = "rsim_config_jacobian";
+extern "C" int rsim_config_mass_matrix(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, float* M_dev) {
+  return rsim_config_mass_matrix_attached(b, ndof, dof_ids, k, q_dev, M_dev, nullptr);
+}
+extern "C" int rsim_config_jacobian_attached(rsim_batch* b, int site, int ndof, const int32_t* dof_ids, int k, const float* q_dev, float* jacp_dev, float* jacr_dev,
+                                             const rsim_attach* att) {
+  const char* who = dyn_who(att, "rsim_config_jacobian", "rsim_config_jacobian_attached");
   if (!b) return fail("%s: batch is NULL", who);
   if (site < 0 || site >= b->m->nsite) return fail("%s: site %d out of range (%d sites)", who, site, b->m->nsite);
   if (!jacp_dev && !jacr_dev) return fail("%s: jacp_dev and jacr_dev are both NULL", who);
@@ -2978,18 +3004,20 @@ extern "C" int rsim_config_jacobian(rsim_batch* b, int site, int ndof, const int
   if (body < 0 || body >= b->m->nbody) return fail("%s: site %d names body %d of %d", who, site, body, b->m->nbody);
   DDyn d;
   const ClearTab* tab;
-  if (dyn_args(b, who, ndof, dof_ids, k, q_dev, 0, &d, &tab)) return 1;
-  d.site_body = body; d.site_slot = tab->slot[body]; d.o_site_pos = b->m->fo[FO_site_pos] + 3 * site;
-  d.site_sig = (unsigned)tab->sig_words[body] & 0xffffu;
+  if (dyn_args(b, who, ndof, dof_ids, k, q_dev, 0, &d, &tab, att)) return 1;
+  const int site_att = dyn_site(b, tab, site, body, &d);
   d.jacp = jacp_dev; d.jacr = jacr_dev;
-  return dyn_run(who, b, d, rsim_launch_dyn_jac);
+  return dyn_run(who, b, d, 2, site_att);
+}
+extern "C" int rsim_config_jacobian(rsim_batch* b, int site, int ndof, const int32_t* dof_ids, int k, const float* q_dev, float* jacp_dev, float* jacr_dev) {
+  return rsim_config_jacobian_attached(b, site, ndof, dof_ids, k, q_dev, jacp_dev, jacr_dev, nullptr);
 }
 
 // ---- M^-1 at candidates (rsim_dyn_solve.hip, include/rsim.h rsim_config_forward_dynamics / rsim_config_mass_solve / rsim_config_opspace): dyn_args above, the
 // unchanged kernels of rsim_dyn.hip into batch scratches, then k_dyn_solve.  rne: k_dyn_rne (qdd null: the bias torques) in front of k_dyn_crb; jac: k_dyn_jac
 // behind it; either leaves in_words floats per candidate in the input scratch.  Both walks keep their per-body words in the one dynamics scratch, which dyn_args
 // has sized for the larger of the two the call runs: they run one after the other on the stream.
-static int solve_run(const char* who, rsim_batch* b, DDyn& d, DSolve& s, int in_words, bool rne, bool jac) {
+static int solve_run(const char* who, rsim_batch* b, DDyn& d, DSolve& s, int in_words, bool rne, bool jac, int site_att = -1) {
   const DClear& c = d.g.c;
   if (clear_grow(b, &b->d_solve_M, &b->solve_M_n, (size_t)c.NC * c.n * c.n)) return 1;
   if (in_words > 0 && clear_grow(b, &b->d_solve_in, &b->solve_in_n, (size_t)c.NC * in_words)) return 1;
@@ -2999,47 +3027,55 @@ static int solve_run(const char* who, rsim_batch* b, DDyn& d, DSolve& s, int in_
   if (!e) e = rsim_launch_clear_joints(&d.g, b->stream);
   if (!e && rne) {
     d.qdd = nullptr; d.tau = b->d_solve_in; s.bias = b->d_solve_in;
-    e = rsim_launch_dyn_rne(&d, b->stream);
+    e = dyn_rne(d, b->stream);
   }
-  if (!e) e = rsim_launch_dyn_crb(&d, b->stream);
+  if (!e) e = dyn_crb(d, b->stream);
   if (!e && jac) {
     d.jacp = b->d_solve_in; d.jacr = b->d_solve_in + (size_t)c.NC * 3 * c.n; s.jacp = d.jacp; s.jacr = d.jacr;
-    e = rsim_launch_dyn_jac(&d, b->stream);
+    e = dyn_jac(d, site_att, b->stream);
   }
   if (!e) e = rsim_launch_dyn_solve(&s, b->stream);
   return launched(who, e);
 }
-extern "C" int rsim_config_forward_dynamics(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, const float* qd_dev, const float* tau_dev,
-                                            float* qdd_dev, int32_t* ok_dev) {
-  const char* who = "rsim_config_forward_dynamics";
+extern "C" int rsim_config_forward_dynamics_attached(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, const float* qd_dev,
+                                                     const float* tau_dev, float* qdd_dev, int32_t* ok_dev, const rsim_attach* att) {
+  const char* who = dyn_who(att, "rsim_config_forward_dynamics", "rsim_config_forward_dynamics_attached");
   if (!b) return fail("%s: batch is NULL", who);
   if (!qdd_dev) return fail("%s: qdd_dev is NULL", who);
   DDyn d;
   const ClearTab* tab;
-  if (dyn_args(b, who, ndof, dof_ids, k, q_dev, RSIM_DYN_RNE_WORDS, &d, &tab)) return 1;
+  if (dyn_args(b, who, ndof, dof_ids, k, q_dev, RSIM_DYN_RNE_WORDS, &d, &tab, att)) return 1;
   DSolve s;
   memset(&s, 0, sizeof(s));
   d.qd = qd_dev;
   s.mode = RSIM_SOLVE_FD; s.tau = tau_dev; s.x = qdd_dev; s.ok = ok_dev;
   return solve_run(who, b, d, s, ndof, true, false);
 }
-extern "C" int rsim_config_mass_solve(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, int nrhs, const float* rhs_dev, float* x_dev,
-                                      int32_t* ok_dev) {
-  const char* who = "rsim_config_mass_solve";
+extern "C" int rsim_config_forward_dynamics(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, const float* qd_dev, const float* tau_dev,
+                                            float* qdd_dev, int32_t* ok_dev) {
+  return rsim_config_forward_dynamics_attached(b, ndof, dof_ids, k, q_dev, qd_dev, tau_dev, qdd_dev, ok_dev, nullptr);
+}
+extern "C" int rsim_config_mass_solve_attached(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, int nrhs, const float* rhs_dev,
+                                               float* x_dev, int32_t* ok_dev, const rsim_attach* att) {
+  const char* who = dyn_who(att, "rsim_config_mass_solve", "rsim_config_mass_solve_attached");
   if (!b) return fail("%s: batch is NULL", who);
   if (nrhs < 1 || nrhs > RSIM_JNT_MAX) return fail("%s: nrhs %d out of range (1..%d)", who, nrhs, RSIM_JNT_MAX);
   if (!rhs_dev || !x_dev) return fail("%s: %s is NULL", who, !rhs_dev ? "rhs_dev" : "x_dev");
   DDyn d;
   const ClearTab* tab;
-  if (dyn_args(b, who, ndof, dof_ids, k, q_dev, RSIM_DYN_CRB_WORDS, &d, &tab)) return 1;
+  if (dyn_args(b, who, ndof, dof_ids, k, q_dev, RSIM_DYN_CRB_WORDS, &d, &tab, att)) return 1;
   DSolve s;
   memset(&s, 0, sizeof(s));
   s.mode = RSIM_SOLVE_RHS; s.nrhs = nrhs; s.rhs = rhs_dev; s.x = x_dev; s.ok = ok_dev;
   return solve_run(who, b, d, s, 0, false, false);
 }
-extern "C" int rsim_config_opspace(rsim_batch* b, int site, int ndof, const int32_t* dof_ids, int k, const float* q_dev, float* lambda_inv_dev, float* minv_jt_dev,
-                                   int32_t* ok_dev) {
-  const char* who = "rsim_config_opspace";
+extern "C" int rsim_config_mass_solve(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, int nrhs, const float* rhs_dev, float* x_dev,
+                                      int32_t* ok_dev) {
+  return rsim_config_mass_solve_attached(b, ndof, dof_ids, k, q_dev, nrhs, rhs_dev, x_dev, ok_dev, nullptr);
+}
+extern "C" int rsim_config_opspace_attached(rsim_batch* b, int site, int ndof, const int32_t* dof_ids, int k, const float* q_dev, float* lambda_inv_dev,
+                                            float* minv_jt_dev, int32_t* ok_dev, const rsim_attach* att) {
+  const char* who = dyn_who(att, "rsim_config_opspace", "rsim_config_opspace_attached");
   if (!b) return fail("%s: batch is NULL", who);
   if (site < 0 || site >= b->m->nsite) return fail("%s: site %d out of range (%d sites)", who, site, b->m->nsite);
   if (!lambda_inv_dev && !minv_jt_dev) return fail("%s: lambda_inv_dev and minv_jt_dev are both NULL", who);
@@ -3047,13 +3083,16 @@ extern "C" int rsim_config_opspace(rsim_batch* b, int site, int ndof, const int3
   if (body < 0 || body >= b->m->nbody) return fail("%s: site %d names body %d of %d", who, site, body, b->m->nbody);
   DDyn d;
   const ClearTab* tab;
-  if (dyn_args(b, who, ndof, dof_ids, k, q_dev, RSIM_DYN_CRB_WORDS, &d, &tab)) return 1;
-  d.site_body = body; d.site_slot = tab->slot[body]; d.o_site_pos = b->m->fo[FO_site_pos] + 3 * site;
-  d.site_sig = (unsigned)tab->sig_words[body] & 0xffffu;
+  if (dyn_args(b, who, ndof, dof_ids, k, q_dev, RSIM_DYN_CRB_WORDS, &d, &tab, att)) return 1;
+  const int site_att = dyn_site(b, tab, site, body, &d);
   DSolve s;
   memset(&s, 0, sizeof(s));
   s.mode = RSIM_SOLVE_OPSPACE; s.x = minv_jt_dev; s.lambda_inv = lambda_inv_dev; s.ok = ok_dev;
-  return solve_run(who, b, d, s, 6 * ndof, false, true);
+  return solve_run(who, b, d, s, 6 * ndof, false, true, site_att);
+}
+extern "C" int rsim_config_opspace(rsim_batch* b, int site, int ndof, const int32_t* dof_ids, int k, const float* q_dev, float* lambda_inv_dev, float* minv_jt_dev,
+                                   int32_t* ok_dev) {
+  return rsim_config_opspace_attached(b, site, ndof, dof_ids, k, q_dev, lambda_inv_dev, minv_jt_dev, ok_dev, nullptr);
 }
 
 // ---- swept clearance (rsim_sweep.hip, include/rsim.h rsim_config_sweep / rsim_config_motion_bound) -----------------------------------------------------------

@@ -14,8 +14,18 @@ at the point c is a_j x (c - p_j).  No recursion over the tree carries a velocit
 composite rigid bodies, the fp64 oracle its own RNE, and this file shares an algorithm with neither.  Bodies the controlled dofs do not move have zero columns
 and drop out by themselves.
 
-Not included, as on the device: tendon springs and dampers, fluid forces, friction loss, actuator, contact, equality and applied forces, the payload of carried
-objects.  Free and ball joints cannot be controlled (clearance._columns refuses them, in the device's words).
+Not included, as on the device: tendon springs and dampers, fluid forces, friction loss, actuator, contact, equality and applied forces.  Free and ball joints
+cannot be controlled (clearance._columns refuses them, in the device's words).
+
+CARRIED PAYLOADS (csrc/rsim_dyn_att.hip, the _attached entries of include/rsim.h): attach = [(body, carrier), ...], held = THIS env's row (None:
+all held), rel = this env's [n, 7] rows or None (the env's current poses; now = (xpos, xquat) hands them in), by clearance.py's rules and refusals.  In an
+env that holds attachment i the attached body and every body below it are rigid load on the carrier at X_carrier(q) o rel, the joints below held at qpos: each
+such body adds its own term of the sum above,  Jp^T m (a - g) + Jr^T (I alpha + omega x I omega),  with Jp / Jr the CARRIER's mjcf.body_jacobian_np at the held
+body's centre of mass, its pose from clearance.fk's attached FK, and mass, inertia, ipos and iquat from the env's own tables.  To M it adds
+Jp^T m Jp + Jr^T I Jr.  The attached body's free joint has no column and no armature.  Not held: nothing is added -- as a free body it has no controlled
+column and drops out by itself.  A site on a held body has the carrier's Jacobian at the point placed from the attached pose; not held: zeros.  Still no
+recursion over the tree.  Not carried: a virtual payload with no body in the model, deciding what is grasped, grasp forces, an object attached to an attached
+object, derivatives.
 
 M^-1 (csrc/rsim_dyn_solve.hip, rsim_config_forward_dynamics / rsim_config_mass_solve / rsim_config_opspace): forward_dynamics, mass_solve and opspace are
 numpy.linalg.solve on this file's own mass_matrix, inverse_dynamics and site_jacobian; the kernel runs a Cholesky factorisation in fp32."""
@@ -76,9 +86,29 @@ def _column_rates(m, kin, col, v):
     return out
 
 
-def inverse_dynamics(flat, qpos, dofs, q, qd=None, qdd=None, overrides=None, model32=None):
-    """tau [n] of one candidate.  qpos: the env's [nq]; q / qd / qdd: [n] of the controlled dofs (None: zeros)"""
+def _payload(flat, m, qpos, dofs, q, attach, held, rel, now):
+    """the held bodies of one env at one candidate: ([(carrier, centre of mass, inertial frame [3, 3], mass, principal moments [3]), ...] one per held attached
+    body and body below it, {body: carrier} for them, (xpos, xquat) of clearance.fk's attached FK) -- on the tables of m"""
+    att = clearance._attachments(flat, dofs, attach)
+    if not att:
+        return [], {}, None
+    xpos, xquat = clearance.fk(flat, qpos, dofs, q, model32=m, attach=att, held=held, rel=rel, now=now)
+    ipos, iquat = np.asarray(m.body_ipos, dtype=np.float64).reshape(-1, 3), np.asarray(m.body_iquat, dtype=np.float64).reshape(-1, 4)
+    mass, inertia = np.asarray(m.body_mass, dtype=np.float64).ravel(), np.asarray(m.body_inertia, dtype=np.float64).reshape(-1, 3)
+    load, carrier_of = [], {}
+    for (body, carrier), h in zip(att, clearance._held_row(att, held)):
+        for b in clearance.subtree(flat, body) if h else ():
+            R = mjcf.quat2mat(xquat[b])
+            load.append((carrier, xpos[b] + R @ ipos[b], R @ mjcf.quat2mat(mjcf.quat_normalize(iquat[b])), float(mass[b]), inertia[b]))
+            carrier_of[b] = carrier
+    return load, carrier_of, (xpos, xquat)
+
+
+def inverse_dynamics(flat, qpos, dofs, q, qd=None, qdd=None, overrides=None, model32=None, attach=None, held=None, rel=None, now=None):
+    """tau [n] of one candidate.  qpos: the env's [nq]; q / qd / qdd: [n] of the controlled dofs (None: zeros); attach / held / rel / now: the env's carried
+    payload (the module's docstring)"""
     m = _model(flat, overrides, model32)
+    load = _payload(flat, m, qpos, dofs, q, attach, held, rel, now)[0]
     col = clearance._columns(flat, dofs)
     dofs = [int(d) for d in np.asarray(dofs).ravel()]
     kin = mjcf.kinematics_np(m, clearance.candidate_qpos(flat, qpos, dofs, q))
@@ -88,8 +118,10 @@ def inverse_dynamics(flat, qpos, dofs, q, qd=None, qdd=None, overrides=None, mod
     jtype, dadr = clearance._I(m, "jnt_type"), clearance._I(m, "jnt_dofadr")
     g = np.asarray(m.gravity, dtype=np.float64).ravel()
     tau = np.zeros(int(flat.nv))
-    for b in range(1, int(m.nbody)):
-        jp, jr = mjcf.body_jacobian_np(m, xpos, xmat, xanchor, xaxis, b, xipos[b])
+    # every body with its own Jacobian at its own centre of mass; a held body with its CARRIER's Jacobian at the held body's centre of mass
+    terms = [(b, xipos[b], ximat[b], float(m.body_mass[b]), m.body_inertia[b]) for b in range(1, int(m.nbody))] + load
+    for jb, com, imat, mass, inertia in terms:
+        jp, jr = mjcf.body_jacobian_np(m, xpos, xmat, xanchor, xaxis, jb, com)
         if not (np.any(jp[:, dofs]) or np.any(jr[:, dofs])):
             continue      # not moved
         omega, vc = jr @ v, jp @ v
@@ -101,29 +133,34 @@ def inverse_dynamics(flat, qpos, dofs, q, qd=None, qdd=None, overrides=None, mod
             if jtype[j] == mjcf.JNT_SLIDE:
                 acc += da * v[d]
             else:
-                acc += (np.cross(da, xipos[b] - xanchor[j]) + np.cross(xaxis[j], vc - dp)) * v[d]
+                acc += (np.cross(da, com - xanchor[j]) + np.cross(xaxis[j], vc - dp)) * v[d]
                 alpha += da * v[d]
-        Iw = ximat[b] @ np.diag(m.body_inertia[b]) @ ximat[b].T
-        tau += jp.T @ (float(m.body_mass[b]) * (acc - g)) + jr.T @ (Iw @ alpha + np.cross(omega, Iw @ omega))
+        Iw = imat @ np.diag(inertia) @ imat.T
+        tau += jp.T @ (mass * (acc - g)) + jr.T @ (Iw @ alpha + np.cross(omega, Iw @ omega))
     tau += np.asarray(m.dof_armature).ravel() * a + np.asarray(m.dof_damping).ravel() * v
     return tau[dofs]
 
 
-def gravity_torque(flat, qpos, dofs, q, overrides=None, model32=None):
-    return inverse_dynamics(flat, qpos, dofs, q, None, None, overrides, model32)
+def gravity_torque(flat, qpos, dofs, q, overrides=None, model32=None, attach=None, held=None, rel=None, now=None):
+    return inverse_dynamics(flat, qpos, dofs, q, None, None, overrides, model32, attach, held, rel, now)
 
 
-def mass_matrix(flat, qpos, dofs, q, overrides=None, model32=None):
-    """M [n, n]: the block of the joint-space inertia at the candidate on the controlled dofs, M = sum Jp^T m Jp + Jr^T I Jr + armature"""
+def mass_matrix(flat, qpos, dofs, q, overrides=None, model32=None, attach=None, held=None, rel=None, now=None):
+    """M [n, n]: the block of the joint-space inertia at the candidate on the controlled dofs, M = sum Jp^T m Jp + Jr^T I Jr + armature; a held body's term with
+    the carrier's Jacobian at its centre of mass"""
     m = _model(flat, overrides, model32)
     clearance._columns(flat, dofs)
     dofs = [int(d) for d in np.asarray(dofs).ravel()]
-    M, _ = mjcf.mass_matrix_np(m, clearance.candidate_qpos(flat, qpos, dofs, q))
+    M, (xpos, _, xmat, _, _, xanchor, xaxis) = mjcf.mass_matrix_np(m, clearance.candidate_qpos(flat, qpos, dofs, q))
+    for carrier, com, imat, mass, inertia in _payload(flat, m, qpos, dofs, q, attach, held, rel, now)[0]:
+        jp, jr = mjcf.body_jacobian_np(m, xpos, xmat, xanchor, xaxis, carrier, com)
+        M = M + mass * jp.T @ jp + jr.T @ (imat @ np.diag(inertia) @ imat.T) @ jr
     return M[np.ix_(dofs, dofs)]
 
 
-def site_jacobian(flat, qpos, site, dofs, q, overrides=None, model32=None):
-    """(jacp [3, n], jacr [3, n]): mj_jacSite at the candidate in the controlled columns"""
+def site_jacobian(flat, qpos, site, dofs, q, overrides=None, model32=None, attach=None, held=None, rel=None, now=None):
+    """(jacp [3, n], jacr [3, n]): mj_jacSite at the candidate in the controlled columns.  A site on a held body (or below one): the carrier's Jacobian at the
+    point placed from the attached pose; on one that is not held: zeros, as for any site no controlled dof moves"""
     m = _model(flat, overrides, model32)
     clearance._columns(flat, dofs)
     if not 0 <= int(site) < int(flat.nsite):
@@ -131,29 +168,34 @@ def site_jacobian(flat, qpos, site, dofs, q, overrides=None, model32=None):
     dofs = [int(d) for d in np.asarray(dofs).ravel()]
     xpos, _, xmat, _, _, xanchor, xaxis = mjcf.kinematics_np(m, clearance.candidate_qpos(flat, qpos, dofs, q))
     b = int(clearance._I(m, "site_bodyid")[int(site)])
-    p = xpos[b] + xmat[b] @ np.asarray(m.site_pos, dtype=np.float64).reshape(-1, 3)[int(site)]
-    jp, jr = mjcf.body_jacobian_np(m, xpos, xmat, xanchor, xaxis, b, p)
+    local = np.asarray(m.site_pos, dtype=np.float64).reshape(-1, 3)[int(site)]
+    _, carrier_of, poses = _payload(flat, m, qpos, dofs, q, attach, held, rel, now)
+    if b in carrier_of:
+        p = poses[0][b] + mjcf.quat2mat(poses[1][b]) @ local
+        jp, jr = mjcf.body_jacobian_np(m, xpos, xmat, xanchor, xaxis, carrier_of[b], p)
+    else:
+        jp, jr = mjcf.body_jacobian_np(m, xpos, xmat, xanchor, xaxis, b, xpos[b] + xmat[b] @ local)
     return jp[:, dofs], jr[:, dofs]
 
 
-def forward_dynamics(flat, qpos, dofs, q, qd=None, tau=None, overrides=None, model32=None):
-    """qdd [n] of one candidate: M(q)^-1 (tau - qfrc_bias(q, qd) - dof_damping qd), every other joint locked -- the exact inverse of inverse_dynamics, with its
-    limits (rsim_config_forward_dynamics).  tau None: zeros"""
-    bias = inverse_dynamics(flat, qpos, dofs, q, qd, None, overrides, model32)
+def forward_dynamics(flat, qpos, dofs, q, qd=None, tau=None, overrides=None, model32=None, attach=None, held=None, rel=None, now=None):
+    """qdd [n] of one candidate: M(q)^-1 (tau - qfrc_bias(q, qd) - dof_damping qd), every other joint locked -- the exact inverse of inverse_dynamics with the
+    same attachment, with its limits (rsim_config_forward_dynamics).  tau None: zeros"""
+    bias = inverse_dynamics(flat, qpos, dofs, q, qd, None, overrides, model32, attach, held, rel, now)
     t = np.zeros_like(bias) if tau is None else np.asarray(tau, dtype=np.float64).ravel()
-    return np.linalg.solve(mass_matrix(flat, qpos, dofs, q, overrides, model32), t - bias)
+    return np.linalg.solve(mass_matrix(flat, qpos, dofs, q, overrides, model32, attach, held, rel, now), t - bias)
 
 
-def mass_solve(flat, qpos, dofs, q, rhs, overrides=None, model32=None):
+def mass_solve(flat, qpos, dofs, q, rhs, overrides=None, model32=None, attach=None, held=None, rel=None, now=None):
     """x = M(q)^-1 rhs for rhs [n] or [n, r] (rsim_config_mass_solve)"""
-    return np.linalg.solve(mass_matrix(flat, qpos, dofs, q, overrides, model32), np.asarray(rhs, dtype=np.float64))
+    return np.linalg.solve(mass_matrix(flat, qpos, dofs, q, overrides, model32, attach, held, rel, now), np.asarray(rhs, dtype=np.float64))
 
 
-def opspace(flat, qpos, site, dofs, q, overrides=None, model32=None):
+def opspace(flat, qpos, site, dofs, q, overrides=None, model32=None, attach=None, held=None, rel=None, now=None):
     """(lambda_inv [6, 6], minv_jt [n, 6]) with J = [jacp; jacr] of site_jacobian: minv_jt = M^-1 J^T, lambda_inv = J M^-1 J^T (rsim_config_opspace).  The
     operational-space inertia is pinv(lambda_inv) -- lambda_inv is singular for n < 6 and at kinematic singularities -- and Jbar = minv_jt @ pinv(lambda_inv)."""
-    J = np.concatenate(site_jacobian(flat, qpos, site, dofs, q, overrides, model32), axis=0)
-    minv_jt = np.linalg.solve(mass_matrix(flat, qpos, dofs, q, overrides, model32), J.T)
+    J = np.concatenate(site_jacobian(flat, qpos, site, dofs, q, overrides, model32, attach, held, rel, now), axis=0)
+    minv_jt = np.linalg.solve(mass_matrix(flat, qpos, dofs, q, overrides, model32, attach, held, rel, now), J.T)
     return J @ minv_jt, minv_jt
 
 
@@ -165,12 +207,15 @@ def site_position(flat, qpos, site, dofs, q, overrides=None, model32=None):
     return xpos[b] + xmat[b] @ np.asarray(m.site_pos, dtype=np.float64).reshape(-1, 3)[int(site)]
 
 
-def potential_energy(flat, qpos, dofs, q, overrides=None, model32=None):
-    """- sum m g . xipos at the candidate (its gradient along the controlled dofs is the gravity torque)"""
+def potential_energy(flat, qpos, dofs, q, overrides=None, model32=None, attach=None, held=None, rel=None, now=None):
+    """- sum m g . xipos at the candidate (its gradient along the controlled dofs is the gravity torque); a held body counts at its attached pose -- where the
+    free body itself lies does not depend on q, so its own term is a constant and stays"""
     m = _model(flat, overrides, model32)
     dofs = [int(d) for d in np.asarray(dofs).ravel()]
     xipos = mjcf.kinematics_np(m, clearance.candidate_qpos(flat, qpos, dofs, q))[3]
-    return -float(np.asarray(m.body_mass).ravel() @ (xipos @ np.asarray(m.gravity, dtype=np.float64).ravel()))
+    g = np.asarray(m.gravity, dtype=np.float64).ravel()
+    held_part = sum(mass * float(com @ g) for _, com, _, mass, _ in _payload(flat, m, qpos, dofs, q, attach, held, rel, now)[0])
+    return -float(np.asarray(m.body_mass).ravel() @ (xipos @ g)) - held_part
 
 
 def path_derivatives(waypoints, dt):

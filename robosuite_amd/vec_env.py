@@ -400,7 +400,7 @@ class VecEnv:
             return names.index(site)
         return int(site)
 
-    def config_inverse_dynamics(self, q, qd=None, qdd=None, arm=0):
+    def config_inverse_dynamics(self, q, qd=None, qdd=None, arm=0, attach=None, held=None, rel=None):
         """Can the arm hold or execute this?  q (and qd, qdd, each None for zeros) [n_envs, K, n] (2-D for K = 1) candidate joint positions, velocities and
         accelerations of the arm -> tau [n_envs, K, n], the joint torques that produce qdd at (q, qd):  M qdd + Coriolis / centrifugal + gravity + joint
         damping, M with the armature (HipBatch.config_inverse_dynamics).  Every joint that is not the arm's -- fingers, objects, the other arm -- is held
@@ -409,47 +409,55 @@ class VecEnv:
             q, err, it, ok = env.solve_ik(pos, quat)
             holdable = ok & (env.config_gravity_torque(q).abs() <= limit).all(-1)
 
-        NOT included: tendon, fluid, friction loss, actuator, contact, equality and applied forces, and the payload of a grasped object."""
-        return self.env.batch.config_inverse_dynamics(self._arm_dofs("config_inverse_dynamics", arm), q, qd=qd, qdd=qdd)
+        THE PAYLOAD OF A GRASPED OBJECT counts only if the call says so, as in config_clearance: attach = [(body, carrier), ...] by name or id (carrier None:
+        the body of the arm's eef_site), held [n_envs] or [n_envs, n] (None: all held), rel [n_envs, n, 7] (None: the env's current poses).  In the envs that
+        hold it the object is rigid load on its carrier, with the env's own mass and inertia; an env that does not returns the empty-hand bits:
 
-    def config_gravity_torque(self, q, arm=0):
-        """The torques that hold the arm still at q: config_inverse_dynamics at zero velocity and acceleration (JOINT_TORQUE feed-forward)."""
-        return self.config_inverse_dynamics(q, arm=arm)
+            tau = env.config_gravity_torque(q, attach=[("cube_main", None)], held=grasped)
 
-    def config_mass_matrix(self, q, arm=0):
+        The same three arguments mean the same on config_gravity_torque, config_mass_matrix, config_jacobian, config_forward_dynamics, config_mass_solve,
+        config_opspace and path_torques.  NOT included: tendon, fluid, friction loss, actuator, contact, equality and applied forces; grasp forces."""
+        return self.env.batch.config_inverse_dynamics(self._arm_dofs("config_inverse_dynamics", arm), q, qd=qd, qdd=qdd, attach=self._attach_ids("config_inverse_dynamics", attach, arm), held=held, rel=rel)
+
+    def config_gravity_torque(self, q, arm=0, attach=None, held=None, rel=None):
+        """The torques that hold the arm still at q: config_inverse_dynamics at zero velocity and acceleration (JOINT_TORQUE feed-forward).  attach / held /
+        rel: with the object in hand."""
+        return self.config_inverse_dynamics(q, arm=arm, attach=attach, held=held, rel=rel)
+
+    def config_mass_matrix(self, q, arm=0, attach=None, held=None, rel=None):
         """The joint-space inertia of the arm at candidate joint vectors -> M [n_envs, K, n, n] (HipBatch.config_mass_matrix): every other joint locked,
         armature on the diagonal, symmetric bit for bit.  arm: as config_fk; with arm="both" the arm-to-arm blocks are exactly zero."""
-        return self.env.batch.config_mass_matrix(self._arm_dofs("config_mass_matrix", arm), q)
+        return self.env.batch.config_mass_matrix(self._arm_dofs("config_mass_matrix", arm), q, attach=self._attach_ids("config_mass_matrix", attach, arm), held=held, rel=rel)
 
-    def config_jacobian(self, q, arm=0, site=None):
+    def config_jacobian(self, q, arm=0, site=None, attach=None, held=None, rel=None):
         """mj_jacSite at candidate arm joint vectors -> (jacp, jacr) [n_envs, K, 3, n] in the arm's columns (HipBatch.config_jacobian).  site: a name or a
-        model site id; None: the arm's `eef_site`.  arm: as config_fk (site=None needs arm 0 or 1)."""
-        return self.env.batch.config_jacobian(self._arm_site("config_jacobian", arm, site), self._arm_dofs("config_jacobian", arm), q)
+        model site id; None: the arm's `eef_site`.  arm: as config_fk (site=None needs arm 0 or 1).  With attach the site may sit on the carried object."""
+        return self.env.batch.config_jacobian(self._arm_site("config_jacobian", arm, site), self._arm_dofs("config_jacobian", arm), q, attach=self._attach_ids("config_jacobian", attach, arm), held=held, rel=rel)
 
-    def config_forward_dynamics(self, q, qd=None, tau=None, arm=0, return_ok=False):
+    def config_forward_dynamics(self, q, qd=None, tau=None, arm=0, return_ok=False, attach=None, held=None, rel=None):
         """What acceleration does this torque give here?  q (and qd, tau, each None for zeros) [n_envs, K, n] (2-D for K = 1) candidate joint positions,
         velocities and joint torques of the arm -> qdd [n_envs, K, n] = M(q)^-1 (tau - Coriolis / centrifugal - gravity - joint damping)
         (HipBatch.config_forward_dynamics): the exact inverse of config_inverse_dynamics, with its conventions and its limits -- every joint that is not the
         arm's is locked, and no tendon, fluid, friction-loss, actuator, contact, equality or applied force acts.  return_ok=True: -> (qdd, ok bool
         [n_envs, K]); where ok is False M was not positive definite in fp32 and qdd is NaN.  arm: as config_fk."""
-        return self.env.batch.config_forward_dynamics(self._arm_dofs("config_forward_dynamics", arm), q, qd=qd, tau=tau, return_ok=return_ok)
+        return self.env.batch.config_forward_dynamics(self._arm_dofs("config_forward_dynamics", arm), q, qd=qd, tau=tau, return_ok=return_ok, attach=self._attach_ids("config_forward_dynamics", attach, arm), held=held, rel=rel)
 
-    def config_mass_solve(self, q, rhs, arm=0, return_ok=False):
+    def config_mass_solve(self, q, rhs, arm=0, return_ok=False, attach=None, held=None, rel=None):
         """M(q)^-1 rhs at candidate arm joint vectors: rhs [n_envs, K, n, r] (r <= 16) or [n_envs, K, n] -> x of rhs's shape (HipBatch.config_mass_solve)."""
-        return self.env.batch.config_mass_solve(self._arm_dofs("config_mass_solve", arm), q, rhs, return_ok=return_ok)
+        return self.env.batch.config_mass_solve(self._arm_dofs("config_mass_solve", arm), q, rhs, return_ok=return_ok, attach=self._attach_ids("config_mass_solve", attach, arm), held=held, rel=rel)
 
-    def config_opspace(self, q, arm=0, site=None, return_ok=False):
+    def config_opspace(self, q, arm=0, site=None, return_ok=False, attach=None, held=None, rel=None):
         """What is the end effector's apparent inertia here?  -> (lambda_inv [n_envs, K, 6, 6], minv_jt [n_envs, K, n, 6]) at candidate arm joint vectors
         (HipBatch.config_opspace): with J = [jacp; jacr] of config_jacobian, minv_jt = M^-1 J^T and lambda_inv = J M^-1 J^T, symmetric bit for bit.  The
         inertia itself takes a pseudo-inverse, as robosuite does it: Lambda = torch.linalg.pinv(lambda_inv), Jbar = minv_jt @ Lambda.  site, arm: as
         config_jacobian."""
-        return self.env.batch.config_opspace(self._arm_site("config_opspace", arm, site), self._arm_dofs("config_opspace", arm), q, return_ok=return_ok)
+        return self.env.batch.config_opspace(self._arm_site("config_opspace", arm, site), self._arm_dofs("config_opspace", arm), q, return_ok=return_ok, attach=self._attach_ids("config_opspace", attach, arm), held=held, rel=rel)
 
-    def path_torques(self, waypoints, dt, arm=0):
+    def path_torques(self, waypoints, dt, arm=0, attach=None, held=None, rel=None):
         """The torques along joint-space paths: is the motion executable, not merely collision-free?  waypoints [n_envs, K, W, n]: K paths per env of W arm
         joint vectors `dt` seconds apart -> tau [n_envs, K, W, n].  Velocities are central differences of the waypoints, one-sided at the two ends, and
         accelerations the same differences of the velocities, formed in torch; then ONE config_inverse_dynamics call on the K W candidates.  Compare
-        tau.abs().amax(2) with the actuators' limits."""
+        tau.abs().amax(2) with the actuators' limits.  attach / held / rel: the torques with the object in hand, as config_inverse_dynamics."""
         import torch
 
         if not (isinstance(waypoints, torch.Tensor) and waypoints.dim() == 4 and waypoints.shape[2] >= 2):
@@ -461,7 +469,7 @@ class VecEnv:
         qd = torch.gradient(w, spacing=float(dt), dim=2)[0]
         qdd = torch.gradient(qd, spacing=float(dt), dim=2)[0]
         flat = lambda x: x.reshape(B, K * W, n)      # noqa: E731
-        return self.config_inverse_dynamics(flat(w), qd=flat(qd), qdd=flat(qdd), arm=arm).reshape(B, K, W, n)
+        return self.config_inverse_dynamics(flat(w), qd=flat(qd), qdd=flat(qdd), arm=arm, attach=attach, held=held, rel=rel).reshape(B, K, W, n)
 
     def enable_applied_forces(self, on: bool = True):
         """Honour `qfrc_applied` and `xfrc_applied` in `step` (off by default: the control step then reads neither).  An env that reports `done`
