@@ -327,6 +327,11 @@ def lib():
             for f in ("rsim_config_inverse_dynamics", "rsim_config_mass_matrix", "rsim_config_jacobian", "rsim_config_forward_dynamics", "rsim_config_mass_solve",
                       "rsim_config_opspace"):
                 getattr(L, f + "_attached").argtypes = list(getattr(L, f).argtypes) + [C.POINTER(Attach)]
+        if hasattr(L, "rsim_config_inverse_dynamics_grad"):     # (as above)
+            head = [vp, C.c_int, C.POINTER(C.c_int32), C.c_int, vp]
+            L.rsim_config_inverse_dynamics_grad.argtypes = head + [vp] * 5
+            L.rsim_config_inverse_dynamics_jvp.argtypes = head + [vp] * 6
+            L.rsim_config_forward_dynamics_grad.argtypes = head + [vp] * 6
         L.rsim_comm_unique_id.argtypes = [vp, C.c_size_t]
         L.rsim_comm_create.argtypes = [vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
         L.rsim_allreduce_stats.argtypes = [vp, vp, C.c_int, C.c_int]
@@ -1387,6 +1392,68 @@ class HipBatch:
         self._ray_fence_out()
         lam, mjt, ok = (lam[:, 0], mjt[:, 0], ok[:, 0] != 0) if flat2 else (lam, mjt, ok != 0)
         return (lam, mjt, ok) if return_ok else (lam, mjt)
+
+    # ---- derivatives of the dynamics at candidates (include/rsim.h rsim_config_inverse_dynamics_grad / _jvp / rsim_config_forward_dynamics_grad,
+    # csrc/rsim_dyn_grad.hip) -------------------------------------------------------------------------------------------------------------------------------
+    def _dyn_grad_head(self, who, dofs, q):
+        if not hasattr(self._L, "rsim_config_inverse_dynamics_grad"):
+            raise RsimError(f"{who}: the loaded library has no rsim_{who}")
+        return self._dyn_head(who, dofs, q)
+
+    def config_inverse_dynamics_grad(self, dofs, q, qd=None, qdd=None):
+        """config_inverse_dynamics and its analytic first derivatives at candidate joint vectors: -> (tau float32 [B, K, n], dtau_dq, dtau_dqd float32
+        [B, K, n, n]) (without the K axis for 2-D q), entry [i, j] = d tau_i / d q_j (resp. qd_j) at (q, qd, qdd).  tau is config_inverse_dynamics's, bit
+        for bit; d tau / d qdd is config_mass_matrix.  Arguments and rules as config_inverse_dynamics, without attach.  A tangent Newton-Euler walk per
+        direction on the device, 2 n of them in a loop inside the lane; robosuite_amd/dynamics.py inverse_dynamics_grad is the fp64 statement by the
+        definition of a derivative.  Joints that are not controlled are held and are no direction."""
+        import torch
+
+        who = "config_inverse_dynamics_grad"
+        head, qc, K, flat2, n = self._dyn_grad_head(who, dofs, q)
+        v, a = self._config_like(who, "qd", qd, qc), self._config_like(who, "qdd", qdd, qc)
+        tau = torch.empty((self.B, K, n), dtype=torch.float32, device=qc.device)
+        gq = torch.empty((self.B, K, n, n), dtype=torch.float32, device=qc.device)
+        gv = torch.empty_like(gq)
+        self._ray_fence_in()
+        _chk(self._L.rsim_config_inverse_dynamics_grad(self.ptr, *head, *(C.c_void_p(t.data_ptr()) if t is not None else None for t in (v, a, tau, gq, gv))))
+        self._ray_fence_out()
+        return (tau[:, 0], gq[:, 0], gv[:, 0]) if flat2 else (tau, gq, gv)
+
+    def config_inverse_dynamics_jvp(self, dofs, q, qd, qdd, dq=None, dqd=None, dqdd=None):
+        """The derivative of config_inverse_dynamics at (q, qd, qdd) along ONE direction per candidate: -> dtau float32 [B, K, n] ([B, n] for 2-D q),
+        dtau = dtau_dq dq + dtau_dqd dqd + M dqdd in one tangent walk.  qd / qdd and dq / dqd / dqdd: each q's shape, or None for zeros.  Within rounding of
+        the product of config_inverse_dynamics_grad's blocks and config_mass_matrix, not bit for bit."""
+        import torch
+
+        who = "config_inverse_dynamics_jvp"
+        head, qc, K, flat2, n = self._dyn_grad_head(who, dofs, q)
+        ins = [self._config_like(who, name, x, qc) for name, x in (("qd", qd), ("qdd", qdd), ("dq", dq), ("dqd", dqd), ("dqdd", dqdd))]
+        dtau = torch.empty((self.B, K, n), dtype=torch.float32, device=qc.device)
+        self._ray_fence_in()
+        _chk(self._L.rsim_config_inverse_dynamics_jvp(self.ptr, *head, *(C.c_void_p(t.data_ptr()) if t is not None else None for t in ins + [dtau])))
+        self._ray_fence_out()
+        return dtau[:, 0] if flat2 else dtau
+
+    def config_forward_dynamics_grad(self, dofs, q, qd=None, tau=None, return_ok=False):
+        """config_forward_dynamics and its analytic first derivatives: -> (qdd float32 [B, K, n], dqdd_dq, dqdd_dqd float32 [B, K, n, n]) (without the K
+        axis for 2-D q; return_ok=True: ok bool [B, K] behind them).  qdd and ok are config_forward_dynamics's, bit for bit; dqdd_dq = -M^-1 dtau_dq and
+        dqdd_dqd = -M^-1 dtau_dqd with the blocks of config_inverse_dynamics_grad AT (q, qd, qdd) -- the linearisation qdd = f(q, qd, tau) of iLQR / MPC.
+        d qdd / d tau is M^-1: config_mass_solve(dofs, q, identity); it is not returned here.  Where ok is False all three outputs of the candidate are
+        NaN; no other candidate is affected.  Arguments and rules as config_forward_dynamics, without attach."""
+        import torch
+
+        who = "config_forward_dynamics_grad"
+        head, qc, K, flat2, n = self._dyn_grad_head(who, dofs, q)
+        v, t = self._config_like(who, "qd", qd, qc), self._config_like(who, "tau", tau, qc)
+        qdd = torch.empty((self.B, K, n), dtype=torch.float32, device=qc.device)
+        gq = torch.empty((self.B, K, n, n), dtype=torch.float32, device=qc.device)
+        gv = torch.empty_like(gq)
+        ok = torch.empty((self.B, K), dtype=torch.int32, device=qc.device)
+        self._ray_fence_in()
+        _chk(self._L.rsim_config_forward_dynamics_grad(self.ptr, *head, *(C.c_void_p(x.data_ptr()) if x is not None else None for x in (v, t, qdd, gq, gv, ok))))
+        self._ray_fence_out()
+        out = (qdd[:, 0], gq[:, 0], gv[:, 0], ok[:, 0] != 0) if flat2 else (qdd, gq, gv, ok != 0)
+        return out if return_ok else out[:3]
 
     # ---- collision-aware inverse kinematics (include/rsim.h rsim_ik_site_avoid, csrc/rsim_ik_avoid.hip) ---------------------------------------------------
     def ik_avoid_tables(self):

@@ -153,6 +153,21 @@ class BatchState:
         (lambda_inv [B, K, 6, 6], minv_jt [B, K, n, 6]).  Lambda = pinv(lambda_inv) is the caller's, as in TorchOSCPoseController.torques_from."""
         return self.batch.config_opspace(site, dofs, q, return_ok=return_ok, attach=attach, held=held, rel=rel)
 
+    def config_inverse_dynamics_grad(self, dofs, q, qd=None, qdd=None):
+        """config_inverse_dynamics and its analytic first derivatives, away from the state (HipBatch.config_inverse_dynamics_grad): -> (tau, dtau_dq
+        [B, K, n, n], dtau_dqd [B, K, n, n]).  d tau / d qdd is config_mass_matrix.  No attach."""
+        return self.batch.config_inverse_dynamics_grad(dofs, q, qd=qd, qdd=qdd)
+
+    def config_inverse_dynamics_jvp(self, dofs, q, qd, qdd, dq=None, dqd=None, dqdd=None):
+        """The derivative of config_inverse_dynamics along one direction per candidate, away from the state (HipBatch.config_inverse_dynamics_jvp): -> dtau
+        [B, K, n]."""
+        return self.batch.config_inverse_dynamics_jvp(dofs, q, qd, qdd, dq=dq, dqd=dqd, dqdd=dqdd)
+
+    def config_forward_dynamics_grad(self, dofs, q, qd=None, tau=None, return_ok=False):
+        """config_forward_dynamics and its analytic first derivatives, away from the state (HipBatch.config_forward_dynamics_grad): -> (qdd, dqdd_dq
+        [B, K, n, n], dqdd_dqd [B, K, n, n]); return_ok=True: ok bool [B, K] behind them.  d qdd / d tau is config_mass_solve of the identity."""
+        return self.batch.config_forward_dynamics_grad(dofs, q, qd=qd, tau=tau, return_ok=return_ok)
+
     def body_dofs(self, body: int):
         """bool [nv]: the dofs that move `body` (its own joints and those of its ancestors)."""
         import torch

@@ -97,6 +97,8 @@ extern "C" int rsim_launch_randomize(const DModel* m, const DBatch* b, const DDr
 #include "rsim_dyn_core.h"
 #include "rsim_dyn_att.h"
 #include "rsim_dyn_solve.h"
+#include "rsim_dyn_grad.h"
+#include "rsim_dyn_grad_core.h"
 #include "rsim_sweep.h"
 #include "rsim_hull.h"
 
@@ -265,6 +267,9 @@ struct rsim_batch {
   // dynamics queries (rsim_dyn.hip): the per-body words of the two walks, grown on demand by the first call that asks
   float* d_dyn_scr;
   size_t dyn_scr_n;
+  // derivatives of the dynamics (rsim_dyn_grad.hip): the tangent words of one direction, grown on demand by the first call that asks
+  float* d_dyn_tan;
+  size_t dyn_tan_n;
   // M^-1 queries (rsim_dyn_solve.hip): M [B K][n][n] and the bias torques or the site Jacobian, as k_dyn_crb / k_dyn_rne / k_dyn_jac leave them for k_dyn_solve,
   // grown on demand by the first call that asks
   float *d_solve_M, *d_solve_in;
@@ -1160,6 +1165,7 @@ extern "C" void rsim_batch_free(rsim_batch* b) {
   for (auto& kv : b->dist_tables) hipFree(kv.second);
   for (auto& kv : b->clear_tabs) { hipFree(kv.second.d_tab); hipFree(kv.second.d_slot); if (kv.second.d_att) hipFree(kv.second.d_att); if (kv.second.d_sig) hipFree(kv.second.d_sig); if (kv.second.d_cols) hipFree(kv.second.d_cols); }
   if (b->d_dyn_scr) hipFree(b->d_dyn_scr);
+  if (b->d_dyn_tan) hipFree(b->d_dyn_tan);
   if (b->d_solve_M) hipFree(b->d_solve_M);
   if (b->d_solve_in) hipFree(b->d_solve_in);
   if (b->d_grad_jscr) hipFree(b->d_grad_jscr);
@@ -3093,6 +3099,83 @@ extern "C" int rsim_config_opspace_attached(rsim_batch* b, int site, int ndof, c
 extern "C" int rsim_config_opspace(rsim_batch* b, int site, int ndof, const int32_t* dof_ids, int k, const float* q_dev, float* lambda_inv_dev, float* minv_jt_dev,
                                    int32_t* ok_dev) {
   return rsim_config_opspace_attached(b, site, ndof, dof_ids, k, q_dev, lambda_inv_dev, minv_jt_dev, ok_dev, nullptr);
+}
+
+// ---- derivatives of the dynamics at candidates (rsim_dyn_grad.hip, include/rsim.h rsim_config_inverse_dynamics_grad / rsim_config_inverse_dynamics_jvp /
+// rsim_config_forward_dynamics_grad): dyn_args above without attachments, the unchanged k_clear_fk, k_clear_joints and k_dyn_rne at the point of linearisation,
+// then the tangent walk, which only reads what they left.  The tangent scratch is the batch's, grown by the first call that asks.
+static int dyn_grad_args(rsim_batch* b, const DDyn& d, DDynGrad* g) {
+  memset(g, 0, sizeof(*g));
+  g->d = d;
+  if (clear_grow(b, &b->d_dyn_tan, &b->dyn_tan_n, (size_t)d.g.c.nslot * RSIM_DYN_TAN_WORDS * d.g.c.NC)) return 1;
+  g->tscr = b->d_dyn_tan;
+  return 0;
+}
+extern "C" int rsim_config_inverse_dynamics_grad(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, const float* qd_dev,
+                                                 const float* qdd_dev, float* tau_dev, float* dtau_dq_dev, float* dtau_dqd_dev) {
+  const char* who = "rsim_config_inverse_dynamics_grad";
+  if (!b) return fail("%s: batch is NULL", who);
+  if (!tau_dev || !dtau_dq_dev || !dtau_dqd_dev) return fail("%s: %s is NULL", who, !tau_dev ? "tau_dev" : !dtau_dq_dev ? "dtau_dq_dev" : "dtau_dqd_dev");
+  DDyn d;
+  const ClearTab* tab;
+  if (dyn_args(b, who, ndof, dof_ids, k, q_dev, RSIM_DYN_RNE_WORDS, &d, &tab, nullptr)) return 1;
+  d.qd = qd_dev; d.qdd = qdd_dev; d.tau = tau_dev;
+  DDynGrad g;
+  if (dyn_grad_args(b, d, &g)) return 1;
+  g.dtau_dq = dtau_dq_dev; g.dtau_dqd = dtau_dqd_dev;
+  int e = rsim_launch_clear_fk(&d.g.c, b->stream);
+  if (!e) e = rsim_launch_clear_joints(&d.g, b->stream);
+  if (!e) e = rsim_launch_dyn_rne(&d, b->stream);
+  if (!e) e = rsim_launch_dyn_rne_grad(&g, b->stream);
+  return launched(who, e);
+}
+extern "C" int rsim_config_inverse_dynamics_jvp(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, const float* qd_dev,
+                                                const float* qdd_dev, const float* dq_dev, const float* dqd_dev, const float* dqdd_dev, float* dtau_dev) {
+  const char* who = "rsim_config_inverse_dynamics_jvp";
+  if (!b) return fail("%s: batch is NULL", who);
+  if (!dtau_dev) return fail("%s: dtau_dev is NULL", who);
+  DDyn d;
+  const ClearTab* tab;
+  if (dyn_args(b, who, ndof, dof_ids, k, q_dev, RSIM_DYN_RNE_WORDS, &d, &tab, nullptr)) return 1;
+  d.qd = qd_dev; d.qdd = qdd_dev;
+  d.tau = dtau_dev;   // k_dyn_rne's torques are not asked for: they pass through the result's words, every one of which the tangent walk then writes
+  DDynGrad g;
+  if (dyn_grad_args(b, d, &g)) return 1;
+  g.dq = dq_dev; g.dqd = dqd_dev; g.dqdd = dqdd_dev; g.dtau = dtau_dev;
+  int e = rsim_launch_clear_fk(&d.g.c, b->stream);
+  if (!e) e = rsim_launch_clear_joints(&d.g, b->stream);
+  if (!e) e = rsim_launch_dyn_rne(&d, b->stream);
+  if (!e) e = rsim_launch_dyn_rne_jvp(&g, b->stream);
+  return launched(who, e);
+}
+// rsim_config_forward_dynamics's chain and bits for qdd and ok; then k_dyn_rne at (q, qd, qdd), the tangent walk with the negate flag straight into the two
+// results, and the unchanged k_dyn_solve on each of them in place as n right-hand-side columns (M is still in its scratch)
+extern "C" int rsim_config_forward_dynamics_grad(rsim_batch* b, int ndof, const int32_t* dof_ids, int k, const float* q_dev, const float* qd_dev,
+                                                 const float* tau_dev, float* qdd_dev, float* dqdd_dq_dev, float* dqdd_dqd_dev, int32_t* ok_dev) {
+  const char* who = "rsim_config_forward_dynamics_grad";
+  if (!b) return fail("%s: batch is NULL", who);
+  if (!qdd_dev || !dqdd_dq_dev || !dqdd_dqd_dev) return fail("%s: %s is NULL", who, !qdd_dev ? "qdd_dev" : !dqdd_dq_dev ? "dqdd_dq_dev" : "dqdd_dqd_dev");
+  DDyn d;
+  const ClearTab* tab;
+  if (dyn_args(b, who, ndof, dof_ids, k, q_dev, RSIM_DYN_RNE_WORDS, &d, &tab, nullptr)) return 1;
+  DDynGrad g;
+  if (dyn_grad_args(b, d, &g)) return 1;   // (every allocation before the first launch)
+  DSolve s;
+  memset(&s, 0, sizeof(s));
+  d.qd = qd_dev;
+  s.mode = RSIM_SOLVE_FD; s.tau = tau_dev; s.x = qdd_dev; s.ok = ok_dev;
+  if (solve_run(who, b, d, s, ndof, true, false)) return 1;
+  d.qdd = qdd_dev; d.tau = b->d_solve_in;   // (the bias torques there have been used)
+  g.d = d;
+  g.dtau_dq = dqdd_dq_dev; g.dtau_dqd = dqdd_dqd_dev; g.negate = 1;
+  int e = rsim_launch_dyn_rne(&d, b->stream);
+  if (!e) e = rsim_launch_dyn_rne_grad(&g, b->stream);
+  s.mode = RSIM_SOLVE_RHS; s.nrhs = ndof; s.ok = nullptr;
+  s.rhs = dqdd_dq_dev; s.x = dqdd_dq_dev;
+  if (!e) e = rsim_launch_dyn_solve(&s, b->stream);
+  s.rhs = dqdd_dqd_dev; s.x = dqdd_dqd_dev;
+  if (!e) e = rsim_launch_dyn_solve(&s, b->stream);
+  return launched(who, e);
 }
 
 // ---- swept clearance (rsim_sweep.hip, include/rsim.h rsim_config_sweep / rsim_config_motion_bound) -----------------------------------------------------------

@@ -28,7 +28,12 @@ recursion over the tree.  Not carried: a virtual payload with no body in the mod
 object, derivatives.
 
 M^-1 (csrc/rsim_dyn_solve.hip, rsim_config_forward_dynamics / rsim_config_mass_solve / rsim_config_opspace): forward_dynamics, mass_solve and opspace are
-numpy.linalg.solve on this file's own mass_matrix, inverse_dynamics and site_jacobian; the kernel runs a Cholesky factorisation in fp32."""
+numpy.linalg.solve on this file's own mass_matrix, inverse_dynamics and site_jacobian; the kernel runs a Cholesky factorisation in fp32.
+
+DERIVATIVES (csrc/rsim_dyn_grad.hip, rsim_config_inverse_dynamics_grad / rsim_config_inverse_dynamics_jvp / rsim_config_forward_dynamics_grad):
+inverse_dynamics_grad, inverse_dynamics_jvp and forward_dynamics_grad are the DEFINITION OF A DERIVATIVE on this file's own inverse_dynamics, mass_matrix and
+forward_dynamics -- Richardson-extrapolated central differences in q, single central differences in qd and qdd, where they are exact -- while the kernel runs
+a tangent (forward-mode) recursive Newton-Euler.  Without attach."""
 from collections import OrderedDict
 
 import numpy as np
@@ -197,6 +202,63 @@ def opspace(flat, qpos, site, dofs, q, overrides=None, model32=None, attach=None
     J = np.concatenate(site_jacobian(flat, qpos, site, dofs, q, overrides, model32, attach, held, rel, now), axis=0)
     minv_jt = np.linalg.solve(mass_matrix(flat, qpos, dofs, q, overrides, model32, attach, held, rel, now), J.T)
     return J @ minv_jt, minv_jt
+
+
+GRAD_H = 1e-3      # the first step of the differences in q below (rad, m); the second is half of it
+
+
+def _richardson(f, h):
+    """central difference of f at 0 with one Richardson step from (h, h / 2): the h^2 term of the error cancels, h^4 / 80 f^(5) is left"""
+    coarse, fine = (f(h) - f(-h)) / (2.0 * h), (f(0.5 * h) - f(-0.5 * h)) / h
+    return (4.0 * fine - coarse) / 3.0
+
+
+def _vec(x, n):
+    return np.zeros(n) if x is None else np.asarray(x, dtype=np.float64).ravel()
+
+
+def inverse_dynamics_jvp(flat, qpos, dofs, q, qd=None, qdd=None, dq=None, dqd=None, dqdd=None, overrides=None, model32=None, h=GRAD_H):
+    """dtau [n]: the derivative of inverse_dynamics at (q, qd, qdd) in the direction (dq, dqd, dqdd) (None: zeros), BY THE DEFINITION OF A DERIVATIVE on this
+    file's own inverse_dynamics (rsim_config_inverse_dynamics_jvp; the kernel runs a tangent recursive Newton-Euler, with which this shares nothing).  Along dq:
+    central differences with one Richardson step from h and h / 2.  Along dqd: one central difference, exact for any step because tau is quadratic in qd.  Along
+    dqdd: one central difference, exact because tau is linear in qdd -- that share is M dqdd.
+    The device differentiates with the STORED joint axis a_j (the column is a_j, the angle turns about a_j / |a_j|), so the true derivative of the statement
+    differs from the device's recursion by a factor |a_j| per column j of d/dq: relative, at most about 2^-23 for an fp32-rounded unit axis (4.9e-9 of the
+    scale on scene D of the tests)."""
+    n = len(np.asarray(dofs).ravel())
+    q, qd, qdd = _vec(q, n), _vec(qd, n), _vec(qdd, n)
+    f = lambda a, b, c: inverse_dynamics(flat, qpos, dofs, a, b, c, overrides, model32)
+    out = np.zeros(n)
+    if dq is not None and np.any(dq):
+        d = _vec(dq, n)
+        out += _richardson(lambda s: f(q + s * d, qd, qdd), h)
+    if dqd is not None and np.any(dqd):
+        d = _vec(dqd, n)
+        out += 0.5 * (f(q, qd + d, qdd) - f(q, qd - d, qdd))
+    if dqdd is not None and np.any(dqdd):
+        d = _vec(dqdd, n)
+        out += 0.5 * (f(q, qd, qdd + d) - f(q, qd, qdd - d))
+    return out
+
+
+def inverse_dynamics_grad(flat, qpos, dofs, q, qd=None, qdd=None, overrides=None, model32=None, h=GRAD_H):
+    """(tau [n], dtau_dq [n, n], dtau_dqd [n, n]) of one candidate, entry [i, j] = d tau_i / d q_j (resp. qd_j): column j is inverse_dynamics_jvp along e_j
+    (rsim_config_inverse_dynamics_grad).  d tau / d qdd is mass_matrix."""
+    n = len(np.asarray(dofs).ravel())
+    eye = np.eye(n)
+    gq = np.stack([inverse_dynamics_jvp(flat, qpos, dofs, q, qd, qdd, eye[j], None, None, overrides, model32, h) for j in range(n)], axis=1)
+    gv = np.stack([inverse_dynamics_jvp(flat, qpos, dofs, q, qd, qdd, None, eye[j], None, overrides, model32, h) for j in range(n)], axis=1)
+    return inverse_dynamics(flat, qpos, dofs, q, qd, qdd, overrides, model32), gq, gv
+
+
+def forward_dynamics_grad(flat, qpos, dofs, q, qd=None, tau=None, overrides=None, model32=None, h=GRAD_H):
+    """(qdd [n], dqdd_dq [n, n], dqdd_dqd [n, n]) of one candidate (rsim_config_forward_dynamics_grad): with qdd = forward_dynamics(q, qd, tau), the implicit
+    function theorem on tau = inverse_dynamics(q, qd, qdd) gives dqdd/dq = -M^-1 dtau/dq and dqdd/dqd = -M^-1 dtau/dqd, both AT (q, qd, qdd); dqdd/dtau is
+    M^-1 itself (mass_solve of the identity)."""
+    qdd = forward_dynamics(flat, qpos, dofs, q, qd, tau, overrides, model32)
+    _, gq, gv = inverse_dynamics_grad(flat, qpos, dofs, q, qd, qdd, overrides, model32, h)
+    M = mass_matrix(flat, qpos, dofs, q, overrides, model32)
+    return qdd, -np.linalg.solve(M, gq), -np.linalg.solve(M, gv)
 
 
 def site_position(flat, qpos, site, dofs, q, overrides=None, model32=None):

@@ -453,22 +453,56 @@ class VecEnv:
         config_jacobian."""
         return self.env.batch.config_opspace(self._arm_site("config_opspace", arm, site), self._arm_dofs("config_opspace", arm), q, return_ok=return_ok, attach=self._attach_ids("config_opspace", attach, arm), held=held, rel=rel)
 
-    def path_torques(self, waypoints, dt, arm=0, attach=None, held=None, rel=None):
+    def config_inverse_dynamics_grad(self, q, qd=None, qdd=None, arm=0):
+        """config_inverse_dynamics and its analytic first derivatives at candidate arm joint vectors -> (tau [n_envs, K, n], dtau_dq, dtau_dqd
+        [n_envs, K, n, n]), entry [i, j] = d tau_i / d q_j (resp. qd_j) (HipBatch.config_inverse_dynamics_grad); d tau / d qdd is config_mass_matrix.
+        tau is config_inverse_dynamics's, bit for bit.  arm: as config_fk.  No attach."""
+        return self.env.batch.config_inverse_dynamics_grad(self._arm_dofs("config_inverse_dynamics_grad", arm), q, qd=qd, qdd=qdd)
+
+    def config_inverse_dynamics_jvp(self, q, qd, qdd, dq=None, dqd=None, dqdd=None, arm=0):
+        """The derivative of config_inverse_dynamics at (q, qd, qdd) along one direction (dq, dqd, dqdd) per candidate, each None for zeros -> dtau
+        [n_envs, K, n], in one tangent walk on the device (HipBatch.config_inverse_dynamics_jvp)."""
+        return self.env.batch.config_inverse_dynamics_jvp(self._arm_dofs("config_inverse_dynamics_jvp", arm), q, qd, qdd, dq=dq, dqd=dqd, dqdd=dqdd)
+
+    def config_forward_dynamics_grad(self, q, qd=None, tau=None, arm=0, return_ok=False):
+        """The linearisation qdd = f(q, qd, tau) of the arm at candidates, for iLQR / MPC -> (qdd [n_envs, K, n], dqdd_dq, dqdd_dqd [n_envs, K, n, n])
+        (HipBatch.config_forward_dynamics_grad; return_ok=True: ok behind them).  qdd and ok are config_forward_dynamics's, bit for bit; d qdd / d tau is
+        M^-1: config_mass_solve(q, identity).  No attach."""
+        return self.env.batch.config_forward_dynamics_grad(self._arm_dofs("config_forward_dynamics_grad", arm), q, qd=qd, tau=tau, return_ok=return_ok)
+
+    def inverse_dynamics(self, q, qd=None, qdd=None, arm=0):
+        """config_inverse_dynamics as a DIFFERENTIABLE torch value: forward returns the plain call's bits; backward contracts the output's gradient with the
+        device's analytic blocks, g_q = g . dtau_dq, g_qd = g . dtau_dqd, g_qdd = M g --
+
+            q.requires_grad_(True)
+            env.inverse_dynamics(q, qd, qdd).square().sum().backward()      # q.grad is filled
+
+        The blocks are computed only if q or qd needs a gradient, config_mass_matrix only if qdd does; nothing is computed for an input that needs none.
+        First order only (no second derivatives).  No attach."""
+        return _inverse_dynamics_fn().apply(self, arm, q, qd, qdd)
+
+    def path_torques(self, waypoints, dt, arm=0, attach=None, held=None, rel=None, differentiable=False):
         """The torques along joint-space paths: is the motion executable, not merely collision-free?  waypoints [n_envs, K, W, n]: K paths per env of W arm
         joint vectors `dt` seconds apart -> tau [n_envs, K, W, n].  Velocities are central differences of the waypoints, one-sided at the two ends, and
         accelerations the same differences of the velocities, formed in torch; then ONE config_inverse_dynamics call on the K W candidates.  Compare
-        tau.abs().amax(2) with the actuators' limits.  attach / held / rel: the torques with the object in hand, as config_inverse_dynamics."""
+        tau.abs().amax(2) with the actuators' limits.  attach / held / rel: the torques with the object in hand, as config_inverse_dynamics.
+        differentiable=True: the one device call goes through inverse_dynamics, so path_torques(w, dt, differentiable=True).square().sum().backward() fills
+        w.grad -- the effort cost of a trajectory optimiser, beside collision_cost.  It does not carry attach."""
         import torch
 
         if not (isinstance(waypoints, torch.Tensor) and waypoints.dim() == 4 and waypoints.shape[2] >= 2):
             raise ValueError(f"path_torques: waypoints must be a tensor [n_envs, K, W, n] with W >= 2, got {tuple(getattr(waypoints, 'shape', ()))}")
         if not dt > 0:
             raise ValueError(f"path_torques: dt {dt!r} is not > 0")
+        if differentiable and attach is not None:
+            raise ValueError("path_torques: differentiable=True does not carry attach (the derivatives of the dynamics have no attached form)")
         B, K, W, n = waypoints.shape
         w = waypoints.float()
         qd = torch.gradient(w, spacing=float(dt), dim=2)[0]
         qdd = torch.gradient(qd, spacing=float(dt), dim=2)[0]
         flat = lambda x: x.reshape(B, K * W, n)      # noqa: E731
+        if differentiable:
+            return self.inverse_dynamics(flat(w), flat(qd), flat(qdd), arm=arm).reshape(B, K, W, n)
         return self.config_inverse_dynamics(flat(w), qd=flat(qd), qdd=flat(qdd), arm=arm, attach=attach, held=held, rel=rel).reshape(B, K, W, n)
 
     def enable_applied_forces(self, on: bool = True):
@@ -534,6 +568,38 @@ def _collision_cost_fn():
 
         _COST_FN = CollisionCost
     return _COST_FN
+
+
+_ID_FN = None
+
+
+def _inverse_dynamics_fn():
+    """the torch.autograd.Function behind VecEnv.inverse_dynamics (built on first use: this module does not import torch)"""
+    global _ID_FN
+    if _ID_FN is None:
+        import torch
+
+        class InverseDynamics(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, env, arm, q, qd, qdd):
+                det = lambda x: None if x is None else x.detach()      # noqa: E731
+                need_q, need_qd, need_qdd = ctx.needs_input_grad[2:5]
+                if need_q or need_qd:
+                    tau, gq, gv = env.config_inverse_dynamics_grad(det(q), det(qd), det(qdd), arm=arm)
+                else:
+                    tau, gq, gv = env.config_inverse_dynamics(det(q), det(qd), det(qdd), arm=arm), None, None
+                M = env.config_mass_matrix(det(q), arm=arm) if need_qdd else None
+                ctx.save_for_backward(gq if need_q else None, gv if need_qd else None, M)
+                return tau
+
+            @staticmethod
+            def backward(ctx, g):
+                gq, gv, M = ctx.saved_tensors
+                vjp = lambda J: None if J is None else torch.einsum("...i,...ij->...j", g, J)      # noqa: E731
+                return None, None, vjp(gq), vjp(gv), vjp(M)      # (M is symmetric bit for bit: g . M = M g)
+
+        _ID_FN = InverseDynamics
+    return _ID_FN
 
 
 def gym_flags(end_reason):
